@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the hot path (BASELINE.json):
 images/sec tagged (ViT-B/16 @448 forward + sigmoid + MCut tag selection, bf16 MFMA, batch 64 per
-GPU, inputs resident in HBM) on N GPUs of one node, plus -- on rank 0 at N=1 -- top-k queries/sec
-over a 100k-document index and the CPU restatement ("port") timed on the host cores.
+GPU, inputs resident in HBM) on N GPUs of one node.  With --full, also the per-kernel breakdown and
+roofline, an output self-check, a sustained run and -- on rank 0 at N=1 -- CCIP, EVA02, the input
+pipeline, top-k queries/sec over a 100k-document index and the CPU restatement ("port") timed on the
+host cores.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one pass of the tagging path over one batch of 64 synthetic images per rank
 (config.workload).  Rank 0 prints ONE JSON line on stdout; everything else goes to stderr.
+--dump-outputs DIR writes what the last timed step returned (rank 0): DIR/probs.npy (float32
+[64, classes]) and DIR/tag_rows.npy (the int32 tag rows as float64, [N * 64, 256]).  Inputs are
+seeded, so two runs with the same arguments see the same images and weights.
 """
 import argparse
 import json
@@ -502,10 +507,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-query", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel breakdown and roofline (HIP events in the timed region), output "
+                         "self-check, sustained run, kernel-alone pass, CCIP / EVA02 / input pipeline / query sections, CPU baselines, --precise")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/probs.npy and DIR/tag_rows.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines, the oracle check and --precise")
+    ap.add_argument("--no-query", action="store_true", help="with --full: skip the CCIP, EVA02, input pipeline and query sections")
     ap.add_argument("--no-exclusive", action="store_true",
-                    help="skip the kernel-alone pass after the timed region (profiler runs: keeps per-launch averages to the timed launches)")
+                    help="with --full: skip the kernel-alone pass after the timed region (profiler runs: keeps per-launch averages to the "
+                         "timed launches)")
     ap.add_argument("--operands", choices=["bf16", "f16"], default="f16",
                     help="16-bit MFMA operand type: f16 (default, the product's: IEEE half, same MFMA rate as bf16, 8x smaller activation "
                          "rounding -- inside the 1e-3 logit tolerance on flat images too) or bf16 (BASELINE.json configs[1]'s wording)")
@@ -513,6 +524,8 @@ def main():
                     help="synthetic checkpoint: trained-like (peaked attention with a heavy tail, logit rms ~10, sparse probabilities, tens "
                          "of labels per image) or the plain random init of rounds 1-2 (logit rms 0.35, ~3000 labels 'selected')")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -609,19 +622,21 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    # HIP events inside the timed region: around the launches of the DOMINANT kernel only (the residual GEMM: 48 of a step's ~130
-    # launches), every 3rd step -- events around every launch cost 0.7 % of the step time (HIPTS_BENCH_PROFILE_ALL=1: as before).
-    # The per-kernel breakdown (`kernels`) comes from three extra steps after the timed region, run the same way.
-    DOM_NAME = "gemm_kernel<EPI_RESID>"
-    dom_cat = -1
-    for c in range(11):
-        nm = ctypes.create_string_buffer(64)
-        _lib.call("hipts_vit_profile_name", c, nm, 64)
-        if nm.value.decode() == DOM_NAME:
-            dom_cat = c
-    profile_all = bool(os.environ.get("HIPTS_BENCH_PROFILE_ALL")) or dom_cat < 0
-    _lib.call("hipts_vit_profile_select", model._h, ctypes.c_uint32(0xffffffff if profile_all else (1 << dom_cat)))
-    _lib.call("hipts_vit_profile_enable", model._h, int(os.environ.get("HIPTS_BENCH_PROFILE_EVERY", "3")))
+    # --full: HIP events inside the timed region, around the launches of the DOMINANT kernel only (the residual GEMM: 48 of a step's
+    # ~130 launches), every 3rd step -- events around every launch cost 0.7 % of the step time (HIPTS_BENCH_PROFILE_ALL=1: as before).
+    # The per-kernel breakdown (`kernels`) comes from three extra steps after the timed region, run the same way.  A plain run records
+    # no events.
+    if args.full:
+        DOM_NAME = "gemm_kernel<EPI_RESID>"
+        dom_cat = -1
+        for c in range(11):
+            nm = ctypes.create_string_buffer(64)
+            _lib.call("hipts_vit_profile_name", c, nm, 64)
+            if nm.value.decode() == DOM_NAME:
+                dom_cat = c
+        profile_all = bool(os.environ.get("HIPTS_BENCH_PROFILE_ALL")) or dom_cat < 0
+        _lib.call("hipts_vit_profile_select", model._h, ctypes.c_uint32(0xffffffff if profile_all else (1 << dom_cat)))
+        _lib.call("hipts_vit_profile_enable", model._h, int(os.environ.get("HIPTS_BENCH_PROFILE_EVERY", "3")))
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -634,6 +649,41 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    # what the last timed step returned to its caller: the probabilities and the tag rows (all ranks' rows, gathered, at N > 1)
+    if rank == 0 and args.dump_outputs:
+        b_last = (counter[0] - 1) & 1
+        out_rows = gathered if world > 1 else rows2[b_last]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "probs.npy"), probs2[b_last].cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "tag_rows.npy"), out_rows.cpu().numpy().astype(np.float64))
+
+    imgs_per_s = world * BATCH * args.steps / elapsed
+    flops_img = model.flops_per_image()
+    result = {
+        "metric": "images/sec tagged (ViT fwd)", "value": imgs_per_s, "unit": "images/sec", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.operands,
+        "dtype_note": ("IEEE-half MFMA operands (v_mfma_f32_16x16x32_f16), fp32 accumulation / residual stream / LayerNorm / softmax "
+                       "statistics; the bf16 checkpoint's matrices are exact in half.  Same matrix rate as the bf16 operands BASELINE.json "
+                       "names (--operands bf16 runs those: outside the 1e-3 logit tolerance on flat images)") if args.operands == "f16"
+                      else "bf16 MFMA operands, fp32 accumulation",
+        "data": "synthetic (%s checkpoint, uniform-noise u8 images)" % args.checkpoint,
+        "config": {"workload": "wd-tagger ViT-B/16 448px 16-bit-operand forward + sigmoid + MCut tag selection, batch 64 per GPU, "
+                               "u8 NHWC images resident in HBM (BASELINE.json configs[1])",
+                   "batch_per_gpu": BATCH, "image": "448x448x3 u8", "classes": cfg["num_classes"],
+                   "parallelism": "dp%d (images sharded by rank, RCCL all-gather of tag rows)" % world if world > 1 else "single GPU",
+                   "flops_per_image": flops_img},
+        "model_tflops": imgs_per_s * flops_img / 1e12 / world,
+        "model_mfma_frac": imgs_per_s * flops_img / 1e12 / world / MFMA_BF16_PEAK_TFLOPS,
+        "full": args.full,
+    }
+    if not args.full:
+        if world > 1:
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        return
 
     # per-kernel device time from the HIP events recorded on the launch stream during the timed steps
     def read_categories():
@@ -799,29 +849,12 @@ def main():
                                  "avg_launch_us": ex[0]["avg_us"], "launches": ex[0]["launches"],
                                  "all_gemm_tflops": sum(c["flops"] for c in egemms) / (sum(c["total_ms"] for c in egemms) * 1e9),
                                  "kernels": [{k: c[k] for k in ("kernel", "launches", "avg_us", "tflops", "gbs")} for c in excl]}
-    imgs_per_s = world * BATCH * args.steps / elapsed
-    flops_img = model.flops_per_image()
-    result = {
-        "metric": "images/sec tagged (ViT fwd)", "value": imgs_per_s, "unit": "images/sec", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.operands,
-        "dtype_note": ("IEEE-half MFMA operands (v_mfma_f32_16x16x32_f16), fp32 accumulation / residual stream / LayerNorm / softmax "
-                       "statistics; the bf16 checkpoint's matrices are exact in half.  Same matrix rate as the bf16 operands BASELINE.json "
-                       "names (--operands bf16 runs those: outside the 1e-3 logit tolerance on flat images)") if args.operands == "f16"
-                      else "bf16 MFMA operands, fp32 accumulation",
-        "data": "synthetic (%s checkpoint, uniform-noise u8 images)" % args.checkpoint,
-        "config": {"workload": "wd-tagger ViT-B/16 448px 16-bit-operand forward + sigmoid + MCut tag selection, batch 64 per GPU, "
-                               "u8 NHWC images resident in HBM (BASELINE.json configs[1])",
-                   "batch_per_gpu": BATCH, "image": "448x448x3 u8", "classes": cfg["num_classes"],
-                   "parallelism": "dp%d (images sharded by rank, RCCL all-gather of tag rows)" % world if world > 1 else "single GPU",
-                   "flops_per_image": flops_img},
-        "model_tflops": imgs_per_s * flops_img / 1e12 / world,
-        "model_mfma_frac": imgs_per_s * flops_img / 1e12 / world / MFMA_BF16_PEAK_TFLOPS,
+    result.update({
         "roofline": roofline,
         "output_check": check,
         "sustained": sustained,
         "kernels": [{k: c[k] for k in ("kernel", "launches", "avg_us", "tflops", "gbs")} for c in cats],
-    }
+    })
     if world == 1 and not args.no_query:
         # before the CPU baselines: their 16 spinning intra-op threads slow the ~600 launches of a two-stream CCIP forward
         try:
