@@ -1336,6 +1336,7 @@ int launch_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
     if (epi == EPI_SWIGLU)
         HIPTS_REQUIRE(a.N % 64 == 0 && (a.ld_out ? a.ld_out : a.N / 2) % 8 == 0 && a.out_bf16, "gemm: SWIGLU needs N %% 64 == 0 and an output stride that is a multiple of 8");
     if (epi == EPI_RESCALE) HIPTS_REQUIRE(a.res_scale != nullptr, "gemm: RESCALE epilogue needs res_scale");
+    if (epi == EPI_RESID_LS) HIPTS_REQUIRE(a.res_scale && a.out_f32 && !a.x_blocked, "gemm: RESID_LS needs the layer scale and the row-major fp32 stream");
     if (epi == EPI_RESID_LN)
         HIPTS_REQUIRE(a.N <= BN && a.ln_gamma && a.out_bf16 && a.out_f32, "gemm: RESID_LN needs the whole row in one tile (N <= %d), gamma and both outputs", BN);
     switch (epi) {
@@ -1354,6 +1355,7 @@ int launch_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
         case EPI_RESID_ROWSTAT: return launch_t<EPI_RESID_ROWSTAT>(a, s);
         case EPI_RESID_XG: return launch_t<EPI_RESID_XG>(a, s);
         case EPI_RESID_XGI: return launch_t<EPI_RESID_XGI>(a, s);
+        case EPI_RESID_LS: return launch_t<EPI_RESID_LS>(a, s);
     }
     return set_error(HIPTS_ERR_INVALID, "gemm: unknown epilogue");
 }

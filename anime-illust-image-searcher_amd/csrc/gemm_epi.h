@@ -735,7 +735,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
             }
             return;
         }
-        if constexpr (EPI == EPI_RESID || EPI == EPI_RESCALE || EPI == EPI_RESID_ROWSTAT) {
+        if constexpr (EPI == EPI_RESID || EPI == EPI_RESCALE || EPI == EPI_RESID_ROWSTAT || EPI == EPI_RESID_LS) {
             f32x4 rs[4];
             if constexpr (EPI == EPI_RESCALE) {
 #pragma unroll
@@ -785,9 +785,16 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
                                 v = xv[u][j] * rs[j] + (acc[i2 + u][j] + bv[j]);
                             else if constexpr (EPI == EPI_RESID_ROWSTAT)
                                 v = xv[u][j] + ((acc[i2 + u][j] * st.x - rs[j] * st.y) + bv[j]);
+                            else if constexpr (EPI == EPI_RESID_LS)
+                                v = xv[u][j] + ((INTERIOR || nv[j]) ? *reinterpret_cast<const f32x4*>(a.res_scale + nc[j]) : f32x4{0.f, 0.f, 0.f, 0.f}) *
+                                                   (acc[i2 + u][j] + bv[j]);      // (the layer scale read where it is used: held in 16 registers it spilled)
                             else
                                 v = xv[u][j] + (acc[i2 + u][j] + bv[j]);
                             if (INTERIOR || (nv[j] && m < a.M)) *reinterpret_cast<f32x4*>(row ? row + nc[j] : a.out_f32 + x_off(a, mc, nc[j], ld)) = v;
+                            if constexpr (EPI == EPI_RESID_LS) {
+                                if (a.out_bf16 && (INTERIOR || (nv[j] && m < a.M)))
+                                    *reinterpret_cast<bf16x4*>(a.out_bf16 + (size_t)mc * ld + nc[j]) = pack4<F16>(v[0], v[1], v[2], v[3]);
+                            }
                         }
                     }
                 }

@@ -215,6 +215,8 @@ enum GemmEpilogue {
                        // W LN(x) + b = rstd (W (gamma x)) - rstd mean (W gamma) + (W beta + b) without a LayerNorm pass over x.
     EPI_RESID_XGI = 14, // EPI_RESID_XG with the fold on its input (rowstat / stat_in + col_u); plain EPI_RESID_XG ignores them, which
                         // leaves it the registers for four row blocks of residual loads in flight instead of two
+    EPI_RESID_LS = 15, // (ConvNeXt fc2) x[m][n] += res_scale[n] * (acc + bias[n]): the layer scale applied in fp32 to the branch, never folded into
+                       // W; optionally (out_bf16) also out_bf16[m][n] = 16bit(x[m][n]), the next depthwise convolution's input.  Row-major x.
     EPI_RESID_LN = 9 // x[m][n] = x[m][n] * (res_scale ? res_scale[n] : 1) + acc + bias[n]  (fp32 in/out), AND the LayerNorm
                      // of the new row: xn[m][n] = bf16((x - mean) * rstd * ln_gamma[n] (+ ln_beta[n])).  Needs the whole
                      // row in one tile: N <= 256.  Saves the separate LayerNorm pass over x (HBM-bound).

@@ -19,6 +19,12 @@ EVA02_L14_448 = dict(image_size=448, patch=14, dim=1024, depth=24, heads=16, mlp
                      rope_ref_grid=16)
 EVA02_TINY = dict(image_size=56, patch=14, dim=128, depth=2, heads=2, mlp_hidden=340, num_classes=200, ln_eps=1e-6,
                   rope_ref_grid=16)
+# timm convnext_base at 448 px (wd-convnext-tagger-v3); the transform mean / std of the v3 taggers (0.5) is an assumption, see DESIGN.md
+CONVNEXT_B_448 = dict(image_size=448, dims=(128, 256, 512, 1024), depths=(3, 3, 27, 3), num_classes=10861, ln_eps=1e-6,
+                      norm_mean=(0.5, 0.5, 0.5), norm_std=(0.5, 0.5, 0.5), operand_f16=1)
+# test geometry: sides 16 / 8 / 4 / 2, the same widths (and so the same kernels) as B
+CONVNEXT_TINY = dict(image_size=64, dims=(128, 256, 512, 1024), depths=(1, 1, 2, 1), num_classes=200, ln_eps=1e-6,
+                     norm_mean=(0.5, 0.5, 0.5), norm_std=(0.5, 0.5, 0.5), operand_f16=1)
 # CCIP feature encoder (gen_cfeatures.py): CAFormer-B36 widths at 384 px, 768-d feature
 CCIP_B36_384 = dict(image_size=384, dims=(128, 256, 512, 768), depths=(3, 12, 18, 3), head_dim=32, ln_eps=1e-6)
 CCIP_TINY = dict(image_size=64, dims=(64, 64, 128, 128), depths=(1, 1, 2, 1), head_dim=32, ln_eps=1e-6)
@@ -160,6 +166,53 @@ def eva_weights(cfg: Dict, seed: int = 0, bf16_matrices: bool = True, trained_li
             p = "blocks.%d." % i
             _trained_like_qk(rng2, w, p + "attn.q_proj.weight", p + "attn.k_proj.weight", 0, 0, i, H, D // H, p + "attn.q_proj.bias", None)
         _trained_like_head(rng2, w, C)
+    return w
+
+
+def convnext_weights(cfg: Dict, seed: int = 0, trained_like: bool = False, bf16_matrices: bool = True) -> Dict[str, np.ndarray]:
+    """Random-init ConvNeXt checkpoint with timm `ConvNeXt` state_dict keys (stem.0/1, stages.{i}.downsample.{0,1},
+    stages.{i}.blocks.{j}.{conv_dw, norm, mlp.fc1, mlp.fc2, gamma}, head.norm, head.fc).  Layer scales at 0.1 (a block's branch must
+    matter for the parity tests to mean anything).  trained_like: the tagger head of _trained_like_head (sparse probabilities), layer
+    scales drawn log-uniformly per channel over [1e-4, 1], and the first block of stage 2 left at timm's initial 1e-6."""
+    rng = np.random.default_rng(seed)
+    dims, depths, C = cfg["dims"], cfg["depths"], cfg["num_classes"]
+    rb = round_to_bf16 if bf16_matrices else (lambda a: a)
+    w: Dict[str, np.ndarray] = {}
+
+    def ln(prefix, d):
+        w[prefix + ".weight"] = rng.uniform(0.5, 1.5, d).astype(np.float32)
+        w[prefix + ".bias"] = _trunc_normal(rng, (d,), 0.02)
+    w["stem.0.weight"] = rb(_trunc_normal(rng, (dims[0], 3, 4, 4), 0.1))
+    w["stem.0.bias"] = _trunc_normal(rng, (dims[0],), 0.02)
+    ln("stem.1", dims[0])
+    for i in range(4):
+        d = dims[i]
+        if i > 0:
+            ln("stages.%d.downsample.0" % i, dims[i - 1])
+            w["stages.%d.downsample.1.weight" % i] = rb(_trunc_normal(rng, (d, dims[i - 1], 2, 2), (4.0 * dims[i - 1]) ** -0.5))
+            w["stages.%d.downsample.1.bias" % i] = _trunc_normal(rng, (d,), 0.02)
+        for j in range(depths[i]):
+            p = "stages.%d.blocks.%d." % (i, j)
+            w[p + "conv_dw.weight"] = _trunc_normal(rng, (d, 1, 7, 7), 1.0 / 7.0)
+            w[p + "conv_dw.bias"] = _trunc_normal(rng, (d,), 0.02)
+            ln(p + "norm", d)
+            w[p + "mlp.fc1.weight"] = rb(_trunc_normal(rng, (4 * d, d), d ** -0.5))
+            w[p + "mlp.fc1.bias"] = _trunc_normal(rng, (4 * d,), 0.02)
+            w[p + "mlp.fc2.weight"] = rb(_trunc_normal(rng, (d, 4 * d), (4.0 * d) ** -0.5))
+            w[p + "mlp.fc2.bias"] = _trunc_normal(rng, (d,), 0.02)
+            w[p + "gamma"] = np.full(d, 0.1, dtype=np.float32)
+    ln("head.norm", dims[3])
+    w["head.fc.weight"] = rb(_trunc_normal(rng, (C, dims[3]), 0.02))
+    w["head.fc.bias"] = _trunc_normal(rng, (C,), 0.02)
+    if trained_like:
+        rng2 = np.random.default_rng(seed + 7919)
+        for i in range(4):
+            for j in range(depths[i]):
+                w["stages.%d.blocks.%d.gamma" % (i, j)] = np.exp(rng2.uniform(np.log(1e-4), 0.0, dims[i])).astype(np.float32)
+        w["stages.2.blocks.0.gamma"] = np.full(dims[2], 1e-6, dtype=np.float32)
+        h = {"head.weight": w.pop("head.fc.weight"), "head.bias": w.pop("head.fc.bias")}
+        _trained_like_head(rng2, h, C)
+        w["head.fc.weight"], w["head.fc.bias"] = h["head.weight"], h["head.bias"]
     return w
 
 

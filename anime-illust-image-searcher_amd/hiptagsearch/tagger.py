@@ -139,6 +139,55 @@ class EvaTagger(ViTTagger):
             self._h = c_void_p()
 
 
+class ConvNeXtTagger(ViTTagger):
+    """Device-resident ConvNeXt tagger (wd-convnext-tagger-v3 = timm convnext_base at 448 px).  Same interface as ViTTagger;
+    `weights` uses timm `ConvNeXt` state_dict keys.  cfg: image_size, dims, depths, num_classes, ln_eps, norm_mean / norm_std (the
+    uint8 entry point's Normalize, RGB order) and operand_f16 (1 = IEEE half operands, the default; 0 = bf16)."""
+
+    def __init__(self, cfg: Dict, weights: Dict[str, np.ndarray], max_batch: int = 64, device: int = 0):
+        self.cfg = dict(cfg)
+        self.device = device
+        self.max_batch = max_batch
+        self.num_classes = cfg["num_classes"]
+        c = _lib.ConvnextConfig()
+        c.image_size = cfg["image_size"]
+        c.dims[:] = list(cfg["dims"])
+        c.depths[:] = list(cfg["depths"])
+        c.num_classes = cfg["num_classes"]
+        c.ln_eps = cfg.get("ln_eps", 1e-6)
+        c.norm_mean[:] = list(cfg.get("norm_mean", (0.5, 0.5, 0.5)))
+        c.norm_std[:] = list(cfg.get("norm_std", (0.5, 0.5, 0.5)))
+        c.max_batch = max_batch
+        c.operand_f16 = cfg.get("operand_f16", 1)
+        self._h = c_void_p()
+        _lib.call("hipts_convnext_create", ctypes.byref(c), device, ctypes.byref(self._h))
+        for key, val in weights.items():
+            arr = np.ascontiguousarray(val, dtype=np.float32)
+            _lib.call("hipts_convnext_set_tensor", self._h, key.encode(), _lib.ptr(arr), ctypes.c_int64(arr.size))
+
+    def flops_per_image(self) -> float:
+        f = c_double()
+        _lib.call("hipts_convnext_flops_per_image", self._h, ctypes.byref(f))
+        return f.value
+
+    def _run(self, fn: str, x, batch: int, logits, probs):
+        super()._run(fn.replace("hipts_vit", "hipts_convnext"), x, batch, logits, probs)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.call("hipts_convnext_destroy", self._h)
+            self._h = c_void_p()
+
+
+def model_class(cfg: Dict):
+    """The tagger class a configuration dict selects: ConvNeXt (stage widths `dims`), EVA02 (SwiGLU width `mlp_hidden`), else ViT."""
+    if "dims" in cfg:
+        return ConvNeXtTagger
+    if "mlp_hidden" in cfg:
+        return EvaTagger
+    return ViTTagger
+
+
 def device_resize_u8(image: np.ndarray, out_h: int, out_w: int, pil_filter: int = 3, device: int = 0, out=None):
     """uint8 [H,W,3] (host numpy or CUDA tensor) -> uint8 [out_h,out_w,3] CUDA tensor: PIL's Image.resize((out_w, out_h), filter) on the
     device, bit for bit (pil_filter 3 = BICUBIC: tagging.py:241's transform; 2 = BILINEAR: gen_cfeatures.py:101)."""
@@ -283,17 +332,24 @@ class Predictor:
         if self.tagger_model is not None:
             return
         self.cfg = dict(cfg or synth.VIT_B16_448)
+        # an EVA02 configuration (the reference's MODEL_REPO, tagging.py:45) is recognised by its SwiGLU width, a ConvNeXt one by its
+        # stage widths
+        cls_ = model_class(self.cfg)
+        eva = cls_ is EvaTagger
         if self.precise:
+            if cls_ is ConvNeXtTagger:
+                raise ValueError("precise is an attention-output option (ViT, EVA02); the ConvNeXt tagger has no attention")
             self.cfg["operand_f16"] = int(self.cfg.get("operand_f16", 1)) | 16
-        # an EVA02 configuration (the reference's MODEL_REPO, tagging.py:45) is recognised by its SwiGLU width
-        eva = "mlp_hidden" in self.cfg
-        cls_ = EvaTagger if eva else ViTTagger
         if checkpoint:
             self.tagger_model = cls_.from_safetensors(checkpoint, self.cfg, max_batch=self.max_batch, device=self.device)
         else:
-            print("No checkpoint given: using the seeded synthetic %s weights (no network in this environment)." % ("EVA02" if eva else "ViT"))
+            name = {EvaTagger: "EVA02", ConvNeXtTagger: "ConvNeXt"}.get(cls_, "ViT")
+            print("No checkpoint given: using the seeded synthetic %s weights (no network in this environment)." % name)
             # the trained-like variant (peaked attention, sparse probabilities: tens of labels per image, as a real tagger selects)
-            weights = synth.eva_weights(self.cfg, seed, trained_like=True) if eva else synth.vit_weights(self.cfg, seed, trained_like=True)
+            if cls_ is ConvNeXtTagger:
+                weights = synth.convnext_weights(self.cfg, seed, trained_like=True)
+            else:
+                weights = synth.eva_weights(self.cfg, seed, trained_like=True) if eva else synth.vit_weights(self.cfg, seed, trained_like=True)
             self.tagger_model = cls_(self.cfg, weights, self.max_batch, self.device)
         if labels_csv:
             import pandas as pd

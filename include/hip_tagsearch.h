@@ -45,7 +45,7 @@ int hipts_abi_version(void);
 int hipts_last_error(char* buf, size_t n);
 int hipts_device_count(int* count);
 /* sizeof() of a configuration structure as THIS LIBRARY was compiled: kind 0 = hipts_vit_config_t, 1 = hipts_eva_config_t,
- * 2 = hipts_ccip_config_t.  A binding in another language compares its own structure's size with it before the first
+ * 2 = hipts_ccip_config_t, 3 = hipts_convnext_config_t.  A binding in another language compares its own structure's size with it before the first
  * hipts_*_create (tests/test_abi.py does, for the ctypes structures and for the stubs printed in INTEGRATION.md). */
 int hipts_sizeof_config(int kind, size_t* bytes);
 
@@ -167,6 +167,42 @@ int hipts_eva_forward_u8(hipts_eva_t* h, const uint8_t* images, int images_memsp
 int hipts_eva_forward_f32(hipts_eva_t* h, const float* x, int x_memspace, int batch, float* logits_out, float* probs_out,
                           int out_memspace, void* stream);
 int hipts_eva_flops_per_image(const hipts_eva_t* h, double* flops);
+
+/* ------------------------------------------------------------------------------------------
+ * ConvNeXt tagger forward -- the convolutional member of the wd-tagger v3 family (wd-convnext-tagger-v3 = timm
+ * convnext_base at 448 px).  Same call sites and output contract as the ViT / EVA02 taggers above.
+ * Graph: stem Conv2d(3, C0, k 4, s 4) + LayerNorm (weight, bias); four stages, stages 1-3 opened by LayerNorm +
+ * Conv2d(k 2, s 2); blocks x = x + gamma * fc2(GELU_erf(fc1(LN(dwconv7x7(x) + b)))); head mean pool -> LayerNorm -> fc ->
+ * sigmoid.  Matrix weights are 16-bit MFMA operands; accumulation, residual stream, LayerNorm, layer scale in float32.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct hipts_convnext hipts_convnext_t;
+
+typedef struct hipts_convnext_config {
+    int32_t image_size;      /* 448 (a multiple of 32)                                                */
+    int32_t dims[4];         /* 128, 256, 512, 1024 (multiples of 64, at most 1024)                   */
+    int32_t depths[4];       /* 3, 3, 27, 3                                                           */
+    int32_t num_classes;     /* 10861                                                                 */
+    float   ln_eps;          /* 1e-6                                                                  */
+    float   norm_mean[3];    /* the uint8 entry point's Normalize, RGB order: 0.5, 0.5, 0.5           */
+    float   norm_std[3];     /* 0.5, 0.5, 0.5                                                         */
+    int32_t max_batch;       /* workspace is sized for this many images per forward call              */
+    int32_t operand_f16;     /* 0: bf16, 1: IEEE half MFMA operands                                   */
+} hipts_convnext_config_t;
+
+int hipts_convnext_create(const hipts_convnext_config_t* cfg, int device, hipts_convnext_t** out);
+int hipts_convnext_destroy(hipts_convnext_t* h);
+/* timm ConvNeXt state_dict keys, host float32 in the timm layout: "stem.0.weight", "stem.1.bias",
+ * "stages.1.downsample.1.weight", "stages.2.blocks.5.conv_dw.weight", "stages.2.blocks.5.mlp.fc1.bias",
+ * "stages.2.blocks.5.gamma", "head.norm.weight", "head.fc.weight", ...  Element counts are checked.  A forward before
+ * every key is set fails with HIPTS_ERR_STATE and names the first missing key. */
+int hipts_convnext_set_tensor(hipts_convnext_t* h, const char* key, const float* data, int64_t numel);
+/* same contracts as hipts_vit_forward_u8 / _f32: images uint8 [batch][S][S][3] RGB (the kernel applies /255, norm_mean /
+ * norm_std and the BGR order); x float32 [batch][3][S][S], already normalised, BGR. */
+int hipts_convnext_forward_u8(hipts_convnext_t* h, const uint8_t* images, int images_memspace, int batch, float* logits_out,
+                              float* probs_out, int out_memspace, void* stream);
+int hipts_convnext_forward_f32(hipts_convnext_t* h, const float* x, int x_memspace, int batch, float* logits_out, float* probs_out,
+                               int out_memspace, void* stream);
+int hipts_convnext_flops_per_image(const hipts_convnext_t* h, double* flops);
 
 /* ------------------------------------------------------------------------------------------
  * CCIP feature encoder.   Replaces the onnxruntime session of gen_cfeatures.py:112-118 and its

@@ -35,6 +35,9 @@ int hiptsdbg_dwconv7(const uint16_t* in_f16, const float* w, uint16_t* out_f16, 
 /* Phase time stamps (100 MHz) of one workgroup of the matrix-core kernel's last launch; zeros unless csrc/ccip.hip was built with
  * -DHIPTS_DW_STAMPS=<workgroup> (tools/dwconv_stamps.py). */
 int hiptsdbg_dwconv7_stamps(unsigned long long* host, int n);
+/* The ConvNeXt forward's float32 residual stream [batch][H*H][dims[stage]] after the last block of `stage` (0..3), from host
+ * float32 input in the layout of hipts_convnext_forward_f32: places a parity failure in the network. */
+int hiptsdbg_convnext_stream(hipts_convnext_t* h, const float* x_host, int batch, int stage, float* out_host);
 /* The fused MLP of the CCIP encoder's stages 0-1 on its own (csrc/mlp.hip): x[m] = rs * x[m] + StarReLU(xn[m] W1^T) W2^T, xn_out[m] = LayerNorm(x[m]) * gamma.
  * Host arrays: xn / xn_out IEEE-half bits [M][C], w1 [4C][C], w2 [C][4C], x [M][C] in / out, res_scale / gamma [C] or null; C = 128 or 256;
  * ms_out: average device time of iters - 1 launches (iters >= 2); waves: 4 / 8 waves per workgroup, 0 = chosen by the size of the launch. */
