@@ -94,7 +94,8 @@ int hipts_sizeof_config(int kind, size_t* bytes) {
         case 1: *bytes = sizeof(hipts_eva_config_t); return HIPTS_OK;
         case 2: *bytes = sizeof(hipts_ccip_config_t); return HIPTS_OK;
         case 3: *bytes = sizeof(hipts_convnext_config_t); return HIPTS_OK;
-        default: return hipts::set_error(HIPTS_ERR_INVALID, "hipts_sizeof_config: kind %d (0 vit, 1 eva, 2 ccip, 3 convnext)", kind);
+        case 4: *bytes = sizeof(hipts_swinv2_config_t); return HIPTS_OK;
+        default: return hipts::set_error(HIPTS_ERR_INVALID, "hipts_sizeof_config: kind %d (0 vit, 1 eva, 2 ccip, 3 convnext, 4 swinv2)", kind);
     }
 }
 

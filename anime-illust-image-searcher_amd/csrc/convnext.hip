@@ -10,7 +10,7 @@
 // operands 16-bit (bf16, or IEEE half with operand_f16 bit 0).  Every 1 x 1 convolution / Linear is the shared persistent MFMA
 // GEMM (gemm.hip) with a fused epilogue:
 //   stem 4x4 s4      patch gather (hi | lo halves against [W | W], K = 2 x 64)  -> EPI_BIAS, then LayerNorm with bias in place
-//                    (cnx_ln_kernel, which also writes the 16-bit copy of x the first depthwise convolution reads)
+//                    (convnet.h: cnx_stem_kernel, cnx_ln_kernel, which also writes the 16-bit copy of x the first depthwise convolution reads)
 //   downsample       LayerNorm fused with the 2 x 2 s2 gather (cnx_ds_kernel writes the GEMM's A matrix) -> EPI_BIAS, 16-bit copy
 //   depthwise 7x7    convnet.h: the matrix-core kernel (half operands, side >= 16) or the VALU kernel; then cnx_dwln_kernel adds the
 //                    depthwise bias and applies the block's LayerNorm (weight, bias) into the 16-bit operand of fc1
@@ -33,9 +33,6 @@
 using namespace hipts;
 
 namespace {
-
-constexpr int CNX_STEM_KH = 64;                  // 4*4*3 = 48 taps padded to 64; K = hi | lo = 128
-constexpr int CNX_STEM_K = 2 * CNX_STEM_KH;
 
 struct CnxBlock {
     DevBuf dw;                     // depthwise weights as [49][C] float32 (VALU kernel)
@@ -70,96 +67,6 @@ struct hipts_convnext {
 
 namespace {
 
-// ---------------------------------------------------------------------------------------------
-// Stem patch matrix: A0[m][(ky*4 + kx)*3 + c] = hi, A0[m][64 + ...] = lo of the normalised pixel (4 oy + ky, 4 ox + kx) of memory
-// channel c (RGB); the BGR order of the model lives in the weight permutation.  Columns 48..63 of each half are zero.
-// U8: images uint8 NHWC RGB through the normalisation table lut[c][u] (built on the host from the configuration's mean / std);
-// F32: float32 [B][3][S][S], already normalised, BGR (channel 2 - c holds memory channel c).
-// One thread per (token, ky): 12 values.
-// ---------------------------------------------------------------------------------------------
-template <bool U8, bool F16>
-__global__ __launch_bounds__(256) void cnx_stem_kernel(const void* __restrict__ img, const float* __restrict__ lut, bf16_t* __restrict__ a0,
-                                                       int64_t total, int S, int H0) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int ky = (int)(idx & 3);
-    const int64_t m = idx >> 2;
-    const int ox = (int)(m % H0), oy = (int)((m / H0) % H0);
-    const int64_t b = m / ((int64_t)H0 * H0);
-    bf16_t* row = a0 + m * CNX_STEM_K;
-    const int iy = 4 * oy + ky;
-#pragma unroll
-    for (int kx = 0; kx < 4; ++kx) {
-        const int ix = 4 * ox + kx;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float v;
-            if constexpr (U8) v = lut[c * 256 + reinterpret_cast<const uint8_t*>(img)[((b * S + iy) * S + ix) * 3 + c]];
-            else v = reinterpret_cast<const float*>(img)[((b * 3 + (2 - c)) * S + iy) * (int64_t)S + ix];
-            const bf16_t hi = to_op<F16>(v);
-            row[(ky * 4 + kx) * 3 + c] = hi;
-            row[CNX_STEM_KH + (ky * 4 + kx) * 3 + c] = to_op<F16>(v - from_op<F16>(hi));
-        }
-    }
-    if (ky == 0) {
-#pragma unroll
-        for (int k = 48; k < CNX_STEM_KH; ++k) {
-            row[k] = to_op<F16>(0.f);
-            row[CNX_STEM_KH + k] = to_op<F16>(0.f);
-        }
-    }
-}
-
-// Row statistics of one row held by a wave as up to four float4 per lane (D <= 1024, D % 4 == 0): the two-pass mean / variance of
-// ln_inplace_kernel (ccip.hip), same operations in the same order.
-__device__ __forceinline__ void row_mean_rstd(const float4 (&v)[4], int lane, int D, float eps, float& mean, float& rstd) {
-    const int nvec = D >> 2;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    mean = wave_sum_f(s) / (float)D;
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        if (lane + 64 * i < nvec) {
-            const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-            ss += (a * a + b * b) + (c * c + d * d);
-        }
-    rstd = 1.0f / sqrtf(wave_sum_f(ss) / (float)D + eps);
-}
-
-__device__ __forceinline__ float4 ln_apply(float4 v, float mean, float rstd, float4 g, float4 b) {
-    return make_float4((v.x - mean) * rstd * g.x + b.x, (v.y - mean) * rstd * g.y + b.y, (v.z - mean) * rstd * g.z + b.z,
-                       (v.w - mean) * rstd * g.w + b.w);
-}
-
-// The stem's LayerNorm (weight and bias) of float32 rows in place; also the 16-bit copy xh.  One wave per row.
-template <bool F16>
-__global__ __launch_bounds__(256) void cnx_ln_kernel(float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ bt,
-                                                     bf16_t* __restrict__ xh, int64_t rows, int D, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nvec = D >> 2;
-    float4* xr = reinterpret_cast<float4*>(x + row * D);
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        v[i] = c < nvec ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float mean, rstd;
-    row_mean_rstd(v, lane, D, eps, mean, rstd);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec) {
-            const float4 o = ln_apply(v[i], mean, rstd, reinterpret_cast<const float4*>(g)[c], reinterpret_cast<const float4*>(bt)[c]);
-            xr[c] = o;
-            *reinterpret_cast<bf16x4*>(xh + row * D + 4 * c) = pack4<F16>(o.x, o.y, o.z, o.w);
-        }
-    }
-}
 
 // Downsample: LayerNorm (weight, bias) of input token (b, iy, ix) written straight into the 2 x 2 s2 patch matrix,
 // col[(b, iy / 2, ix / 2)][((iy & 1) * 2 + (ix & 1)) * C + c].  The patches do not overlap: every token is normalised once and lands
@@ -237,17 +144,6 @@ __global__ __launch_bounds__(256) void cnx_dwln_kernel(const bf16_t* __restrict_
     }
 }
 
-// Pooled features as hi | lo halves (the head GEMM runs K = 2 C against [W | W]): f2[b][c] = hi, f2[b][C + c] = lo.
-template <bool F16>
-__global__ __launch_bounds__(256) void cnx_split_kernel(const float* __restrict__ f, bf16_t* __restrict__ f2, int batch, int C) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= batch * C) return;
-    const int b = i / C, c = i - b * C;
-    const float v = f[i];
-    const bf16_t hi = to_op<F16>(v);
-    f2[(size_t)b * 2 * C + c] = hi;
-    f2[(size_t)b * 2 * C + C + c] = to_op<F16>(v - from_op<F16>(hi));
-}
 
 int cnx_upload_f32(DevBuf& buf, const float* data, size_t n) {
     HIPTS_TRY(buf.alloc(n * 4));

@@ -1,0 +1,694 @@
+// swinv2.hip -- SwinV2 tagger forward (wd-swinv2-tagger-v3 = timm `swinv2_base_window8_256` built with img_size 448, window_size 14)
+// behind hipts_swinv2_*.
+//
+// Layer algebra (timm `models/swin_transformer_v2.py`, >= 0.9 layout):
+//   stem      x = LN(Conv2d(3, C0, k = 4, s = 4)(img) + b)
+//   stage i   (i > 0) patch merging: x = LN(Linear(4 C_{i-1} -> C_i, no bias)(cat of the 2 x 2 neighbours, (dy, dx) = (0,0) (1,0) (0,1) (1,1)))
+//             blocks (shift s = 0 for even j, window / 2 for odd j; a stage whose side is <= window attends over the whole map, unshifted):
+//               x = x + LN1(proj(WindowAttn(x)))          x = x + LN2(fc2(GELU(fc1(x))))          (post-norm; qkv and fc1 read x)
+//   head      logits = fc(mean over tokens of LN(x)), probs = sigmoid(logits)
+//
+// Data layout as in the ConvNeXt forward: token-major NHWC, the residual stream x float32 [B*H*W][C], its hi | lo 16-bit halves xh2
+// [B*H*W][2 C] the A operand of q | k | v and fc1.  Every Linear is the shared persistent MFMA GEMM (gemm.hip):
+//   stem          convnet.h's cnx_stem_kernel (hi | lo patch gather) -> EPI_BIAS -> cnx_ln_kernel (LayerNorm with bias in place; its
+//                 16-bit copy xh is not read here) -> sw_split_x_kernel (xh2)
+//   merging       sw_merge_kernel (2 x 2 gather in timm's order as hi | lo halves of the fp32 stream) -> EPI_BIAS (K = 8 C, zero bias)
+//                 -> cnx_ln_kernel in place
+//   q | k | v     EPI_BIAS into float32 [M][3 C] (bias [q_bias | 0 | v_bias]) from the hi | lo halves of x (xh2, K = 2 C against
+//                 [W | W]).  The cosine multiplies q and k by up to 100 after normalisation: a single 16-bit rounding of x moves a score
+//                 by ~2e-2 (measured: 0.6 max |dlogit| on the trained-like checkpoint).  q and k reach the attention in float32, which
+//                 normalises them before its own hi | lo rounding (swin_attn.hip)
+//   attention     launch_swin_attention: windows, shift, cosine, position bias and the -100 mask as index math; 16-bit output
+//   proj, fc2     EPI_BIAS into the float32 branch buffer, then sw_postnorm_kernel: x += LN(branch) (weight, bias) and xh2 = the hi | lo
+//                 halves of the new x, the operand of fc1 / of the next block's q | k | v.  One form for every stage: which kernels run
+//                 depends on the configuration only, never on the batch or its split.
+//   fc1           EPI_GELU from xh2 (K = 2 C against [W | W]; gelu_tanh from the configuration, 0 = the erf form).  The hi | lo operands
+//                 of merging, q | k | v and fc1 are what brings a flat picture's logits within 1e-3 of float64: its tokens share every
+//                 rounding error, which the mean over tokens then cannot average out
+//   head          sw_ln_rows_kernel (per-token LayerNorm, float32) -> sw_mean_kernel -> cnx_split_kernel (hi | lo) -> EPI_HEAD
+// The position-bias tables 16 sigmoid(cpb_mlp(table)) depend on the weights only: computed on the host (double, stored float32) at the
+// first forward after the last cpb_mlp tensor was set, [heads][(2 w - 1)^2] per block.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "vit_internal.h"
+#include "convnet.h"
+
+using namespace hipts;
+
+namespace {
+
+constexpr int SW_CPB_HIDDEN = 512;               // timm's cpb_mlp: Linear(2, 512) -> ReLU -> Linear(512, heads, no bias)
+
+struct SwBlock {
+    int shift = 0;
+    DevBuf qkv2, qkv_b, proj, proj_b, n1_w, n1_b, fc1, fc1_b, fc2, fc2_b, n2_w, n2_b, ls, cpb;
+    std::vector<float> qkv_bh;                   // host [q_bias | 0 | v_bias]
+    std::vector<float> cpb_w1, cpb_b1, cpb_w2;   // host copies of cpb_mlp.{0.weight, 0.bias, 2.weight}
+};
+
+struct SwStage {
+    int C = 0, H = 0, T = 0, heads = 0, win = 0, hid = 0;
+    DevBuf ds_w, ds_b, ds_nw, ds_nb;             // patch merging (stage > 0): reduction [C][4 Cprev] (timm's column order), zero bias, LN
+    std::vector<SwBlock> blocks;
+};
+
+}  // namespace
+
+struct hipts_swinv2 {
+    int device = 0;
+    hipts_swinv2_config_t cfg{};
+    SwStage st[4];
+    DevBuf stem_w, stem_b, stem_nw, stem_nb, head_nw, head_nb, head_w, head_b, lut;
+    std::vector<std::string> missing;
+    bool cpb_ready = false;
+    // workspace (sized for cfg.max_batch), carved per image with the stride of the largest stage
+    DevBuf img_in, a0, x, xh, xh2, qkv, ao, br, m1, col, feat, feat2, logits, probs;
+    size_t px = 0, p3c = 0, phid = 0, pcol = 0;
+    static constexpr int NSUB = 2;
+    hipStream_t sub[NSUB] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[NSUB] = {};
+    double flops_per_image = 0.0;
+};
+
+namespace {
+
+// Patch merging gather as hi | lo halves: col[(b, oy, ox)][q * C + c] = hi and [4 C + q * C + c] = lo of x[b][2 oy + dy][2 ox + dx][c] with
+// q = 2 dx + dy -- timm's reshape(B, H/2, 2, W/2, 2, C).permute(0, 1, 3, 4, 2, 5) order, so the reduction weight is used as it is (twice:
+// [W | W]).  One thread per float4 of the hi half.
+template <bool F16>
+__global__ __launch_bounds__(256) void sw_merge_kernel(const float* __restrict__ x, bf16_t* __restrict__ col, int64_t total4, int H, int C) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    const int c4 = C >> 2;
+    const int c = (int)(i % c4) * 4;
+    int64_t r = i / c4;
+    const int q = (int)(r & 3);
+    r >>= 2;
+    const int Ho = H >> 1;
+    const int ox = (int)(r % Ho), oy = (int)((r / Ho) % Ho);
+    const int64_t b = r / ((int64_t)Ho * Ho);
+    const int dy = q & 1, dx = q >> 1;
+    const float4 v = *reinterpret_cast<const float4*>(x + ((b * H + 2 * oy + dy) * H + 2 * ox + dx) * C + c);
+    const bf16x4 hi = pack4<F16>(v.x, v.y, v.z, v.w);
+    bf16_t* dst = col + r * 8 * C + q * C + c;
+    *reinterpret_cast<bf16x4*>(dst) = hi;
+    *reinterpret_cast<bf16x4*>(dst + 4 * C) =
+        pack4<F16>(v.x - from_op<F16>(hi[0]), v.y - from_op<F16>(hi[1]), v.z - from_op<F16>(hi[2]), v.w - from_op<F16>(hi[3]));
+}
+
+// Post-norm residual: x += LN(branch) * w + b over rows of D (<= 1024) float32, then the hi | lo halves of the new x.  One wave per row.
+template <bool F16>
+__global__ __launch_bounds__(256) void sw_postnorm_kernel(const float* __restrict__ br, const float* __restrict__ g, const float* __restrict__ bt,
+                                                          float* __restrict__ x, bf16_t* __restrict__ xh2, int64_t rows, int D, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int nvec = D >> 2;
+    const float4* bv = reinterpret_cast<const float4*>(br + row * D);
+    float4 v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = c < nvec ? bv[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float mean, rstd;
+    row_mean_rstd(v, lane, D, eps, mean, rstd);
+    float4* xr = reinterpret_cast<float4*>(x + row * D);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nvec) {
+            const float4 o = ln_apply(v[i], mean, rstd, reinterpret_cast<const float4*>(g)[c], reinterpret_cast<const float4*>(bt)[c]);
+            float4 n = xr[c];
+            n.x += o.x; n.y += o.y; n.z += o.z; n.w += o.w;
+            xr[c] = n;
+            const bf16x4 hi = pack4<F16>(n.x, n.y, n.z, n.w);
+            *reinterpret_cast<bf16x4*>(xh2 + row * 2 * D + 4 * c) = hi;
+            *reinterpret_cast<bf16x4*>(xh2 + row * 2 * D + D + 4 * c) =
+                pack4<F16>(n.x - from_op<F16>(hi[0]), n.y - from_op<F16>(hi[1]), n.z - from_op<F16>(hi[2]), n.w - from_op<F16>(hi[3]));
+        }
+    }
+}
+
+// x as hi | lo halves, xh2[m] = [16bit(x[m]) | 16bit(x[m] - hi)] (behind the stem and merging LayerNorms).  One thread per float4.
+template <bool F16>
+__global__ __launch_bounds__(256) void sw_split_x_kernel(const float* __restrict__ x, bf16_t* __restrict__ xh2, int64_t n4, int D) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const int64_t row = i / (D >> 2);
+    const int c = (int)(i - row * (D >> 2)) * 4;
+    const float4 v = reinterpret_cast<const float4*>(x)[i];
+    const bf16x4 hi = pack4<F16>(v.x, v.y, v.z, v.w);
+    *reinterpret_cast<bf16x4*>(xh2 + row * 2 * D + c) = hi;
+    *reinterpret_cast<bf16x4*>(xh2 + row * 2 * D + D + c) =
+        pack4<F16>(v.x - from_op<F16>(hi[0]), v.y - from_op<F16>(hi[1]), v.z - from_op<F16>(hi[2]), v.w - from_op<F16>(hi[3]));
+}
+
+// The head's LayerNorm of every token, float32 out.  One wave per row.
+__global__ __launch_bounds__(256) void sw_ln_rows_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ bt,
+                                                         float* __restrict__ y, int64_t rows, int D, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int nvec = D >> 2;
+    const float4* xr = reinterpret_cast<const float4*>(x + row * D);
+    float4 v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = c < nvec ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float mean, rstd;
+    row_mean_rstd(v, lane, D, eps, mean, rstd);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nvec)
+            reinterpret_cast<float4*>(y + row * D)[c] =
+                ln_apply(v[i], mean, rstd, reinterpret_cast<const float4*>(g)[c], reinterpret_cast<const float4*>(bt)[c]);
+    }
+}
+
+// Mean over an image's T tokens, tokens summed in order (one workgroup per image).
+__global__ __launch_bounds__(256) void sw_mean_kernel(const float* __restrict__ y, float* __restrict__ f, int T, int C) {
+    const int64_t b = blockIdx.x;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float s = 0.f;
+        for (int t = 0; t < T; ++t) s += y[(b * T + t) * C + c];
+        f[b * C + c] = s / (float)T;
+    }
+}
+
+int sw_upload_f32(DevBuf& buf, const float* data, size_t n) {
+    HIPTS_TRY(buf.alloc(n * 4));
+    return upload(buf.p, data, n * 4);
+}
+
+// 16 sigmoid(cpb_mlp(table)) for one block: [heads][(2 w - 1)^2], table entry (dy, dx) = sign(t) log2(1 + |t|) / log2(8) with
+// t = 8 offset / (pw - 1) per axis (pw = the window, or cpb_pretrained_window when set).
+std::vector<float> sw_cpb_table(const SwBlock& B, int w, int pw, int heads) {
+    const int n = 2 * w - 1;
+    std::vector<float> out((size_t)heads * n * n);
+    std::vector<double> hid(SW_CPB_HIDDEN);
+    auto coord = [&](int o) {
+        const double t = 8.0 * o / (double)(pw - 1);
+        return (t > 0 ? 1.0 : t < 0 ? -1.0 : 0.0) * std::log2(1.0 + std::fabs(t)) / 3.0;
+    };
+    for (int a = 0; a < n; ++a)
+        for (int c = 0; c < n; ++c) {
+            const double t0 = coord(a - (w - 1)), t1 = coord(c - (w - 1));
+            for (int u = 0; u < SW_CPB_HIDDEN; ++u) {
+                const double v = (double)B.cpb_w1[2 * u] * t0 + (double)B.cpb_w1[2 * u + 1] * t1 + (double)B.cpb_b1[u];
+                hid[u] = v > 0.0 ? v : 0.0;
+            }
+            for (int hh = 0; hh < heads; ++hh) {
+                const float* w2 = B.cpb_w2.data() + (size_t)hh * SW_CPB_HIDDEN;
+                double acc = 0.0;
+                for (int u = 0; u < SW_CPB_HIDDEN; ++u) acc += (double)w2[u] * hid[u];
+                out[(size_t)hh * n * n + a * n + c] = (float)(16.0 / (1.0 + std::exp(-acc)));
+            }
+        }
+    return out;
+}
+
+int sw_prepare_cpb(hipts_swinv2* h) {
+    if (h->cpb_ready) return HIPTS_OK;
+    const int pw_cfg = h->cfg.cpb_pretrained_window;
+    for (SwStage& St : h->st)
+        for (SwBlock& B : St.blocks) {
+            const std::vector<float> t = sw_cpb_table(B, St.win, pw_cfg > 0 ? pw_cfg : St.win, St.heads);
+            HIPTS_TRY(sw_upload_f32(B.cpb, t.data(), t.size()));
+        }
+    h->cpb_ready = true;
+    return HIPTS_OK;
+}
+
+// The kernel sequence for images [i0, i0 + batch) on stream s.  stop_stage >= 0 (debug entry): return after that stage's last block,
+// x holding its residual stream.
+int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int batch, float* lg, float* pr, hipStream_t s, bool shared_chip,
+                  int stop_stage) {
+    const auto& c = h->cfg;
+    const int S = c.image_size;
+    const bool f16 = (c.operand_f16 & 1) != 0;
+    const size_t img_bytes = (size_t)S * S * 3 * (is_u8 ? 1 : 4);
+    in_dev = (const char*)in_dev + (size_t)i0 * img_bytes;
+    float* x = h->x.as<float>() + (size_t)i0 * h->px;
+    bf16_t* xh = h->xh.as<bf16_t>() + (size_t)i0 * h->px;
+    bf16_t* xh2 = h->xh2.as<bf16_t>() + (size_t)i0 * 2 * h->px;
+    float* qkv = h->qkv.as<float>() + (size_t)i0 * h->p3c;
+    bf16_t* ao = h->ao.as<bf16_t>() + (size_t)i0 * h->px;
+    float* br = h->br.as<float>() + (size_t)i0 * h->px;
+    bf16_t* m1 = h->m1.as<bf16_t>() + (size_t)i0 * h->phid;
+    bf16_t* col = h->col.as<bf16_t>() + (size_t)i0 * h->pcol;
+    bf16_t* a0 = h->a0.as<bf16_t>() + (size_t)i0 * h->st[0].T * CNX_STEM_K;
+    auto gemm_args = [&]() {
+        GemmArgs g{};
+        g.f16 = f16;
+        g.shared_chip = shared_chip;
+        return g;
+    };
+
+    // ---- stem: conv 4x4 s4 (+bias) -> LayerNorm (weight, bias) = the residual stream of stage 0
+    {
+        const SwStage& S0 = h->st[0];
+        const int64_t M = (int64_t)batch * S0.T;
+        const int blocks = ceil_div(M * 4, 256);
+        if (is_u8) {
+            if (f16) cnx_stem_kernel<true, true><<<blocks, 256, 0, s>>>(in_dev, h->lut.as<float>(), a0, M * 4, S, S0.H);
+            else cnx_stem_kernel<true, false><<<blocks, 256, 0, s>>>(in_dev, h->lut.as<float>(), a0, M * 4, S, S0.H);
+        } else {
+            if (f16) cnx_stem_kernel<false, true><<<blocks, 256, 0, s>>>(in_dev, nullptr, a0, M * 4, S, S0.H);
+            else cnx_stem_kernel<false, false><<<blocks, 256, 0, s>>>(in_dev, nullptr, a0, M * 4, S, S0.H);
+        }
+        HIPTS_LAUNCH_CHECK();
+        GemmArgs g = gemm_args();
+        g.A = a0; g.W = h->stem_w.as<bf16_t>(); g.M = (int)M; g.N = S0.C; g.K = CNX_STEM_K;
+        g.bias = h->stem_b.as<float>(); g.out_f32 = x;
+        HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
+        if (f16) cnx_ln_kernel<true><<<ceil_div(M, 4), 256, 0, s>>>(x, h->stem_nw.as<float>(), h->stem_nb.as<float>(), xh, M, S0.C, c.ln_eps);
+        else cnx_ln_kernel<false><<<ceil_div(M, 4), 256, 0, s>>>(x, h->stem_nw.as<float>(), h->stem_nb.as<float>(), xh, M, S0.C, c.ln_eps);
+        HIPTS_LAUNCH_CHECK();
+        const int64_t n4 = M * S0.C / 4;
+        if (f16) sw_split_x_kernel<true><<<ceil_div(n4, 256), 256, 0, s>>>(x, xh2, n4, S0.C);
+        else sw_split_x_kernel<false><<<ceil_div(n4, 256), 256, 0, s>>>(x, xh2, n4, S0.C);
+        HIPTS_LAUNCH_CHECK();
+    }
+
+    for (int si = 0; si < 4; ++si) {
+        SwStage& St = h->st[si];
+        const int C = St.C, H = St.H;
+        const int M = batch * St.T;
+        if (si > 0) {
+            // patch merging: 2x2 gather -> reduction GEMM -> LayerNorm (weight, bias) in place, with the 16-bit copy
+            const SwStage& Pv = h->st[si - 1];
+            const int64_t total4 = (int64_t)M * Pv.C;          // M rows of 4 Cprev, in float4
+            if (f16) sw_merge_kernel<true><<<ceil_div(total4, 256), 256, 0, s>>>(x, col, total4, Pv.H, Pv.C);
+            else sw_merge_kernel<false><<<ceil_div(total4, 256), 256, 0, s>>>(x, col, total4, Pv.H, Pv.C);
+            HIPTS_LAUNCH_CHECK();
+            GemmArgs g = gemm_args();
+            g.A = col; g.W = St.ds_w.as<bf16_t>(); g.M = M; g.N = C; g.K = 8 * Pv.C;
+            g.bias = St.ds_b.as<float>(); g.out_f32 = x;
+            HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
+            if (f16) cnx_ln_kernel<true><<<ceil_div(M, 4), 256, 0, s>>>(x, St.ds_nw.as<float>(), St.ds_nb.as<float>(), xh, M, C, c.ln_eps);
+            else cnx_ln_kernel<false><<<ceil_div(M, 4), 256, 0, s>>>(x, St.ds_nw.as<float>(), St.ds_nb.as<float>(), xh, M, C, c.ln_eps);
+            HIPTS_LAUNCH_CHECK();
+            const int64_t n4 = (int64_t)M * C / 4;
+            if (f16) sw_split_x_kernel<true><<<ceil_div(n4, 256), 256, 0, s>>>(x, xh2, n4, C);
+            else sw_split_x_kernel<false><<<ceil_div(n4, 256), 256, 0, s>>>(x, xh2, n4, C);
+            HIPTS_LAUNCH_CHECK();
+        }
+        for (SwBlock& B : St.blocks) {
+            GemmArgs g = gemm_args();
+            g.A = xh2; g.W = B.qkv2.as<bf16_t>(); g.M = M; g.N = 3 * C; g.K = 2 * C; g.bias = B.qkv_b.as<float>(); g.out_f32 = qkv;
+            HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
+            HIPTS_TRY(launch_swin_attention(qkv, B.ls.as<float>(), B.cpb.as<float>(), ao, batch, H, St.win, B.shift, St.heads, f16, s));
+            g = gemm_args();
+            g.A = ao; g.W = B.proj.as<bf16_t>(); g.M = M; g.N = C; g.K = C; g.bias = B.proj_b.as<float>(); g.out_f32 = br;
+            HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
+            if (f16) sw_postnorm_kernel<true><<<ceil_div(M, 4), 256, 0, s>>>(br, B.n1_w.as<float>(), B.n1_b.as<float>(), x, xh2, M, C, c.ln_eps);
+            else sw_postnorm_kernel<false><<<ceil_div(M, 4), 256, 0, s>>>(br, B.n1_w.as<float>(), B.n1_b.as<float>(), x, xh2, M, C, c.ln_eps);
+            HIPTS_LAUNCH_CHECK();
+            g = gemm_args();
+            g.A = xh2; g.W = B.fc1.as<bf16_t>(); g.M = M; g.N = St.hid; g.K = 2 * C; g.bias = B.fc1_b.as<float>();
+            g.out_bf16 = m1; g.gelu_tanh = c.gelu_tanh;
+            HIPTS_TRY(launch_gemm(EPI_GELU, g, s));
+            g = gemm_args();
+            g.A = m1; g.W = B.fc2.as<bf16_t>(); g.M = M; g.N = C; g.K = St.hid; g.bias = B.fc2_b.as<float>(); g.out_f32 = br;
+            HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
+            if (f16) sw_postnorm_kernel<true><<<ceil_div(M, 4), 256, 0, s>>>(br, B.n2_w.as<float>(), B.n2_b.as<float>(), x, xh2, M, C, c.ln_eps);
+            else sw_postnorm_kernel<false><<<ceil_div(M, 4), 256, 0, s>>>(br, B.n2_w.as<float>(), B.n2_b.as<float>(), x, xh2, M, C, c.ln_eps);
+            HIPTS_LAUNCH_CHECK();
+        }
+        if (si == stop_stage) return HIPTS_OK;
+    }
+    // ---- head: LayerNorm per token -> mean over tokens -> hi | lo -> fc (+bias) with sigmoid
+    const SwStage& L = h->st[3];
+    const int64_t ML = (int64_t)batch * L.T;
+    float* feat = h->feat.as<float>() + (size_t)i0 * L.C;
+    bf16_t* feat2 = h->feat2.as<bf16_t>() + (size_t)i0 * 2 * L.C;
+    sw_ln_rows_kernel<<<ceil_div(ML, 4), 256, 0, s>>>(x, h->head_nw.as<float>(), h->head_nb.as<float>(), br, ML, L.C, c.ln_eps);
+    HIPTS_LAUNCH_CHECK();
+    sw_mean_kernel<<<batch, 256, 0, s>>>(br, feat, L.T, L.C);
+    HIPTS_LAUNCH_CHECK();
+    if (f16) cnx_split_kernel<true><<<ceil_div((int64_t)batch * L.C, 256), 256, 0, s>>>(feat, feat2, batch, L.C);
+    else cnx_split_kernel<false><<<ceil_div((int64_t)batch * L.C, 256), 256, 0, s>>>(feat, feat2, batch, L.C);
+    HIPTS_LAUNCH_CHECK();
+    GemmArgs g = gemm_args();
+    g.A = feat2; g.W = h->head_w.as<bf16_t>(); g.M = batch; g.N = c.num_classes; g.K = 2 * L.C;
+    g.bias = h->head_b.as<float>(); g.out_f32 = lg ? lg + (size_t)i0 * c.num_classes : nullptr;
+    g.out2_f32 = pr ? pr + (size_t)i0 * c.num_classes : nullptr;
+    HIPTS_TRY(launch_gemm(EPI_HEAD, g, s));
+    return HIPTS_OK;
+}
+
+int sw_forward_impl(hipts_swinv2* h, const void* input, int in_memspace, bool is_u8, int batch, float* logits_out, float* probs_out,
+                    int out_memspace, hipStream_t s, int stop_stage = -1) {
+    HIPTS_REQUIRE(h && input && batch >= 1, "hipts_swinv2_forward: bad arguments");
+    HIPTS_REQUIRE(batch <= h->cfg.max_batch, "batch %d exceeds max_batch %d", batch, h->cfg.max_batch);
+    if (!h->missing.empty())
+        return set_error(HIPTS_ERR_STATE, "hipts_swinv2_forward: %zu checkpoint tensors not set (first: %s)", h->missing.size(),
+                         h->missing[0].c_str());
+    HIPTS_TRY(use_device(h->device));
+    HIPTS_TRY(sw_prepare_cpb(h));
+    const auto& c = h->cfg;
+    const int S = c.image_size, NC = c.num_classes;
+    const void* in_dev = input;
+    if (in_memspace != HIPTS_DEVICE) {
+        const size_t bytes = (size_t)batch * S * S * 3 * (is_u8 ? 1 : 4);
+        HIPTS_TRY(h->img_in.reserve(bytes));
+        HIPTS_HIP(hipMemcpyAsync(h->img_in.p, input, bytes, hipMemcpyHostToDevice, s));
+        in_dev = h->img_in.p;
+    }
+    const bool dev_out = out_memspace == HIPTS_DEVICE;
+    float* lg = dev_out ? logits_out : (logits_out ? h->logits.as<float>() : nullptr);
+    float* pr = dev_out ? probs_out : (probs_out ? h->probs.as<float>() : nullptr);
+    // Two sub-batches on two internal streams from 32 images on (as the other forwards); the split changes which images share a
+    // launch, never an image's arithmetic.
+    const int ns = (stop_stage < 0 && batch >= 32) ? hipts_swinv2::NSUB : 1;
+    if (ns >= 2) {
+        if (!h->ev_fork) {
+            HIPTS_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+            for (int i = 0; i < hipts_swinv2::NSUB; ++i) {
+                HIPTS_HIP(hipStreamCreateWithFlags(&h->sub[i], hipStreamNonBlocking));
+                HIPTS_HIP(hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
+            }
+        }
+        HIPTS_HIP(hipEventRecord(h->ev_fork, s));
+        for (int i = 0; i < ns; ++i) {
+            const int a0 = i ? (batch + 1) / 2 : 0, a1 = i ? batch : (batch + 1) / 2;
+            HIPTS_HIP(hipStreamWaitEvent(h->sub[i], h->ev_fork, 0));
+            HIPTS_TRY(sw_run_images(h, in_dev, is_u8, a0, a1 - a0, lg, pr, h->sub[i], true, -1));
+            HIPTS_HIP(hipEventRecord(h->ev_join[i], h->sub[i]));
+            HIPTS_HIP(hipStreamWaitEvent(s, h->ev_join[i], 0));
+        }
+    } else {
+        HIPTS_TRY(sw_run_images(h, in_dev, is_u8, 0, batch, lg, pr, s, false, stop_stage));
+    }
+    if (stop_stage < 0 && !dev_out) {
+        if (logits_out) HIPTS_HIP(hipMemcpyAsync(logits_out, lg, (size_t)batch * NC * 4, hipMemcpyDeviceToHost, s));
+        if (probs_out) HIPTS_HIP(hipMemcpyAsync(probs_out, pr, (size_t)batch * NC * 4, hipMemcpyDeviceToHost, s));
+        HIPTS_HIP(hipStreamSynchronize(s));
+    }
+    return HIPTS_OK;
+}
+
+float half_bits_to_f32(uint16_t v, bool f16) {
+    if (!f16) {
+        const uint32_t u = (uint32_t)v << 16;
+        float f;
+        memcpy(&f, &u, 4);
+        return f;
+    }
+    const int e = (v >> 10) & 31, m = v & 1023;
+    const float sgn = (v & 0x8000) ? -1.0f : 1.0f;
+    if (e == 0) return sgn * std::ldexp((float)m, -24);
+    if (e == 31) return m ? NAN : sgn * INFINITY;
+    return sgn * std::ldexp((float)(m | 1024), e - 25);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hipts_swinv2_create(const hipts_swinv2_config_t* cfg, int device, hipts_swinv2_t** out) {
+    HIPTS_REQUIRE(cfg && out, "hipts_swinv2_create: null argument");
+    HIPTS_REQUIRE(cfg->patch == 4, "patch = %d: only 4 is built", cfg->patch);
+    HIPTS_REQUIRE(cfg->image_size >= 32 && cfg->image_size % 32 == 0, "image_size %d must be a positive multiple of 32", cfg->image_size);
+    HIPTS_REQUIRE(cfg->max_batch >= 1, "max_batch must be >= 1");
+    HIPTS_REQUIRE(cfg->num_classes >= 1, "num_classes must be >= 1");
+    HIPTS_REQUIRE(cfg->operand_f16 == 0 || cfg->operand_f16 == 1, "operand_f16 = %d: 0 (bf16) or 1 (IEEE half)", cfg->operand_f16);
+    HIPTS_REQUIRE(cfg->ln_eps > 0.f, "ln_eps must be positive");
+    HIPTS_REQUIRE(cfg->gelu_tanh == 0 || cfg->gelu_tanh == 1, "gelu_tanh = %d: 0 (erf) or 1 (tanh)", cfg->gelu_tanh);
+    HIPTS_REQUIRE(cfg->mlp_ratio >= 1 && cfg->mlp_ratio <= 16, "mlp_ratio = %d must be in [1, 16]", cfg->mlp_ratio);
+    HIPTS_REQUIRE(cfg->cpb_pretrained_window == 0 || cfg->cpb_pretrained_window >= 2, "cpb_pretrained_window = %d: 0 or >= 2",
+                  cfg->cpb_pretrained_window);
+    HIPTS_REQUIRE(cfg->window >= 2, "window = %d must be >= 2", cfg->window);
+    for (int i = 0; i < 3; ++i)
+        HIPTS_REQUIRE(cfg->norm_std[i] > 0.f && std::isfinite(cfg->norm_std[i]) && std::isfinite(cfg->norm_mean[i]), "norm_std[%d] must be positive", i);
+    int H = cfg->image_size / 4;
+    for (int s = 0; s < 4; ++s, H /= 2) {
+        HIPTS_REQUIRE(cfg->dims[s] >= 64 && cfg->dims[s] % 64 == 0 && cfg->dims[s] <= 1024, "dims[%d] = %d must be a multiple of 64, at most 1024",
+                      s, cfg->dims[s]);
+        HIPTS_REQUIRE(cfg->heads[s] >= 1 && cfg->dims[s] == 32 * cfg->heads[s], "stage %d: dims %d / heads %d: head_dim must be 32", s,
+                      cfg->dims[s], cfg->heads[s]);
+        HIPTS_REQUIRE(cfg->depths[s] >= 1, "depths[%d] must be >= 1", s);
+        const int w = std::min(H, cfg->window);
+        HIPTS_REQUIRE(w >= 2 && H % w == 0, "stage %d: window %d does not divide the side %d", s, w, H);
+        HIPTS_REQUIRE(w * w <= 256, "stage %d: window %d has %d tokens (at most 256)", s, w, w * w);
+    }
+    HIPTS_TRY(use_device(device));
+    auto* h = new hipts_swinv2();
+    h->device = device;
+    h->cfg = *cfg;
+    const int B = cfg->max_batch;
+    double flops = 0.0;
+    H = cfg->image_size / 4;
+    flops += 2.0 * H * H * cfg->dims[0] * 48.0;
+    for (int s = 0; s < 4; ++s) {
+        SwStage& St = h->st[s];
+        if (s > 0) H /= 2;
+        St.C = cfg->dims[s];
+        St.H = H;
+        St.T = H * H;
+        St.heads = cfg->heads[s];
+        St.win = std::min(H, cfg->window);
+        St.hid = cfg->mlp_ratio * St.C;
+        St.blocks.resize(cfg->depths[s]);
+        for (int j = 0; j < cfg->depths[s]; ++j) St.blocks[j].shift = (j % 2 == 1 && H > cfg->window) ? cfg->window / 2 : 0;
+        const double T = St.T, C = St.C;
+        if (s > 0) {
+            flops += 2.0 * T * C * 4.0 * cfg->dims[s - 1];
+            h->pcol = std::max(h->pcol, (size_t)St.T * 8 * cfg->dims[s - 1]);
+        }
+        // q | k | v, proj, fc1, fc2; Q K^T and P V over the window's tokens
+        flops += cfg->depths[s] * (2.0 * T * C * (3.0 * C + C + 2.0 * St.hid) + 4.0 * T * (double)(St.win * St.win) * C);
+        h->px = std::max(h->px, (size_t)St.T * St.C);
+        h->p3c = std::max(h->p3c, (size_t)St.T * 3 * St.C);
+        h->phid = std::max(h->phid, (size_t)St.T * St.hid);
+    }
+    flops += 2.0 * cfg->dims[3] * (double)cfg->num_classes;
+    h->flops_per_image = flops;
+    const int C3 = cfg->dims[3];
+    std::vector<float> lut(3 * 256);
+    for (int cc = 0; cc < 3; ++cc)
+        for (int u = 0; u < 256; ++u) lut[cc * 256 + u] = ((float)u / 255.0f - cfg->norm_mean[cc]) / cfg->norm_std[cc];      // ToTensor + Normalize, float32
+    int st = 0;
+    if ((st = sw_upload_f32(h->lut, lut.data(), lut.size())) || (st = h->a0.alloc((size_t)B * h->st[0].T * CNX_STEM_K * 2)) ||
+        (st = h->x.alloc((size_t)B * h->px * 4)) || (st = h->xh.alloc((size_t)B * h->px * 2)) || (st = h->xh2.alloc((size_t)B * h->px * 4)) || (st = h->qkv.alloc((size_t)B * h->p3c * 4)) ||
+        (st = h->ao.alloc((size_t)B * h->px * 2)) || (st = h->br.alloc((size_t)B * h->px * 4)) || (st = h->m1.alloc((size_t)B * h->phid * 2)) ||
+        (st = h->col.alloc((size_t)B * h->pcol * 2)) || (st = h->feat.alloc((size_t)B * C3 * 4)) || (st = h->feat2.alloc((size_t)B * 2 * C3 * 2)) ||
+        (st = h->logits.alloc((size_t)B * cfg->num_classes * 4)) || (st = h->probs.alloc((size_t)B * cfg->num_classes * 4))) {
+        delete h;
+        return st;
+    }
+    for (int s = 1; s < 4; ++s) {
+        const std::vector<float> zero(h->st[s].C, 0.f);
+        if ((st = sw_upload_f32(h->st[s].ds_b, zero.data(), zero.size()))) {
+            delete h;
+            return st;
+        }
+    }
+    auto need = [&](const std::string& k) { h->missing.push_back(k); };
+    need("patch_embed.proj.weight"); need("patch_embed.proj.bias"); need("patch_embed.norm.weight"); need("patch_embed.norm.bias");
+    for (int s = 0; s < 4; ++s) {
+        const std::string sp = "layers." + std::to_string(s) + ".";
+        if (s > 0) {
+            need(sp + "downsample.reduction.weight"); need(sp + "downsample.norm.weight"); need(sp + "downsample.norm.bias");
+        }
+        for (int i = 0; i < cfg->depths[s]; ++i) {
+            const std::string p = sp + "blocks." + std::to_string(i) + ".";
+            for (const char* k : {"attn.qkv.weight", "attn.q_bias", "attn.v_bias", "attn.logit_scale", "attn.cpb_mlp.0.weight", "attn.cpb_mlp.0.bias",
+                                  "attn.cpb_mlp.2.weight", "attn.proj.weight", "attn.proj.bias", "norm1.weight", "norm1.bias", "mlp.fc1.weight",
+                                  "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias", "norm2.weight", "norm2.bias"})
+                need(p + k);
+        }
+    }
+    need("norm.weight"); need("norm.bias"); need("head.fc.weight"); need("head.fc.bias");
+    *out = h;
+    return HIPTS_OK;
+}
+
+int hipts_swinv2_destroy(hipts_swinv2_t* h) {
+    if (h) {
+        (void)hipSetDevice(h->device);
+        (void)hipDeviceSynchronize();
+        for (int i = 0; i < hipts_swinv2::NSUB; ++i) {
+            if (h->sub[i]) (void)hipStreamDestroy(h->sub[i]);
+            if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]);
+        }
+        if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
+        delete h;
+    }
+    return HIPTS_OK;
+}
+
+int hipts_swinv2_set_tensor(hipts_swinv2_t* h, const char* key_c, const float* data, int64_t numel) {
+    HIPTS_REQUIRE(h && key_c && data, "hipts_swinv2_set_tensor: null argument");
+    HIPTS_TRY(use_device(h->device));
+    const std::string key(key_c);
+    const auto& cf = h->cfg;
+    const bool f16 = (cf.operand_f16 & 1) != 0;
+    int st = HIPTS_OK;
+#define EXPECT(n)                                                                                                         \
+    do {                                                                                                                  \
+        if (numel != (int64_t)(n)) return set_error(HIPTS_ERR_INVALID, "tensor %s: %lld elements, expected %lld", key_c, (long long)numel, (long long)(n)); \
+    } while (0)
+    const int C0 = cf.dims[0], C3 = cf.dims[3], NC = cf.num_classes;
+    if (key == "patch_embed.proj.weight") {
+        EXPECT((int64_t)C0 * 48);
+        // [n][c_model][ky][kx] -> [n][(ky*4 + kx)*3 + c_mem], c_model = 2 - c_mem (BGR), duplicated for the hi | lo halves (cnx_stem_kernel)
+        std::vector<float> w2((size_t)C0 * CNX_STEM_K, 0.f);
+        for (int n = 0; n < C0; ++n)
+            for (int cm = 0; cm < 3; ++cm)
+                for (int t = 0; t < 16; ++t) {
+                    const float v = data[((size_t)n * 3 + (2 - cm)) * 16 + t];
+                    w2[(size_t)n * CNX_STEM_K + t * 3 + cm] = v;
+                    w2[(size_t)n * CNX_STEM_K + CNX_STEM_KH + t * 3 + cm] = v;
+                }
+        st = upload_matrix16(h->stem_w, w2.data(), C0, CNX_STEM_K, round_up(C0, 256), f16);
+    } else if (key == "patch_embed.proj.bias") { EXPECT(C0); st = sw_upload_f32(h->stem_b, data, C0); }
+    else if (key == "patch_embed.norm.weight") { EXPECT(C0); st = sw_upload_f32(h->stem_nw, data, C0); }
+    else if (key == "patch_embed.norm.bias") { EXPECT(C0); st = sw_upload_f32(h->stem_nb, data, C0); }
+    else if (key == "norm.weight") { EXPECT(C3); st = sw_upload_f32(h->head_nw, data, C3); }
+    else if (key == "norm.bias") { EXPECT(C3); st = sw_upload_f32(h->head_nb, data, C3); }
+    else if (key == "head.fc.bias") { EXPECT(NC); st = sw_upload_f32(h->head_b, data, NC); }
+    else if (key == "head.fc.weight") {
+        EXPECT((int64_t)NC * C3);
+        std::vector<float> dup((size_t)NC * 2 * C3);
+        for (int n = 0; n < NC; ++n)
+            for (int k = 0; k < C3; ++k) dup[(size_t)n * 2 * C3 + k] = dup[(size_t)n * 2 * C3 + C3 + k] = data[(size_t)n * C3 + k];
+        st = upload_matrix16(h->head_w, dup.data(), NC, 2 * C3, round_up(NC, 256), f16);
+    } else if (key.rfind("layers.", 0) == 0) {
+        const size_t d1 = key.find('.', 7);
+        if (d1 == std::string::npos) return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
+        const int s = atoi(key.substr(7, d1 - 7).c_str());
+        if (s < 0 || s > 3) return set_error(HIPTS_ERR_INVALID, "tensor %s: stage out of range", key_c);
+        SwStage& St = h->st[s];
+        const int C = St.C;
+        const std::string sub = key.substr(d1 + 1);
+        if (sub.rfind("downsample.", 0) == 0) {
+            if (s == 0) return set_error(HIPTS_ERR_INVALID, "tensor %s: stage 0 has no downsample", key_c);
+            const int Cp = cf.dims[s - 1];
+            if (sub == "downsample.norm.weight") { EXPECT(C); st = sw_upload_f32(St.ds_nw, data, C); }
+            else if (sub == "downsample.norm.bias") { EXPECT(C); st = sw_upload_f32(St.ds_nb, data, C); }
+            else if (sub == "downsample.reduction.weight") {
+                EXPECT((int64_t)C * 4 * Cp);            // columns in timm's (dx, dy, c) order: the order sw_merge_kernel writes; [W | W]
+                std::vector<float> dup((size_t)C * 8 * Cp);
+                for (int n = 0; n < C; ++n)
+                    for (int k = 0; k < 4 * Cp; ++k) dup[(size_t)n * 8 * Cp + k] = dup[(size_t)n * 8 * Cp + 4 * Cp + k] = data[(size_t)n * 4 * Cp + k];
+                st = upload_matrix16(St.ds_w, dup.data(), C, 8 * Cp, round_up(C, 256), f16);
+            } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
+        } else if (sub.rfind("blocks.", 0) == 0) {
+            const size_t d2 = sub.find('.', 7);
+            if (d2 == std::string::npos) return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
+            const int bi = atoi(sub.substr(7, d2 - 7).c_str());
+            if (bi < 0 || bi >= (int)St.blocks.size()) return set_error(HIPTS_ERR_INVALID, "tensor %s: block out of range", key_c);
+            SwBlock& B = St.blocks[bi];
+            const std::string t = sub.substr(d2 + 1);
+            const int nh = St.heads;
+            if (t == "attn.qkv.weight") {
+                EXPECT((int64_t)3 * C * C);
+                std::vector<float> dup((size_t)3 * C * 2 * C);       // against [hi | lo] of x: [W | W]
+                for (int n = 0; n < 3 * C; ++n)
+                    for (int k = 0; k < C; ++k) dup[(size_t)n * 2 * C + k] = dup[(size_t)n * 2 * C + C + k] = data[(size_t)n * C + k];
+                st = upload_matrix16(B.qkv2, dup.data(), 3 * C, 2 * C, round_up(3 * C, 256), f16);
+            }
+            else if (t == "attn.q_bias" || t == "attn.v_bias") {
+                EXPECT(C);
+                if (B.qkv_bh.empty()) B.qkv_bh.assign((size_t)3 * C, 0.f);        // [q_bias | 0 | v_bias]: timm's k bias is a zero buffer
+                std::copy(data, data + C, B.qkv_bh.begin() + (t == "attn.q_bias" ? 0 : 2 * C));
+                st = sw_upload_f32(B.qkv_b, B.qkv_bh.data(), B.qkv_bh.size());
+            }
+            else if (t == "attn.logit_scale") { EXPECT(nh); st = sw_upload_f32(B.ls, data, nh); }
+            else if (t == "attn.cpb_mlp.0.weight") { EXPECT(2 * SW_CPB_HIDDEN); B.cpb_w1.assign(data, data + 2 * SW_CPB_HIDDEN); h->cpb_ready = false; }
+            else if (t == "attn.cpb_mlp.0.bias") { EXPECT(SW_CPB_HIDDEN); B.cpb_b1.assign(data, data + SW_CPB_HIDDEN); h->cpb_ready = false; }
+            else if (t == "attn.cpb_mlp.2.weight") {
+                EXPECT((int64_t)nh * SW_CPB_HIDDEN);
+                B.cpb_w2.assign(data, data + (size_t)nh * SW_CPB_HIDDEN);
+                h->cpb_ready = false;
+            }
+            else if (t == "attn.proj.weight") { EXPECT((int64_t)C * C); st = upload_matrix16(B.proj, data, C, C, round_up(C, 256), f16); }
+            else if (t == "attn.proj.bias") { EXPECT(C); st = sw_upload_f32(B.proj_b, data, C); }
+            else if (t == "norm1.weight") { EXPECT(C); st = sw_upload_f32(B.n1_w, data, C); }
+            else if (t == "norm1.bias") { EXPECT(C); st = sw_upload_f32(B.n1_b, data, C); }
+            else if (t == "norm2.weight") { EXPECT(C); st = sw_upload_f32(B.n2_w, data, C); }
+            else if (t == "norm2.bias") { EXPECT(C); st = sw_upload_f32(B.n2_b, data, C); }
+            else if (t == "mlp.fc1.weight") {
+                EXPECT((int64_t)St.hid * C);
+                std::vector<float> dup((size_t)St.hid * 2 * C);      // against [hi | lo] of x: [W | W]
+                for (int n = 0; n < St.hid; ++n)
+                    for (int k = 0; k < C; ++k) dup[(size_t)n * 2 * C + k] = dup[(size_t)n * 2 * C + C + k] = data[(size_t)n * C + k];
+                st = upload_matrix16(B.fc1, dup.data(), St.hid, 2 * C, round_up(St.hid, 256), f16);
+            }
+            else if (t == "mlp.fc1.bias") { EXPECT(St.hid); st = sw_upload_f32(B.fc1_b, data, St.hid); }
+            else if (t == "mlp.fc2.weight") { EXPECT((int64_t)St.hid * C); st = upload_matrix16(B.fc2, data, C, St.hid, round_up(C, 256), f16); }
+            else if (t == "mlp.fc2.bias") { EXPECT(C); st = sw_upload_f32(B.fc2_b, data, C); }
+            else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
+        } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
+    } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
+#undef EXPECT
+    if (st) return st;
+    auto it = std::find(h->missing.begin(), h->missing.end(), key);
+    if (it != h->missing.end()) h->missing.erase(it);
+    return HIPTS_OK;
+}
+
+int hipts_swinv2_forward_u8(hipts_swinv2_t* h, const uint8_t* images, int images_memspace, int batch, float* logits_out, float* probs_out,
+                            int out_memspace, void* stream) {
+    return sw_forward_impl(h, images, images_memspace, true, batch, logits_out, probs_out, out_memspace, (hipStream_t)stream);
+}
+
+int hipts_swinv2_forward_f32(hipts_swinv2_t* h, const float* x, int x_memspace, int batch, float* logits_out, float* probs_out,
+                             int out_memspace, void* stream) {
+    return sw_forward_impl(h, x, x_memspace, false, batch, logits_out, probs_out, out_memspace, (hipStream_t)stream);
+}
+
+int hipts_swinv2_flops_per_image(const hipts_swinv2_t* h, double* flops) {
+    HIPTS_REQUIRE(h && flops, "null argument");
+    *flops = h->flops_per_image;
+    return HIPTS_OK;
+}
+
+// Debug / test entry (include/hip_tagsearch_debug.h): the float32 residual stream [batch][H*H][dims[stage]] after the last block of
+// `stage`, from host float32 input (the layout of hipts_swinv2_forward_f32).
+int hiptsdbg_swinv2_stream(hipts_swinv2_t* h, const float* x_host, int batch, int stage, float* out_host) {
+    HIPTS_REQUIRE(h && x_host && out_host && stage >= 0 && stage <= 3, "hiptsdbg_swinv2_stream: bad argument");
+    HIPTS_TRY(sw_forward_impl(h, x_host, HIPTS_HOST, false, batch, nullptr, nullptr, HIPTS_HOST, nullptr, stage));
+    HIPTS_HIP(hipDeviceSynchronize());
+    HIPTS_HIP(hipMemcpy(out_host, h->x.p, (size_t)batch * h->st[stage].T * h->st[stage].C * 4, hipMemcpyDeviceToHost));
+    return HIPTS_OK;
+}
+
+// Debug / test entry: the window attention kernel alone (include/hip_tagsearch_debug.h).
+int hiptsdbg_swinv2_window_attention(const float* q, const float* k, const float* v, const float* logit_scale, const float* cpb, int batch,
+                                     int heads, int side, int window, int shift, int operand_f16, float* out) {
+    HIPTS_REQUIRE(q && k && v && logit_scale && cpb && out && batch >= 1 && heads >= 1 && side >= 1, "hiptsdbg_swinv2_window_attention: bad argument");
+    HIPTS_REQUIRE(operand_f16 == 0 || operand_f16 == 1, "operand_f16 must be 0 or 1");
+    HIPTS_REQUIRE(window >= 2 && window <= 16, "window %d out of range", window);
+    const int C = 32 * heads;
+    const size_t M = (size_t)batch * side * side, nb = (size_t)(2 * window - 1) * (2 * window - 1);
+    std::vector<float> packed(M * 3 * C);
+    for (size_t m = 0; m < M; ++m) {
+        std::copy(q + m * C, q + (m + 1) * C, packed.begin() + m * 3 * C);
+        std::copy(k + m * C, k + (m + 1) * C, packed.begin() + m * 3 * C + C);
+        std::copy(v + m * C, v + (m + 1) * C, packed.begin() + m * 3 * C + 2 * C);
+    }
+    DevBuf dqkv, dls, dcpb, dout;
+    HIPTS_TRY(sw_upload_f32(dqkv, packed.data(), packed.size()));
+    HIPTS_TRY(sw_upload_f32(dls, logit_scale, heads));
+    HIPTS_TRY(sw_upload_f32(dcpb, cpb, (size_t)heads * nb));
+    HIPTS_TRY(dout.alloc(M * C * 2));
+    HIPTS_TRY(launch_swin_attention(dqkv.as<float>(), dls.as<float>(), dcpb.as<float>(), dout.as<bf16_t>(), batch, side, window, shift, heads,
+                                    operand_f16 == 1, nullptr));
+    HIPTS_HIP(hipDeviceSynchronize());
+    std::vector<uint16_t> o16(M * C);
+    HIPTS_HIP(hipMemcpy(o16.data(), dout.p, M * C * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < M * C; ++i) out[i] = half_bits_to_f32(o16[i], operand_f16 == 1);
+    return HIPTS_OK;
+}
+
+}  // extern "C"

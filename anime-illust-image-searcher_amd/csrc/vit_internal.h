@@ -314,6 +314,12 @@ inline float split_lo_scale(bool f16) {
 
 int attention2_read_stamps(unsigned long long* host, int n);      // measurement-only builds (HIPTS_X_STAMPS)
 
+// swin_attn.hip: SwinV2 window attention, head_dim 32, window^2 <= 256 tokens: qkv float32 [batch * side^2][3 * 32 heads] (raster order, bias
+// added), logit_scale [heads] (raw), cpb [heads][(2 window - 1)^2] (16 sigmoid(cpb_mlp)), out 16-bit [batch * side^2][32 heads]; the
+// windows of a block with shift > 0 are rolled by -shift first (index math only).
+int launch_swin_attention(const float* qkv, const float* logit_scale, const float* cpb, bf16_t* out, int batch, int side, int window,
+                          int shift, int heads, bool f16, hipStream_t s);
+
 // out[row][:] = bf16((x[row][:] - mean) * rstd * g + b)  (b may be null: bias-free LayerNorm); D % 4 == 0, D <= 1024
 int launch_layernorm(const float* x, const float* g, const float* b, bf16_t* out, int64_t rows, int D, float eps, bool f16,
                      hipStream_t s);

@@ -44,6 +44,13 @@ class ConvnextConfig(ctypes.Structure):
                 ("norm_mean", c_float * 3), ("norm_std", c_float * 3), ("max_batch", c_int32), ("operand_f16", c_int32)]
 
 
+class Swinv2Config(ctypes.Structure):
+    _fields_ = [("image_size", c_int32), ("patch", c_int32), ("window", c_int32), ("dims", c_int32 * 4), ("depths", c_int32 * 4),
+                ("heads", c_int32 * 4), ("mlp_ratio", c_int32), ("num_classes", c_int32), ("ln_eps", c_float), ("gelu_tanh", c_int32),
+                ("cpb_pretrained_window", c_int32), ("norm_mean", c_float * 3), ("norm_std", c_float * 3), ("max_batch", c_int32),
+                ("operand_f16", c_int32)]
+
+
 # name -> (argtypes); every function returns int status unless listed in _PLAIN
 _SIGNATURES = {
     "hipts_abi_version": [],
@@ -75,6 +82,12 @@ _SIGNATURES = {
     "hipts_convnext_forward_u8": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "hipts_convnext_forward_f32": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "hipts_convnext_flops_per_image": [c_void_p, POINTER(c_double)],
+    "hipts_swinv2_create": [POINTER(Swinv2Config), c_int, POINTER(c_void_p)],
+    "hipts_swinv2_destroy": [c_void_p],
+    "hipts_swinv2_set_tensor": [c_void_p, c_char_p, c_void_p, c_int64],
+    "hipts_swinv2_forward_u8": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    "hipts_swinv2_forward_f32": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    "hipts_swinv2_flops_per_image": [c_void_p, POINTER(c_double)],
     "hipts_ccip_create": [POINTER(CcipConfig), c_int, POINTER(c_void_p)],
     "hipts_ccip_destroy": [c_void_p],
     "hipts_ccip_set_tensor": [c_void_p, c_char_p, c_void_p, c_int64],
@@ -162,7 +175,7 @@ def load():
         fn.restype = c_int
     lib.hipts_jpeg_slot_bytes.restype = ctypes.c_int64      # the one entry point that returns a size, not a status
     # the three configuration structures are passed by pointer: a layout that differs from the library's would be read past
-    for kind, st in enumerate((VitConfig, EvaConfig, CcipConfig, ConvnextConfig)):
+    for kind, st in enumerate((VitConfig, EvaConfig, CcipConfig, ConvnextConfig, Swinv2Config)):
         n = c_size_t(0)
         if lib.hipts_sizeof_config(kind, ctypes.byref(n)) != 0 or n.value != ctypes.sizeof(st):
             raise ImportError("%s is %d bytes here but %d in libhip_tagsearch.so: binding and library are out of step"

@@ -25,6 +25,15 @@ CONVNEXT_B_448 = dict(image_size=448, dims=(128, 256, 512, 1024), depths=(3, 3, 
 # test geometry: sides 16 / 8 / 4 / 2, the same widths (and so the same kernels) as B
 CONVNEXT_TINY = dict(image_size=64, dims=(128, 256, 512, 1024), depths=(1, 1, 2, 1), num_classes=200, ln_eps=1e-6,
                      norm_mean=(0.5, 0.5, 0.5), norm_std=(0.5, 0.5, 0.5), operand_f16=1)
+# timm swinv2_base_window8_256 built with img_size 448, window_size 14 (wd-swinv2-tagger-v3); window, GELU form, transform mean / std and
+# the position-bias normalisation window are assumptions (the checkpoint's config.json is not read here), see DESIGN.md
+SWINV2_B_448 = dict(image_size=448, patch=4, window=14, dims=(128, 256, 512, 1024), depths=(2, 2, 18, 2), heads=(4, 8, 16, 32), mlp_ratio=4,
+                    num_classes=10861, ln_eps=1e-5, gelu_tanh=0, cpb_pretrained_window=0, norm_mean=(0.5, 0.5, 0.5), norm_std=(0.5, 0.5, 0.5),
+                    operand_f16=1)
+# test geometry: sides 56 / 28 / 14 / 7 with window 7 -- three shifted stages, the last one unshifted, 49-token windows (padded keys)
+SWINV2_TINY = dict(image_size=224, patch=4, window=7, dims=(64, 128, 256, 512), depths=(2, 2, 2, 2), heads=(2, 4, 8, 16), mlp_ratio=4,
+                   num_classes=200, ln_eps=1e-5, gelu_tanh=0, cpb_pretrained_window=0, norm_mean=(0.5, 0.5, 0.5), norm_std=(0.5, 0.5, 0.5),
+                   operand_f16=1)
 # CCIP feature encoder (gen_cfeatures.py): CAFormer-B36 widths at 384 px, 768-d feature
 CCIP_B36_384 = dict(image_size=384, dims=(128, 256, 512, 768), depths=(3, 12, 18, 3), head_dim=32, ln_eps=1e-6)
 CCIP_TINY = dict(image_size=64, dims=(64, 64, 128, 128), depths=(1, 1, 2, 1), head_dim=32, ln_eps=1e-6)
@@ -210,6 +219,71 @@ def convnext_weights(cfg: Dict, seed: int = 0, trained_like: bool = False, bf16_
             for j in range(depths[i]):
                 w["stages.%d.blocks.%d.gamma" % (i, j)] = np.exp(rng2.uniform(np.log(1e-4), 0.0, dims[i])).astype(np.float32)
         w["stages.2.blocks.0.gamma"] = np.full(dims[2], 1e-6, dtype=np.float32)
+        h = {"head.weight": w.pop("head.fc.weight"), "head.bias": w.pop("head.fc.bias")}
+        _trained_like_head(rng2, h, C)
+        w["head.fc.weight"], w["head.fc.bias"] = h["head.weight"], h["head.bias"]
+    return w
+
+
+def swinv2_weights(cfg: Dict, seed: int = 0, trained_like: bool = False, bf16_matrices: bool = True) -> Dict[str, np.ndarray]:
+    """Random-init SwinV2 checkpoint with timm `SwinTransformerV2` state_dict keys (>= 0.9 layout: patch_embed.{proj, norm},
+    layers.{i}.downsample.{reduction, norm}, layers.{i}.blocks.{j}.{attn.{qkv, q_bias, v_bias, logit_scale, cpb_mlp.0, cpb_mlp.2, proj},
+    norm1, mlp.fc1, mlp.fc2, norm2}, norm, head.fc).  Logit scales at timm's initial ln 10; cpb_mlp weights that give a spread,
+    unsaturated position bias (16 sigmoid of ~N(0, 1)); the post-norm gains at 0.2-0.6 so that every block's branches matter.
+    trained_like: per-head logit scales spread from ln 10 to past the clamp at ln 100 (head 0 of every block above it), the heads
+    above ln 50 made local (k projection = q projection + noise), and the tagger head of _trained_like_head (sparse probabilities)."""
+    rng = np.random.default_rng(seed)
+    dims, depths, heads, C = cfg["dims"], cfg["depths"], cfg["heads"], cfg["num_classes"]
+    r = cfg.get("mlp_ratio", 4)
+    rb = round_to_bf16 if bf16_matrices else (lambda a: a)
+    w: Dict[str, np.ndarray] = {}
+
+    def ln(prefix, d, lo=0.5, hi=1.5):
+        w[prefix + ".weight"] = rng.uniform(lo, hi, d).astype(np.float32)
+        w[prefix + ".bias"] = _trunc_normal(rng, (d,), 0.02)
+    w["patch_embed.proj.weight"] = rb(_trunc_normal(rng, (dims[0], 3, 4, 4), 0.1))
+    w["patch_embed.proj.bias"] = _trunc_normal(rng, (dims[0],), 0.02)
+    ln("patch_embed.norm", dims[0])
+    for i in range(4):
+        d, nh = dims[i], heads[i]
+        if i > 0:
+            w["layers.%d.downsample.reduction.weight" % i] = rb(_trunc_normal(rng, (d, 4 * dims[i - 1]), (4.0 * dims[i - 1]) ** -0.5))
+            ln("layers.%d.downsample.norm" % i, d)
+        for j in range(depths[i]):
+            p = "layers.%d.blocks.%d." % (i, j)
+            w[p + "attn.qkv.weight"] = rb(_trunc_normal(rng, (3 * d, d), d ** -0.5))
+            w[p + "attn.q_bias"] = _trunc_normal(rng, (d,), 0.02)
+            w[p + "attn.v_bias"] = _trunc_normal(rng, (d,), 0.02)
+            w[p + "attn.logit_scale"] = np.full((nh, 1, 1), np.log(10.0), dtype=np.float32)
+            w[p + "attn.cpb_mlp.0.weight"] = rng.standard_normal((512, 2)).astype(np.float32)
+            w[p + "attn.cpb_mlp.0.bias"] = (0.5 * rng.standard_normal(512)).astype(np.float32)
+            w[p + "attn.cpb_mlp.2.weight"] = _trunc_normal(rng, (nh, 512), 1.0 / np.sqrt(512.0))
+            w[p + "attn.proj.weight"] = rb(_trunc_normal(rng, (d, d), d ** -0.5))
+            w[p + "attn.proj.bias"] = _trunc_normal(rng, (d,), 0.02)
+            ln(p + "norm1", d, 0.2, 0.6)
+            w[p + "mlp.fc1.weight"] = rb(_trunc_normal(rng, (r * d, d), d ** -0.5))
+            w[p + "mlp.fc1.bias"] = _trunc_normal(rng, (r * d,), 0.02)
+            w[p + "mlp.fc2.weight"] = rb(_trunc_normal(rng, (d, r * d), (float(r) * d) ** -0.5))
+            w[p + "mlp.fc2.bias"] = _trunc_normal(rng, (d,), 0.02)
+            ln(p + "norm2", d, 0.2, 0.6)
+    ln("norm", dims[3])
+    w["head.fc.weight"] = rb(_trunc_normal(rng, (C, dims[3]), 0.02))
+    w["head.fc.bias"] = _trunc_normal(rng, (C,), 0.02)
+    if trained_like:
+        rng2 = np.random.default_rng(seed + 7919)
+        for i in range(4):
+            for j in range(depths[i]):
+                s = rng2.uniform(np.log(10.0), np.log(100.0) + 0.5, heads[i])
+                s[0] = np.log(150.0)                               # above the clamp at ln 100
+                w["layers.%d.blocks.%d.attn.logit_scale" % (i, j)] = s.astype(np.float32).reshape(-1, 1, 1)
+                # the sharp heads (scale > 50) attend locally, as trained ones do: their k projection is their q projection plus
+                # 30 % noise, so a token's own key leads by a margin instead of random keys racing within the 16-bit rounding
+                d = dims[i]
+                qkv = w["layers.%d.blocks.%d.attn.qkv.weight" % (i, j)]
+                for hh in np.flatnonzero(s > np.log(50.0)):
+                    rows = slice(hh * 32, hh * 32 + 32)
+                    k = qkv[rows] + _trunc_normal(rng2, (32, d), 0.3 * d ** -0.5)
+                    qkv[d + hh * 32:d + hh * 32 + 32] = rb(k)
         h = {"head.weight": w.pop("head.fc.weight"), "head.bias": w.pop("head.fc.bias")}
         _trained_like_head(rng2, h, C)
         w["head.fc.weight"], w["head.fc.bias"] = h["head.weight"], h["head.bias"]

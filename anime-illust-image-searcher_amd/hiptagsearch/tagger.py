@@ -179,8 +179,63 @@ class ConvNeXtTagger(ViTTagger):
             self._h = c_void_p()
 
 
+class SwinV2Tagger(ViTTagger):
+    """Device-resident SwinV2 tagger (wd-swinv2-tagger-v3 = timm swinv2_base_window8_256 built at 448 px with window 14).  Same
+    interface as ViTTagger; `weights` uses timm `SwinTransformerV2` state_dict keys (>= 0.9 layout).  cfg: image_size, patch, window,
+    dims, depths, heads, mlp_ratio, num_classes, ln_eps, gelu_tanh, cpb_pretrained_window, norm_mean / norm_std (the uint8 entry
+    point's Normalize, RGB order) and operand_f16 (1 = IEEE half operands, the default; 0 = bf16)."""
+
+    # timm's non-persistent buffers, which a checkpoint file may still hold: derived from the configuration, never loaded
+    BUFFER_SUFFIXES = ("relative_position_index", "relative_coords_table", "attn_mask", "k_bias")
+
+    def __init__(self, cfg: Dict, weights: Dict[str, np.ndarray], max_batch: int = 64, device: int = 0):
+        self.cfg = dict(cfg)
+        self.device = device
+        self.max_batch = max_batch
+        self.num_classes = cfg["num_classes"]
+        c = _lib.Swinv2Config()
+        c.image_size = cfg["image_size"]
+        c.patch = cfg.get("patch", 4)
+        c.window = cfg["window"]
+        c.dims[:] = list(cfg["dims"])
+        c.depths[:] = list(cfg["depths"])
+        c.heads[:] = list(cfg["heads"])
+        c.mlp_ratio = cfg.get("mlp_ratio", 4)
+        c.num_classes = cfg["num_classes"]
+        c.ln_eps = cfg.get("ln_eps", 1e-5)
+        c.gelu_tanh = cfg.get("gelu_tanh", 0)
+        c.cpb_pretrained_window = cfg.get("cpb_pretrained_window", 0)
+        c.norm_mean[:] = list(cfg.get("norm_mean", (0.5, 0.5, 0.5)))
+        c.norm_std[:] = list(cfg.get("norm_std", (0.5, 0.5, 0.5)))
+        c.max_batch = max_batch
+        c.operand_f16 = cfg.get("operand_f16", 1)
+        self._h = c_void_p()
+        _lib.call("hipts_swinv2_create", ctypes.byref(c), device, ctypes.byref(self._h))
+        for key, val in weights.items():
+            if key.endswith(self.BUFFER_SUFFIXES):
+                continue
+            arr = np.ascontiguousarray(val, dtype=np.float32)
+            _lib.call("hipts_swinv2_set_tensor", self._h, key.encode(), _lib.ptr(arr), ctypes.c_int64(arr.size))
+
+    def flops_per_image(self) -> float:
+        f = c_double()
+        _lib.call("hipts_swinv2_flops_per_image", self._h, ctypes.byref(f))
+        return f.value
+
+    def _run(self, fn: str, x, batch: int, logits, probs):
+        super()._run(fn.replace("hipts_vit", "hipts_swinv2"), x, batch, logits, probs)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.call("hipts_swinv2_destroy", self._h)
+            self._h = c_void_p()
+
+
 def model_class(cfg: Dict):
-    """The tagger class a configuration dict selects: ConvNeXt (stage widths `dims`), EVA02 (SwiGLU width `mlp_hidden`), else ViT."""
+    """The tagger class a configuration dict selects: SwinV2 (a `window`; its dict also has `dims`, so it is tested first), ConvNeXt
+    (stage widths `dims`), EVA02 (SwiGLU width `mlp_hidden`), else ViT."""
+    if "window" in cfg:
+        return SwinV2Tagger
     if "dims" in cfg:
         return ConvNeXtTagger
     if "mlp_hidden" in cfg:
@@ -339,15 +394,19 @@ class Predictor:
         if self.precise:
             if cls_ is ConvNeXtTagger:
                 raise ValueError("precise is an attention-output option (ViT, EVA02); the ConvNeXt tagger has no attention")
+            if cls_ is SwinV2Tagger:
+                raise ValueError("precise is an attention-output option of the ViT and EVA02 taggers; the SwinV2 window attention has none")
             self.cfg["operand_f16"] = int(self.cfg.get("operand_f16", 1)) | 16
         if checkpoint:
             self.tagger_model = cls_.from_safetensors(checkpoint, self.cfg, max_batch=self.max_batch, device=self.device)
         else:
-            name = {EvaTagger: "EVA02", ConvNeXtTagger: "ConvNeXt"}.get(cls_, "ViT")
+            name = {EvaTagger: "EVA02", ConvNeXtTagger: "ConvNeXt", SwinV2Tagger: "SwinV2"}.get(cls_, "ViT")
             print("No checkpoint given: using the seeded synthetic %s weights (no network in this environment)." % name)
             # the trained-like variant (peaked attention, sparse probabilities: tens of labels per image, as a real tagger selects)
             if cls_ is ConvNeXtTagger:
                 weights = synth.convnext_weights(self.cfg, seed, trained_like=True)
+            elif cls_ is SwinV2Tagger:
+                weights = synth.swinv2_weights(self.cfg, seed, trained_like=True)
             else:
                 weights = synth.eva_weights(self.cfg, seed, trained_like=True) if eva else synth.vit_weights(self.cfg, seed, trained_like=True)
             self.tagger_model = cls_(self.cfg, weights, self.max_batch, self.device)

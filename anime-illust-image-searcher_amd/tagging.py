@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """python tagging.py --dir D [--after YYYY-MM-DD]        (same flags as the reference, tagging.py:361-383)
 
-Extra switches: --model vit-b16|eva02-l14|convnext-b, --checkpoint model.safetensors (timm key layout) and --labels
+Extra switches: --model vit-b16|eva02-l14|convnext-b|swinv2-b, --checkpoint model.safetensors (timm key layout) and --labels
 selected_tags.csv for a real wd tagger; without them the seeded synthetic stand-ins are used (no network here).
 --compat reproduces the reference's dropped tail batch; --batch sets the device batch size; --precise trades about 5 % of the
 throughput for the 1e-3 logit tolerance on flat / padded pictures (operand_f16 bit 4).
@@ -26,9 +26,11 @@ def main(arg_str: list) -> None:
     parser.add_argument('--checkpoint', default=None)
     parser.add_argument('--labels', default=None)
     parser.add_argument('--compat', action='store_true')
-    parser.add_argument('--model', choices=['vit-b16', 'eva02-l14', 'convnext-b', 'vit-tiny', 'convnext-tiny'], default='vit-b16',
+    parser.add_argument('--model', choices=['vit-b16', 'eva02-l14', 'convnext-b', 'swinv2-b', 'vit-tiny', 'convnext-tiny', 'swinv2-tiny'],
+                        default='vit-b16',
                         help='vit-b16: wd-vit-tagger-v3 geometry (BASELINE.json contract model); eva02-l14: wd-eva02-large-tagger-v3, the repo tagging.py:45 names; '
-                             'convnext-b: wd-convnext-tagger-v3 (timm convnext_base at 448 px)')
+                             'convnext-b: wd-convnext-tagger-v3 (timm convnext_base at 448 px); '
+                             'swinv2-b: wd-swinv2-tagger-v3 (timm swinv2_base at 448 px, window 14)')
     parser.add_argument('--batch', type=int, default=64)
     parser.add_argument('--workers', type=int, default=0,
                         help='decode / resize in this many processes (shared-memory pipeline) instead of 8 threads')
@@ -49,6 +51,8 @@ def main(arg_str: list) -> None:
     args = parser.parse_args(arg_str)
     if args.precise and args.model.startswith('convnext'):
         parser.error('--precise is an attention-output option (ViT, EVA02): the ConvNeXt tagger has no attention')
+    if args.precise and args.model.startswith('swinv2'):
+        parser.error('--precise is an attention-output option (ViT, EVA02): the SwinV2 window attention has none')
     # under torch.distributed.run (WORLD_SIZE > 1): one process per GPU, the process group comes up before any GPU call
     from hiptagsearch import dist as hdist
     dist, rank, world, device = hdist.init_from_env(args.device)
@@ -56,8 +60,8 @@ def main(arg_str: list) -> None:
     predictor = Predictor(device=device, max_batch=args.batch, compat=args.compat, gpu_resize=args.gpu_resize or args.gpu_jpeg, gpu_jpeg=args.gpu_jpeg,
                           precise=args.precise)
     from hiptagsearch import synth
-    model_cfg = {'vit-b16': synth.VIT_B16_448, 'eva02-l14': synth.EVA02_L14_448, 'convnext-b': synth.CONVNEXT_B_448,
-                 'vit-tiny': synth.VIT_TINY, 'convnext-tiny': synth.CONVNEXT_TINY}[args.model]   # *-tiny: test geometries
+    model_cfg = {'vit-b16': synth.VIT_B16_448, 'eva02-l14': synth.EVA02_L14_448, 'convnext-b': synth.CONVNEXT_B_448, 'swinv2-b': synth.SWINV2_B_448,
+                 'vit-tiny': synth.VIT_TINY, 'convnext-tiny': synth.CONVNEXT_TINY, 'swinv2-tiny': synth.SWINV2_TINY}[args.model]   # *-tiny: test geometries
     after_date = None
     if args.after is not None:
         try:

@@ -45,7 +45,7 @@ int hipts_abi_version(void);
 int hipts_last_error(char* buf, size_t n);
 int hipts_device_count(int* count);
 /* sizeof() of a configuration structure as THIS LIBRARY was compiled: kind 0 = hipts_vit_config_t, 1 = hipts_eva_config_t,
- * 2 = hipts_ccip_config_t, 3 = hipts_convnext_config_t.  A binding in another language compares its own structure's size with it before the first
+ * 2 = hipts_ccip_config_t, 3 = hipts_convnext_config_t, 4 = hipts_swinv2_config_t.  A binding in another language compares its own structure's size with it before the first
  * hipts_*_create (tests/test_abi.py does, for the ctypes structures and for the stubs printed in INTEGRATION.md). */
 int hipts_sizeof_config(int kind, size_t* bytes);
 
@@ -203,6 +203,51 @@ int hipts_convnext_forward_u8(hipts_convnext_t* h, const uint8_t* images, int im
 int hipts_convnext_forward_f32(hipts_convnext_t* h, const float* x, int x_memspace, int batch, float* logits_out, float* probs_out,
                                int out_memspace, void* stream);
 int hipts_convnext_flops_per_image(const hipts_convnext_t* h, double* flops);
+
+/* ------------------------------------------------------------------------------------------
+ * SwinV2 tagger forward -- the windowed-attention member of the wd-tagger v3 family (wd-swinv2-tagger-v3 = timm
+ * swinv2_base_window8_256 built with img_size 448, window_size 14).  Same call sites and output contract as the taggers above.
+ * Graph: stem Conv2d(3, C0, k 4, s 4) + LayerNorm (weight, bias); four stages, stages 1-3 opened by a 2 x 2 patch merging
+ * (Linear(4 C, C', no bias) + LayerNorm); blocks x = x + LN1(proj(WindowAttn(x))), x = x + LN2(fc2(GELU(fc1(x)))) (post-norm),
+ * the window attention a scaled cosine with a continuous position bias (16 sigmoid(cpb_mlp)) and, every other block, shifted
+ * windows; head LayerNorm per token -> mean over tokens -> fc -> sigmoid.  Matrix weights are 16-bit MFMA operands; accumulation,
+ * residual stream, LayerNorms, the cosine's unit vectors (as hi | lo pairs) and the position-bias table in float32.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct hipts_swinv2 hipts_swinv2_t;
+
+typedef struct hipts_swinv2_config {
+    int32_t image_size;      /* 448 (a multiple of 32)                                                         */
+    int32_t patch;           /* 4 (the only patch size built)                                                  */
+    int32_t window;          /* 14; a stage whose side is <= window uses the side as its window, unshifted     */
+    int32_t dims[4];         /* 128, 256, 512, 1024 (multiples of 64, at most 1024; head_dim 32)               */
+    int32_t depths[4];       /* 2, 2, 18, 2                                                                    */
+    int32_t heads[4];        /* 4, 8, 16, 32: dims[i] = 32 heads[i]                                            */
+    int32_t mlp_ratio;       /* 4: fc1 width = mlp_ratio * dims[i]                                             */
+    int32_t num_classes;     /* 10861                                                                          */
+    float   ln_eps;          /* 1e-5 (nn.LayerNorm's default)                                                  */
+    int32_t gelu_tanh;       /* 0: erf GELU (timm's nn.GELU), 1: tanh form                                     */
+    int32_t cpb_pretrained_window; /* 0: the position-bias table is normalised by the window, else by this size (timm pretrained_window_size) */
+    float   norm_mean[3];    /* the uint8 entry point's Normalize, RGB order: 0.5, 0.5, 0.5                    */
+    float   norm_std[3];     /* 0.5, 0.5, 0.5                                                                  */
+    int32_t max_batch;       /* workspace is sized for this many images per forward call                       */
+    int32_t operand_f16;     /* 0: bf16, 1: IEEE half MFMA operands                                            */
+} hipts_swinv2_config_t;
+
+int hipts_swinv2_create(const hipts_swinv2_config_t* cfg, int device, hipts_swinv2_t** out);
+int hipts_swinv2_destroy(hipts_swinv2_t* h);
+/* timm SwinTransformerV2 state_dict keys (timm >= 0.9 layout), host float32 in the timm layout: "patch_embed.proj.weight",
+ * "layers.1.downsample.reduction.weight", "layers.2.blocks.3.attn.qkv.weight", "layers.2.blocks.3.attn.q_bias",
+ * "layers.2.blocks.3.attn.logit_scale", "layers.2.blocks.3.attn.cpb_mlp.0.weight", "layers.2.blocks.3.norm1.weight", "norm.bias",
+ * "head.fc.weight", ...  Element counts are checked.  A forward before every key is set fails with HIPTS_ERR_STATE and names the
+ * first missing key.  The position-bias tables are computed from the cpb_mlp weights at the first forward after they change. */
+int hipts_swinv2_set_tensor(hipts_swinv2_t* h, const char* key, const float* data, int64_t numel);
+/* same contracts as hipts_convnext_forward_u8 / _f32: images uint8 [batch][S][S][3] RGB (the kernel applies /255, norm_mean /
+ * norm_std and the BGR order); x float32 [batch][3][S][S], already normalised, BGR. */
+int hipts_swinv2_forward_u8(hipts_swinv2_t* h, const uint8_t* images, int images_memspace, int batch, float* logits_out,
+                            float* probs_out, int out_memspace, void* stream);
+int hipts_swinv2_forward_f32(hipts_swinv2_t* h, const float* x, int x_memspace, int batch, float* logits_out, float* probs_out,
+                             int out_memspace, void* stream);
+int hipts_swinv2_flops_per_image(const hipts_swinv2_t* h, double* flops);
 
 /* ------------------------------------------------------------------------------------------
  * CCIP feature encoder.   Replaces the onnxruntime session of gen_cfeatures.py:112-118 and its

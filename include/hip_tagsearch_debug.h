@@ -38,6 +38,15 @@ int hiptsdbg_dwconv7_stamps(unsigned long long* host, int n);
 /* The ConvNeXt forward's float32 residual stream [batch][H*H][dims[stage]] after the last block of `stage` (0..3), from host
  * float32 input in the layout of hipts_convnext_forward_f32: places a parity failure in the network. */
 int hiptsdbg_convnext_stream(hipts_convnext_t* h, const float* x_host, int batch, int stage, float* out_host);
+/* The SwinV2 forward's float32 residual stream [batch][H*H][dims[stage]] after the last block of `stage` (0..3), from host float32
+ * input in the layout of hipts_swinv2_forward_f32. */
+int hiptsdbg_swinv2_stream(hipts_swinv2_t* h, const float* x_host, int batch, int stage, float* out_host);
+/* SwinV2 window attention on its own (csrc/swin_attn.hip).  Host float32 q, k, v [batch][side*side][heads*32] in raster order (q, k
+ * as they leave the qkv Linear, before F.normalize), logit_scale [heads] (before the clamp at ln 100), cpb [heads][(2w-1)^2] (the
+ * table 16 sigmoid(cpb_mlp(.)), indexed (dy + w - 1) (2w - 1) + dx + w - 1 for query minus key offsets); the windows are shifted
+ * by `shift` (0: none).  out: float32 [batch][side*side][heads*32], the kernel's 16-bit output widened. */
+int hiptsdbg_swinv2_window_attention(const float* q, const float* k, const float* v, const float* logit_scale, const float* cpb, int batch,
+                                     int heads, int side, int window, int shift, int operand_f16, float* out);
 /* The fused MLP of the CCIP encoder's stages 0-1 on its own (csrc/mlp.hip): x[m] = rs * x[m] + StarReLU(xn[m] W1^T) W2^T, xn_out[m] = LayerNorm(x[m]) * gamma.
  * Host arrays: xn / xn_out IEEE-half bits [M][C], w1 [4C][C], w2 [C][4C], x [M][C] in / out, res_scale / gamma [C] or null; C = 128 or 256;
  * ms_out: average device time of iters - 1 launches (iters >= 2); waves: 4 / 8 waves per workgroup, 0 = chosen by the size of the launch. */
