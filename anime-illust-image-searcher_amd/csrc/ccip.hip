@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "vit_internal.h"
+#include "model_host.h"
 #include "convnet.h"
 
 using namespace hipts;
@@ -63,7 +64,7 @@ struct hipts_ccip {
     hipts_ccip_config_t cfg{};
     Stage st[4];
     DevBuf stem_w, stem_b, stem_norm, head_g, head_b, zeros, lut;
-    std::vector<std::string> missing;
+    TensorLedger ledger;
     // workspace (sized for cfg.max_batch)
     DevBuf img_in, a0, x, xn, h1, h2, m1, col, q, k, vT, feat;
     DevBuf stat_part, fold_c;      // folded LayerNorms of the wide stages: per (256-column tile, row) partial (sum, sum of squares); scratch for W beta (unused: no beta)
@@ -71,8 +72,7 @@ struct hipts_ccip {
     bool fold_dirty = true;        // a norm / qkv / fc1 tensor changed since the fold vectors were computed
     size_t px = 0, p2c = 0, p4c = 0, pcol = 0, pqk = 0;   // per-image element strides of the workspace buffers (largest stage)
     static constexpr int MAX_SUB = 4;
-    hipStream_t sub[MAX_SUB] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[MAX_SUB] = {};
+    SubStreams<MAX_SUB> streams;
     double flops_per_image = 0.0;
 };
 
@@ -285,11 +285,6 @@ __global__ __launch_bounds__(256) void ds_im2col_kernel(const bf16_t* __restrict
 }
 
 
-int upload_f32(DevBuf& buf, const float* data, size_t n) {
-    HIPTS_TRY(buf.alloc(n * 4));
-    return upload(buf.p, data, n * 4);
-}
-
 // y = act(A W^T) helpers over the shared persistent GEMM
 int gemm(GemmEpilogue epi, GemmArgs& g, hipStream_t s) { return launch_gemm(epi, g, s); }
 
@@ -336,9 +331,7 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
     bool xblk = false;          // layout of x right now (the stage being processed)
     auto layernorm_xn = [&](const float* gamma, int64_t rows, int D) -> int {
         if (xblk) {
-            if (f16) layernorm_blk_kernel<true><<<ceil_div(rows, 4), 256, 0, s>>>(x, gamma, xn, rows, D, c.ln_eps);
-            else layernorm_blk_kernel<false><<<ceil_div(rows, 4), 256, 0, s>>>(x, gamma, xn, rows, D, c.ln_eps);
-            HIPTS_LAUNCH_CHECK();
+            HIPTS_LAUNCH_F16(f16, layernorm_blk_kernel, ceil_div(rows, 4), 256, 0, s, x, gamma, xn, rows, D, c.ln_eps);
             return HIPTS_OK;
         }
         return launch_layernorm(x, gamma, nullptr, xn, rows, D, c.ln_eps, f16, s);
@@ -458,9 +451,7 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
                 const int tiles_x = ceil_div(H, DW_TW), tiles_y = ceil_div(H, DW_TH);
                 const int dw_grid = batch * tiles_y * tiles_x * (2 * C / DW_CS);
                 if (f16 && H >= 16 && dw_mfma && B.dwz.p) HIPTS_TRY(launch_dwconv7_mfma(h1, B.dwz.as<uint32_t>(), h2, batch, H, 2 * C, dw_mfma, s));
-                else if (f16) dwconv7_kernel<true><<<dw_grid, 256, DW_LDS_BYTES, s>>>(h1, B.dw.as<float>(), h2, H, 2 * C, tiles_x, tiles_y);
-                else dwconv7_kernel<false><<<dw_grid, 256, DW_LDS_BYTES, s>>>(h1, B.dw.as<float>(), h2, H, 2 * C, tiles_x, tiles_y);
-                HIPTS_LAUNCH_CHECK();
+                else HIPTS_LAUNCH_F16(f16, dwconv7_kernel, dw_grid, 256, DW_LDS_BYTES, s, h1, B.dw.as<float>(), h2, H, 2 * C, tiles_x, tiles_y);
                 g = GemmArgs{};
                 g.f16 = f16;
                 g.shared_chip = shared_chip;
@@ -536,19 +527,12 @@ int ccip_forward_impl(hipts_ccip* h, const void* input, int in_memspace, bool is
                       hipStream_t s) {
     HIPTS_REQUIRE(h && input && out && batch >= 1, "hipts_ccip_forward: bad arguments");
     HIPTS_REQUIRE(batch <= h->cfg.max_batch, "batch %d exceeds max_batch %d", batch, h->cfg.max_batch);
-    if (!h->missing.empty())
-        return set_error(HIPTS_ERR_STATE, "hipts_ccip_forward: %zu checkpoint tensors not set (first: %s)", h->missing.size(),
-                         h->missing[0].c_str());
+    HIPTS_TRY(h->ledger.require_complete("hipts_ccip_forward"));
     HIPTS_TRY(use_device(h->device));
     const auto& c = h->cfg;
     const int S = c.image_size;
-    const void* in_dev = input;
-    if (in_memspace != HIPTS_DEVICE) {
-        const size_t bytes = (size_t)batch * S * S * 3 * (is_u8 ? 1 : 4);
-        HIPTS_TRY(h->img_in.reserve(bytes));
-        HIPTS_HIP(hipMemcpyAsync(h->img_in.p, input, bytes, hipMemcpyHostToDevice, s));
-        in_dev = h->img_in.p;
-    }
+    const void* in_dev = nullptr;
+    HIPTS_TRY(stage_input(h->img_in, input, in_memspace, (size_t)batch * S * S * 3 * (is_u8 ? 1 : 4), s, &in_dev));
     const bool dev_out = out_memspace == HIPTS_DEVICE;
     float* f_dev = dev_out ? out : h->feat.as<float>();
     if (h->fold_dirty) {        // W gamma of the wide stages' q | k, v and fc1 (folded LayerNorms): once per checkpoint
@@ -578,30 +562,10 @@ int ccip_forward_impl(hipts_ccip* h, const void* input, int in_memspace, bool is
     // to gain and the doubled launch count costs, so small batches stay on the caller's stream)
     static const int min_sub = getenv("HIPTS_CCIP_MINSUB") && atoi(getenv("HIPTS_CCIP_MINSUB")) > 0 ? atoi(getenv("HIPTS_CCIP_MINSUB")) : 16;      // images per sub-batch needed to split
     const int ns = std::min({want_streams, (int)hipts_ccip::MAX_SUB, batch / min_sub});      // (round 5, HIPTS_CCIP_STREAMS = 2 / 3 / 4 at batch 64: 3608 / 3458 / 2844 images/s -- two it stays)
-    if (ns >= 2) {
-        if (!h->ev_fork) {
-            HIPTS_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            for (int i = 0; i < hipts_ccip::MAX_SUB; ++i) {
-                HIPTS_HIP(hipStreamCreateWithFlags(&h->sub[i], hipStreamNonBlocking));
-                HIPTS_HIP(hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
-            }
-        }
-        HIPTS_HIP(hipEventRecord(h->ev_fork, s));
-        for (int i = 0; i < ns; ++i) {
-            const int i0 = (int)((int64_t)batch * i / ns), i1 = (int)((int64_t)batch * (i + 1) / ns);      // (two streams: the halves as before, the larger one first)
-            const int a0 = ns == 2 ? (i ? (batch + 1) / 2 : 0) : i0, a1 = ns == 2 ? (i ? batch : (batch + 1) / 2) : i1;
-            HIPTS_HIP(hipStreamWaitEvent(h->sub[i], h->ev_fork, 0));
-            HIPTS_TRY(ccip_run_images(h, in_dev, is_u8, a0, a1 - a0, f_dev, h->sub[i], true));
-            HIPTS_HIP(hipEventRecord(h->ev_join[i], h->sub[i]));
-            HIPTS_HIP(hipStreamWaitEvent(s, h->ev_join[i], 0));
-        }
-    } else {
-        HIPTS_TRY(ccip_run_images(h, in_dev, is_u8, 0, batch, f_dev, s, false));
-    }
-    if (!dev_out) {
-        HIPTS_HIP(hipMemcpyAsync(out, f_dev, (size_t)batch * h->st[3].C * 4, hipMemcpyDeviceToHost, s));
-        HIPTS_HIP(hipStreamSynchronize(s));
-    }
+    HIPTS_TRY(run_split(h->streams, s, batch, ns, [&](int i0, int nb, hipStream_t st, bool shared_chip, int) {
+        return ccip_run_images(h, in_dev, is_u8, i0, nb, f_dev, st, shared_chip);
+    }));
+    if (!dev_out) HIPTS_TRY(read_back(s, (size_t)batch * h->st[3].C * 4, out, f_dev));      // a single output: the pooled features
     return HIPTS_OK;
 }
 
@@ -664,12 +628,8 @@ int hipts_ccip_create(const hipts_ccip_config_t* cfg, int device, hipts_ccip_t**
     h->flops_per_image = flops;
     int st = 0;
     std::vector<float> z(4096, 0.f);
-    std::vector<float> lut(3 * 256);
-    {
-        const double mean[3] = {0.48145466, 0.4578275, 0.40821073}, stdv[3] = {0.26862954, 0.26130258, 0.27577711};   // gen_cfeatures.py:103-104
-        for (int cc = 0; cc < 3; ++cc)
-            for (int u = 0; u < 256; ++u) lut[cc * 256 + u] = (float)(((double)((float)u / 255.0f) - mean[cc]) / stdv[cc]);
-    }
+    const double mean[3] = {0.48145466, 0.4578275, 0.40821073}, stdv[3] = {0.26862954, 0.26130258, 0.27577711};   // gen_cfeatures.py:103-104
+    const std::vector<float> lut = norm_lut(mean, stdv);      // (x - mean) / std in float64, as the reference's numpy does
     if ((st = upload_f32(h->zeros, z.data(), z.size())) || (st = upload_f32(h->lut, lut.data(), lut.size())) || (st = h->a0.alloc((size_t)B * h->st[0].T * STEM_K * 2)) ||
         (st = h->x.alloc(max_x * 4)) || (st = h->xn.alloc(max_x * 2)) || (st = h->h1.alloc(max_2c * 2)) || (st = h->h2.alloc(max_2c * 2)) ||
         (st = h->m1.alloc(max_4c * 2)) || (st = h->col.alloc(max_col * 2)) || (st = h->q.alloc(max_qk * 2)) || (st = h->k.alloc(max_qk * 2)) ||
@@ -693,7 +653,7 @@ int hipts_ccip_create(const hipts_ccip_config_t* cfg, int device, hipts_ccip_t**
         delete h;
         return set_error(HIPTS_ERR_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     }
-    auto need = [&](const std::string& k) { h->missing.push_back(k); };
+    auto need = [&](const std::string& k) { h->ledger.need(k); };
     need("stem.conv.weight"); need("stem.conv.bias"); need("stem.norm.weight"); need("head.norm.weight"); need("head.norm.bias");
     for (int s = 0; s < 4; ++s) {
         const std::string sp = "stages." + std::to_string(s) + ".";
@@ -717,11 +677,6 @@ int hipts_ccip_destroy(hipts_ccip_t* h) {
     if (h) {
         (void)hipSetDevice(h->device);
         (void)hipDeviceSynchronize();
-        for (int i = 0; i < hipts_ccip::MAX_SUB; ++i) {
-            if (h->sub[i]) (void)hipStreamDestroy(h->sub[i]);
-            if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]);
-        }
-        if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
         delete h;
     }
     return HIPTS_OK;
@@ -733,62 +688,44 @@ int hipts_ccip_set_tensor(hipts_ccip_t* h, const char* key_c, const float* data,
     const std::string key(key_c);
     const bool f16 = h->cfg.operand_f16 != 0;
     int st = HIPTS_OK;
-#define EXPECT(n)                                                                                                         \
-    do {                                                                                                                  \
-        if (numel != (int64_t)(n)) return set_error(HIPTS_ERR_INVALID, "tensor %s: %lld elements, expected %lld", key_c, (long long)numel, (long long)(n)); \
-    } while (0)
     const int C0 = h->cfg.dims[0], C3 = h->cfg.dims[3];
+    int s = 0, bi = 0;
+    std::string sub, t;
     if (key == "stem.conv.weight") {
-        EXPECT((int64_t)C0 * 147);
-        // [n][c][ky][kx] -> [n][(ky*7 + kx)*3 + c], duplicated for the hi | lo halves of the patch matrix
-        std::vector<float> w2((size_t)C0 * STEM_K, 0.f);
-        for (int n = 0; n < C0; ++n)
-            for (int c = 0; c < 3; ++c)
-                for (int t = 0; t < 49; ++t) {
-                    const float v = data[((size_t)n * 3 + c) * 49 + t];
-                    w2[(size_t)n * STEM_K + t * 3 + c] = v;
-                    w2[(size_t)n * STEM_K + STEM_KH + t * 3 + c] = v;
-                }
+        EXPECT_NUMEL((int64_t)C0 * 147);
+        const std::vector<float> w2 = stem_weight_hilo(data, C0, 49, STEM_KH, false);      // the hi | lo halves of the stem patch matrix
         st = upload_matrix16(h->stem_w, w2.data(), C0, STEM_K, round_up(C0, 256), f16);
-    } else if (key == "stem.conv.bias") { EXPECT(C0); st = upload_f32(h->stem_b, data, C0); }
-    else if (key == "stem.norm.weight") { EXPECT(C0); st = upload_f32(h->stem_norm, data, C0); }
-    else if (key == "head.norm.weight") { EXPECT(C3); st = upload_f32(h->head_g, data, C3); }
-    else if (key == "head.norm.bias") { EXPECT(C3); st = upload_f32(h->head_b, data, C3); }
-    else if (key.rfind("stages.", 0) == 0) {
-        const size_t d1 = key.find('.', 7);
-        if (d1 == std::string::npos) return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-        const int s = atoi(key.substr(7, d1 - 7).c_str());
+    } else if (key == "stem.conv.bias") { EXPECT_NUMEL(C0); st = upload_f32(h->stem_b, data, C0); }
+    else if (key == "stem.norm.weight") { EXPECT_NUMEL(C0); st = upload_f32(h->stem_norm, data, C0); }
+    else if (key == "head.norm.weight") { EXPECT_NUMEL(C3); st = upload_f32(h->head_g, data, C3); }
+    else if (key == "head.norm.bias") { EXPECT_NUMEL(C3); st = upload_f32(h->head_b, data, C3); }
+    else if (parse_indexed(key, "stages.", &s, &sub)) {
         if (s < 0 || s > 3) return set_error(HIPTS_ERR_INVALID, "tensor %s: stage out of range", key_c);
         Stage& St = h->st[s];
         const int C = St.C;
-        std::string sub = key.substr(d1 + 1);
         if (sub.rfind("downsample.", 0) == 0) {
             if (s == 0) return set_error(HIPTS_ERR_INVALID, "tensor %s: stage 0 has no downsample", key_c);
             const int Cp = h->cfg.dims[s - 1];
-            if (sub == "downsample.norm.weight") { EXPECT(Cp); st = upload_f32(St.ds_norm, data, Cp); }
-            else if (sub == "downsample.conv.bias") { EXPECT(C); st = upload_f32(St.ds_b, data, C); }
+            if (sub == "downsample.norm.weight") { EXPECT_NUMEL(Cp); st = upload_f32(St.ds_norm, data, Cp); }
+            else if (sub == "downsample.conv.bias") { EXPECT_NUMEL(C); st = upload_f32(St.ds_b, data, C); }
             else if (sub == "downsample.conv.weight") {
-                EXPECT((int64_t)C * Cp * 9);
+                EXPECT_NUMEL((int64_t)C * Cp * 9);
                 std::vector<float> w2((size_t)C * 9 * Cp);          // [n][c][tap] -> [n][tap*Cp + c]
                 for (int n = 0; n < C; ++n)
                     for (int cc = 0; cc < Cp; ++cc)
                         for (int t = 0; t < 9; ++t) w2[((size_t)n * 9 + t) * Cp + cc] = data[((size_t)n * Cp + cc) * 9 + t];
                 st = upload_matrix16(St.ds_w, w2.data(), C, 9 * Cp, round_up(C, 256), f16);
             } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-        } else if (sub.rfind("blocks.", 0) == 0) {
-            const size_t d2 = sub.find('.', 7);
-            if (d2 == std::string::npos) return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-            const int bi = atoi(sub.substr(7, d2 - 7).c_str());
+        } else if (parse_indexed(sub, "blocks.", &bi, &t)) {
             if (bi < 0 || bi >= (int)St.blocks.size()) return set_error(HIPTS_ERR_INVALID, "tensor %s: block out of range", key_c);
             Block& B = St.blocks[bi];
-            const std::string t = sub.substr(d2 + 1);
             auto up = [&](DevBuf& buf, int rows, int cols, int rows_pad) -> int { return upload_matrix16(buf, data, rows, cols, rows_pad, f16); };
-            if (t == "norm1.weight") { EXPECT(C); st = upload_f32(B.n1, data, C); }
-            else if (t == "norm2.weight") { EXPECT(C); st = upload_f32(B.n2, data, C); }
-            else if (t == "res_scale1.scale") { EXPECT(C); st = upload_f32(B.rs1, data, C); B.has_rs1 = true; }
-            else if (t == "res_scale2.scale") { EXPECT(C); st = upload_f32(B.rs2, data, C); B.has_rs2 = true; }
+            if (t == "norm1.weight") { EXPECT_NUMEL(C); st = upload_f32(B.n1, data, C); }
+            else if (t == "norm2.weight") { EXPECT_NUMEL(C); st = upload_f32(B.n2, data, C); }
+            else if (t == "res_scale1.scale") { EXPECT_NUMEL(C); st = upload_f32(B.rs1, data, C); B.has_rs1 = true; }
+            else if (t == "res_scale2.scale") { EXPECT_NUMEL(C); st = upload_f32(B.rs2, data, C); B.has_rs2 = true; }
             else if (t == "mlp.fc1.weight" || t == "mlp.fc2.weight") {
-                EXPECT((int64_t)4 * C * C);
+                EXPECT_NUMEL((int64_t)4 * C * C);
                 const bool first = t == "mlp.fc1.weight";
                 st = first ? up(B.fc1, 4 * C, C, round_up(4 * C, 256)) : up(B.fc2, C, 4 * C, round_up(C, 256));
                 if (st == HIPTS_OK && f16 && mlp_fused_supports(C)) {
@@ -800,14 +737,14 @@ int hipts_ccip_set_tensor(hipts_ccip_t* h, const char* key_c, const float* data,
                     }
                 }
             }
-            else if (t == "mlp.act.scale") { EXPECT(1); B.s2 = data[0]; }
-            else if (t == "mlp.act.bias") { EXPECT(1); B.b2 = data[0]; }
-            else if (!B.attn && t == "token_mixer.pwconv1.weight") { EXPECT((int64_t)2 * C * C); st = upload_matrix16(B.w_in, data, 2 * C, C, round_up(2 * C, 256), f16); }
-            else if (!B.attn && t == "token_mixer.pwconv2.weight") { EXPECT((int64_t)2 * C * C); st = up(B.w_out, C, 2 * C, round_up(C, 256)); }
-            else if (!B.attn && t == "token_mixer.act1.scale") { EXPECT(1); B.s1 = data[0]; }
-            else if (!B.attn && t == "token_mixer.act1.bias") { EXPECT(1); B.b1 = data[0]; }
+            else if (t == "mlp.act.scale") { EXPECT_NUMEL(1); B.s2 = data[0]; }
+            else if (t == "mlp.act.bias") { EXPECT_NUMEL(1); B.b2 = data[0]; }
+            else if (!B.attn && t == "token_mixer.pwconv1.weight") { EXPECT_NUMEL((int64_t)2 * C * C); st = upload_matrix16(B.w_in, data, 2 * C, C, round_up(2 * C, 256), f16); }
+            else if (!B.attn && t == "token_mixer.pwconv2.weight") { EXPECT_NUMEL((int64_t)2 * C * C); st = up(B.w_out, C, 2 * C, round_up(C, 256)); }
+            else if (!B.attn && t == "token_mixer.act1.scale") { EXPECT_NUMEL(1); B.s1 = data[0]; }
+            else if (!B.attn && t == "token_mixer.act1.bias") { EXPECT_NUMEL(1); B.b1 = data[0]; }
             else if (!B.attn && t == "token_mixer.dwconv.weight") {
-                EXPECT((int64_t)2 * C * 49);
+                EXPECT_NUMEL((int64_t)2 * C * 49);
                 std::vector<float> w2((size_t)49 * 2 * C);          // [c][tap] -> [tap][c]
                 for (int cc = 0; cc < 2 * C; ++cc)
                     for (int tp = 0; tp < 49; ++tp) w2[(size_t)tp * 2 * C + cc] = data[(size_t)cc * 49 + tp];
@@ -818,20 +755,18 @@ int hipts_ccip_set_tensor(hipts_ccip_t* h, const char* key_c, const float* data,
                 }
             }
             else if (B.attn && t == "token_mixer.qkv.weight") {
-                EXPECT((int64_t)3 * C * C);
+                EXPECT_NUMEL((int64_t)3 * C * C);
                 // q|k rows and the v rows are read by separate launches whose last tile may run past its
                 // own rows: pad behind the v rows as well
                 st = upload_matrix16(B.w_in, data, 3 * C, C, round_up(2 * C, 256) + round_up(C, 256) + 256, f16);
             }
-            else if (B.attn && t == "token_mixer.proj.weight") { EXPECT((int64_t)C * C); st = upload_matrix16(B.w_out, data, C, C, round_up(C, 256), f16); }
+            else if (B.attn && t == "token_mixer.proj.weight") { EXPECT_NUMEL((int64_t)C * C); st = upload_matrix16(B.w_out, data, C, C, round_up(C, 256), f16); }
             else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
         } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
     } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-#undef EXPECT
     if (st) return st;
     h->fold_dirty = true;
-    auto it = std::find(h->missing.begin(), h->missing.end(), key);
-    if (it != h->missing.end()) h->missing.erase(it);
+    h->ledger.mark_set(key);
     return HIPTS_OK;
 }
 

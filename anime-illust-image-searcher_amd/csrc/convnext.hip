@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "vit_internal.h"
+#include "model_host.h"
 #include "convnet.h"
 
 using namespace hipts;
@@ -55,13 +56,11 @@ struct hipts_convnext {
     hipts_convnext_config_t cfg{};
     CnxStage st[4];
     DevBuf stem_w, stem_b, stem_nw, stem_nb, head_nw, head_nb, head_w, head_b, lut;
-    std::vector<std::string> missing;
+    TensorLedger ledger;
     // workspace (sized for cfg.max_batch), carved per image with the stride of the largest stage
     DevBuf img_in, a0, x, xh, dwo, xn, m1, col, feat, feat2, logits, probs;
     size_t px = 0, p4c = 0, pcol = 0;
-    static constexpr int NSUB = 2;
-    hipStream_t sub[NSUB] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[NSUB] = {};
+    SubStreams<2> streams;
     double flops_per_image = 0.0;
 };
 
@@ -144,12 +143,6 @@ __global__ __launch_bounds__(256) void cnx_dwln_kernel(const bf16_t* __restrict_
     }
 }
 
-
-int cnx_upload_f32(DevBuf& buf, const float* data, size_t n) {
-    HIPTS_TRY(buf.alloc(n * 4));
-    return upload(buf.p, data, n * 4);
-}
-
 // The kernel sequence for images [i0, i0 + batch) on stream s.  stop_stage >= 0 (debug entry): return after that stage's last block,
 // x holding its residual stream.
 int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, int batch, float* lg, float* pr, hipStream_t s, bool shared_chip,
@@ -190,9 +183,7 @@ int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, in
         g.A = a0; g.W = h->stem_w.as<bf16_t>(); g.M = (int)M; g.N = S0.C; g.K = CNX_STEM_K;
         g.bias = h->stem_b.as<float>(); g.out_f32 = x;
         HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
-        if (f16) cnx_ln_kernel<true><<<ceil_div(M, 4), 256, 0, s>>>(x, h->stem_nw.as<float>(), h->stem_nb.as<float>(), xh, M, S0.C, c.ln_eps);
-        else cnx_ln_kernel<false><<<ceil_div(M, 4), 256, 0, s>>>(x, h->stem_nw.as<float>(), h->stem_nb.as<float>(), xh, M, S0.C, c.ln_eps);
-        HIPTS_LAUNCH_CHECK();
+        HIPTS_LAUNCH_F16(f16, cnx_ln_kernel, ceil_div(M, 4), 256, 0, s, x, h->stem_nw.as<float>(), h->stem_nb.as<float>(), xh, M, S0.C, c.ln_eps);
     }
 
     for (int si = 0; si < 4; ++si) {
@@ -203,17 +194,13 @@ int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, in
             // downsample: LN(x) gathered into 2x2 s2 patches -> GEMM (+bias) -> x, then its 16-bit copy
             const CnxStage& Pv = h->st[si - 1];
             const int64_t rows_in = (int64_t)batch * Pv.T;
-            if (f16) cnx_ds_kernel<true><<<ceil_div(rows_in, 4), 256, 0, s>>>(x, St.ds_nw.as<float>(), St.ds_nb.as<float>(), col, rows_in, Pv.H, Pv.C, c.ln_eps);
-            else cnx_ds_kernel<false><<<ceil_div(rows_in, 4), 256, 0, s>>>(x, St.ds_nw.as<float>(), St.ds_nb.as<float>(), col, rows_in, Pv.H, Pv.C, c.ln_eps);
-            HIPTS_LAUNCH_CHECK();
+            HIPTS_LAUNCH_F16(f16, cnx_ds_kernel, ceil_div(rows_in, 4), 256, 0, s, x, St.ds_nw.as<float>(), St.ds_nb.as<float>(), col, rows_in, Pv.H, Pv.C, c.ln_eps);
             GemmArgs g = gemm_args();
             g.A = col; g.W = St.ds_w.as<bf16_t>(); g.M = M; g.N = C; g.K = 4 * Pv.C;
             g.bias = St.ds_b.as<float>(); g.out_f32 = x;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
             const int64_t n4 = (int64_t)M * C / 4;
-            if (f16) cnx_cast_kernel<true><<<ceil_div(n4, 256), 256, 0, s>>>(x, xh, n4);
-            else cnx_cast_kernel<false><<<ceil_div(n4, 256), 256, 0, s>>>(x, xh, n4);
-            HIPTS_LAUNCH_CHECK();
+            HIPTS_LAUNCH_F16(f16, cnx_cast_kernel, ceil_div(n4, 256), 256, 0, s, x, xh, n4);
         }
         for (CnxBlock& B : St.blocks) {
             // depthwise 7x7 (no bias) of the 16-bit copy of x
@@ -222,14 +209,10 @@ int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, in
             } else {
                 const int tiles_x = ceil_div(H, DW_TW), tiles_y = ceil_div(H, DW_TH);
                 const int dw_grid = batch * tiles_y * tiles_x * (C / DW_CS);
-                if (f16) dwconv7_kernel<true><<<dw_grid, 256, DW_LDS_BYTES, s>>>(xh, B.dw.as<float>(), dwo, H, C, tiles_x, tiles_y);
-                else dwconv7_kernel<false><<<dw_grid, 256, DW_LDS_BYTES, s>>>(xh, B.dw.as<float>(), dwo, H, C, tiles_x, tiles_y);
-                HIPTS_LAUNCH_CHECK();
+                HIPTS_LAUNCH_F16(f16, dwconv7_kernel, dw_grid, 256, DW_LDS_BYTES, s, xh, B.dw.as<float>(), dwo, H, C, tiles_x, tiles_y);
             }
             // + depthwise bias -> LayerNorm (weight, bias) -> the 16-bit operand of fc1
-            if (f16) cnx_dwln_kernel<true><<<ceil_div(M, 4), 256, 0, s>>>(dwo, B.dw_b.as<float>(), B.n_w.as<float>(), B.n_b.as<float>(), xn, M, C, c.ln_eps);
-            else cnx_dwln_kernel<false><<<ceil_div(M, 4), 256, 0, s>>>(dwo, B.dw_b.as<float>(), B.n_w.as<float>(), B.n_b.as<float>(), xn, M, C, c.ln_eps);
-            HIPTS_LAUNCH_CHECK();
+            HIPTS_LAUNCH_F16(f16, cnx_dwln_kernel, ceil_div(M, 4), 256, 0, s, dwo, B.dw_b.as<float>(), B.n_w.as<float>(), B.n_b.as<float>(), xn, M, C, c.ln_eps);
             GemmArgs g = gemm_args();
             g.A = xn; g.W = B.fc1.as<bf16_t>(); g.M = M; g.N = 4 * C; g.K = C; g.bias = B.fc1_b.as<float>();
             g.out_bf16 = m1; g.gelu_tanh = 0;
@@ -247,9 +230,7 @@ int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, in
     bf16_t* feat2 = h->feat2.as<bf16_t>() + (size_t)i0 * 2 * L.C;
     pool_ln_kernel<<<batch, 1024, 0, s>>>(x, h->head_nw.as<float>(), h->head_nb.as<float>(), feat, L.T, L.C, c.ln_eps, 0);
     HIPTS_LAUNCH_CHECK();
-    if (f16) cnx_split_kernel<true><<<ceil_div((int64_t)batch * L.C, 256), 256, 0, s>>>(feat, feat2, batch, L.C);
-    else cnx_split_kernel<false><<<ceil_div((int64_t)batch * L.C, 256), 256, 0, s>>>(feat, feat2, batch, L.C);
-    HIPTS_LAUNCH_CHECK();
+    HIPTS_LAUNCH_F16(f16, cnx_split_kernel, ceil_div((int64_t)batch * L.C, 256), 256, 0, s, feat, feat2, batch, L.C);
     GemmArgs g = gemm_args();
     g.A = feat2; g.W = h->head_w.as<bf16_t>(); g.M = batch; g.N = c.num_classes; g.K = 2 * L.C;
     g.bias = h->head_b.as<float>(); g.out_f32 = lg ? lg + (size_t)i0 * c.num_classes : nullptr;
@@ -262,50 +243,25 @@ int cnx_forward_impl(hipts_convnext* h, const void* input, int in_memspace, bool
                      int out_memspace, hipStream_t s, int stop_stage = -1) {
     HIPTS_REQUIRE(h && input && batch >= 1, "hipts_convnext_forward: bad arguments");
     HIPTS_REQUIRE(batch <= h->cfg.max_batch, "batch %d exceeds max_batch %d", batch, h->cfg.max_batch);
-    if (!h->missing.empty())
-        return set_error(HIPTS_ERR_STATE, "hipts_convnext_forward: %zu checkpoint tensors not set (first: %s)", h->missing.size(),
-                         h->missing[0].c_str());
+    HIPTS_TRY(h->ledger.require_complete("hipts_convnext_forward"));
     HIPTS_TRY(use_device(h->device));
     const auto& c = h->cfg;
     const int S = c.image_size, NC = c.num_classes;
-    const void* in_dev = input;
-    if (in_memspace != HIPTS_DEVICE) {
-        const size_t bytes = (size_t)batch * S * S * 3 * (is_u8 ? 1 : 4);
-        HIPTS_TRY(h->img_in.reserve(bytes));
-        HIPTS_HIP(hipMemcpyAsync(h->img_in.p, input, bytes, hipMemcpyHostToDevice, s));
-        in_dev = h->img_in.p;
-    }
+    const void* in_dev = nullptr;
+    HIPTS_TRY(stage_input(h->img_in, input, in_memspace, (size_t)batch * S * S * 3 * (is_u8 ? 1 : 4), s, &in_dev));
     const bool dev_out = out_memspace == HIPTS_DEVICE;
+    // deliberate: an output the caller does not ask for stays null and EPI_HEAD skips it (the ViT / EVA02 forwards always compute logits)
     float* lg = dev_out ? logits_out : (logits_out ? h->logits.as<float>() : nullptr);
     float* pr = dev_out ? probs_out : (probs_out ? h->probs.as<float>() : nullptr);
     // Two sub-batches on two internal streams from 32 images on (as the CCIP and ViT forwards): the late stages have fewer output
     // tiles than the chip has CUs, and a kernel of one half fills the CUs the other half leaves idle.  The split changes which images
     // share a launch, never an image's arithmetic.
-    const int ns = (stop_stage < 0 && batch >= 32) ? hipts_convnext::NSUB : 1;
-    if (ns >= 2) {
-        if (!h->ev_fork) {
-            HIPTS_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            for (int i = 0; i < hipts_convnext::NSUB; ++i) {
-                HIPTS_HIP(hipStreamCreateWithFlags(&h->sub[i], hipStreamNonBlocking));
-                HIPTS_HIP(hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
-            }
-        }
-        HIPTS_HIP(hipEventRecord(h->ev_fork, s));
-        for (int i = 0; i < ns; ++i) {
-            const int a0 = i ? (batch + 1) / 2 : 0, a1 = i ? batch : (batch + 1) / 2;
-            HIPTS_HIP(hipStreamWaitEvent(h->sub[i], h->ev_fork, 0));
-            HIPTS_TRY(cnx_run_images(h, in_dev, is_u8, a0, a1 - a0, lg, pr, h->sub[i], true, -1));
-            HIPTS_HIP(hipEventRecord(h->ev_join[i], h->sub[i]));
-            HIPTS_HIP(hipStreamWaitEvent(s, h->ev_join[i], 0));
-        }
-    } else {
-        HIPTS_TRY(cnx_run_images(h, in_dev, is_u8, 0, batch, lg, pr, s, false, stop_stage));
-    }
-    if (stop_stage < 0 && !dev_out) {
-        if (logits_out) HIPTS_HIP(hipMemcpyAsync(logits_out, lg, (size_t)batch * NC * 4, hipMemcpyDeviceToHost, s));
-        if (probs_out) HIPTS_HIP(hipMemcpyAsync(probs_out, pr, (size_t)batch * NC * 4, hipMemcpyDeviceToHost, s));
-        HIPTS_HIP(hipStreamSynchronize(s));
-    }
+    // The debug entry (stop_stage >= 0) never splits and reads nothing back: its caller copies the residual stream itself.
+    const int ns = (stop_stage < 0 && batch >= 32) ? 2 : 1;
+    HIPTS_TRY(run_split(h->streams, s, batch, ns, [&](int i0, int nb, hipStream_t st, bool shared_chip, int) {
+        return cnx_run_images(h, in_dev, is_u8, i0, nb, lg, pr, st, shared_chip, stop_stage);
+    }));
+    if (stop_stage < 0 && !dev_out) HIPTS_TRY(read_back(s, (size_t)batch * NC * 4, logits_out, lg, probs_out, pr));
     return HIPTS_OK;
 }
 
@@ -355,11 +311,9 @@ int hipts_convnext_create(const hipts_convnext_config_t* cfg, int device, hipts_
     flops += 2.0 * cfg->dims[3] * (double)cfg->num_classes;
     h->flops_per_image = flops;
     const int C3 = cfg->dims[3];
-    std::vector<float> lut(3 * 256);
-    for (int cc = 0; cc < 3; ++cc)
-        for (int u = 0; u < 256; ++u) lut[cc * 256 + u] = ((float)u / 255.0f - cfg->norm_mean[cc]) / cfg->norm_std[cc];      // ToTensor + Normalize, float32
+    const std::vector<float> lut = norm_lut(cfg->norm_mean, cfg->norm_std);
     int st = 0;
-    if ((st = cnx_upload_f32(h->lut, lut.data(), lut.size())) || (st = h->a0.alloc((size_t)B * h->st[0].T * CNX_STEM_K * 2)) ||
+    if ((st = upload_f32(h->lut, lut.data(), lut.size())) || (st = h->a0.alloc((size_t)B * h->st[0].T * CNX_STEM_K * 2)) ||
         (st = h->x.alloc((size_t)B * h->px * 4)) || (st = h->xh.alloc((size_t)B * h->px * 2)) || (st = h->dwo.alloc((size_t)B * h->px * 2)) ||
         (st = h->xn.alloc((size_t)B * h->px * 2)) || (st = h->m1.alloc((size_t)B * h->p4c * 2)) || (st = h->col.alloc((size_t)B * h->pcol * 2)) ||
         (st = h->feat.alloc((size_t)B * C3 * 4)) || (st = h->feat2.alloc((size_t)B * 2 * C3 * 2)) ||
@@ -373,7 +327,7 @@ int hipts_convnext_create(const hipts_convnext_config_t* cfg, int device, hipts_
         delete h;
         return set_error(HIPTS_ERR_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     }
-    auto need = [&](const std::string& k) { h->missing.push_back(k); };
+    auto need = [&](const std::string& k) { h->ledger.need(k); };
     need("stem.0.weight"); need("stem.0.bias"); need("stem.1.weight"); need("stem.1.bias");
     for (int s = 0; s < 4; ++s) {
         const std::string sp = "stages." + std::to_string(s) + ".";
@@ -396,11 +350,6 @@ int hipts_convnext_destroy(hipts_convnext_t* h) {
     if (h) {
         (void)hipSetDevice(h->device);
         (void)hipDeviceSynchronize();
-        for (int i = 0; i < hipts_convnext::NSUB; ++i) {
-            if (h->sub[i]) (void)hipStreamDestroy(h->sub[i]);
-            if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]);
-        }
-        if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
         delete h;
     }
     return HIPTS_OK;
@@ -413,90 +362,67 @@ int hipts_convnext_set_tensor(hipts_convnext_t* h, const char* key_c, const floa
     const auto& cf = h->cfg;
     const bool f16 = (cf.operand_f16 & 1) != 0;
     int st = HIPTS_OK;
-#define EXPECT(n)                                                                                                         \
-    do {                                                                                                                  \
-        if (numel != (int64_t)(n)) return set_error(HIPTS_ERR_INVALID, "tensor %s: %lld elements, expected %lld", key_c, (long long)numel, (long long)(n)); \
-    } while (0)
     const int C0 = cf.dims[0], C3 = cf.dims[3], NC = cf.num_classes;
+    int s = 0, bi = 0;
+    std::string sub, t;
     if (key == "stem.0.weight") {
-        EXPECT((int64_t)C0 * 48);
-        // [n][c_model][ky][kx] -> [n][(ky*4 + kx)*3 + c_mem], c_model = 2 - c_mem (BGR), duplicated for the hi | lo halves
-        std::vector<float> w2((size_t)C0 * CNX_STEM_K, 0.f);
-        for (int n = 0; n < C0; ++n)
-            for (int cm = 0; cm < 3; ++cm)
-                for (int t = 0; t < 16; ++t) {
-                    const float v = data[((size_t)n * 3 + (2 - cm)) * 16 + t];
-                    w2[(size_t)n * CNX_STEM_K + t * 3 + cm] = v;
-                    w2[(size_t)n * CNX_STEM_K + CNX_STEM_KH + t * 3 + cm] = v;
-                }
+        EXPECT_NUMEL((int64_t)C0 * 48);
+        const std::vector<float> w2 = stem_weight_hilo(data, C0, 16, CNX_STEM_KH, true);      // BGR; the hi | lo halves of cnx_stem_kernel
         st = upload_matrix16(h->stem_w, w2.data(), C0, CNX_STEM_K, round_up(C0, 256), f16);
-    } else if (key == "stem.0.bias") { EXPECT(C0); st = cnx_upload_f32(h->stem_b, data, C0); }
-    else if (key == "stem.1.weight") { EXPECT(C0); st = cnx_upload_f32(h->stem_nw, data, C0); }
-    else if (key == "stem.1.bias") { EXPECT(C0); st = cnx_upload_f32(h->stem_nb, data, C0); }
-    else if (key == "head.norm.weight") { EXPECT(C3); st = cnx_upload_f32(h->head_nw, data, C3); }
-    else if (key == "head.norm.bias") { EXPECT(C3); st = cnx_upload_f32(h->head_nb, data, C3); }
-    else if (key == "head.fc.bias") { EXPECT(NC); st = cnx_upload_f32(h->head_b, data, NC); }
+    } else if (key == "stem.0.bias") { EXPECT_NUMEL(C0); st = upload_f32(h->stem_b, data, C0); }
+    else if (key == "stem.1.weight") { EXPECT_NUMEL(C0); st = upload_f32(h->stem_nw, data, C0); }
+    else if (key == "stem.1.bias") { EXPECT_NUMEL(C0); st = upload_f32(h->stem_nb, data, C0); }
+    else if (key == "head.norm.weight") { EXPECT_NUMEL(C3); st = upload_f32(h->head_nw, data, C3); }
+    else if (key == "head.norm.bias") { EXPECT_NUMEL(C3); st = upload_f32(h->head_nb, data, C3); }
+    else if (key == "head.fc.bias") { EXPECT_NUMEL(NC); st = upload_f32(h->head_b, data, NC); }
     else if (key == "head.fc.weight") {
-        EXPECT((int64_t)NC * C3);
-        std::vector<float> dup((size_t)NC * 2 * C3);
-        for (int n = 0; n < NC; ++n)
-            for (int k = 0; k < C3; ++k) dup[(size_t)n * 2 * C3 + k] = dup[(size_t)n * 2 * C3 + C3 + k] = data[(size_t)n * C3 + k];
-        st = upload_matrix16(h->head_w, dup.data(), NC, 2 * C3, round_up(NC, 256), f16);
-    } else if (key.rfind("stages.", 0) == 0) {
-        const size_t d1 = key.find('.', 7);
-        if (d1 == std::string::npos) return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-        const int s = atoi(key.substr(7, d1 - 7).c_str());
+        EXPECT_NUMEL((int64_t)NC * C3);
+        st = upload_matrix16_dup(h->head_w, data, NC, C3, round_up(NC, 256), f16);
+    } else if (parse_indexed(key, "stages.", &s, &sub)) {
         if (s < 0 || s > 3) return set_error(HIPTS_ERR_INVALID, "tensor %s: stage out of range", key_c);
         CnxStage& St = h->st[s];
         const int C = St.C;
-        const std::string sub = key.substr(d1 + 1);
         if (sub.rfind("downsample.", 0) == 0) {
             if (s == 0) return set_error(HIPTS_ERR_INVALID, "tensor %s: stage 0 has no downsample", key_c);
             const int Cp = cf.dims[s - 1];
-            if (sub == "downsample.0.weight") { EXPECT(Cp); st = cnx_upload_f32(St.ds_nw, data, Cp); }
-            else if (sub == "downsample.0.bias") { EXPECT(Cp); st = cnx_upload_f32(St.ds_nb, data, Cp); }
-            else if (sub == "downsample.1.bias") { EXPECT(C); st = cnx_upload_f32(St.ds_b, data, C); }
+            if (sub == "downsample.0.weight") { EXPECT_NUMEL(Cp); st = upload_f32(St.ds_nw, data, Cp); }
+            else if (sub == "downsample.0.bias") { EXPECT_NUMEL(Cp); st = upload_f32(St.ds_nb, data, Cp); }
+            else if (sub == "downsample.1.bias") { EXPECT_NUMEL(C); st = upload_f32(St.ds_b, data, C); }
             else if (sub == "downsample.1.weight") {
-                EXPECT((int64_t)C * Cp * 4);
+                EXPECT_NUMEL((int64_t)C * Cp * 4);
                 std::vector<float> w2((size_t)C * 4 * Cp);          // [n][c][ky][kx] -> [n][(ky*2 + kx)*Cp + c], the gather's order
                 for (int n = 0; n < C; ++n)
                     for (int cc = 0; cc < Cp; ++cc)
                         for (int t = 0; t < 4; ++t) w2[((size_t)n * 4 + t) * Cp + cc] = data[((size_t)n * Cp + cc) * 4 + t];
                 st = upload_matrix16(St.ds_w, w2.data(), C, 4 * Cp, round_up(C, 256), f16);
             } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-        } else if (sub.rfind("blocks.", 0) == 0) {
-            const size_t d2 = sub.find('.', 7);
-            if (d2 == std::string::npos) return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-            const int bi = atoi(sub.substr(7, d2 - 7).c_str());
+        } else if (parse_indexed(sub, "blocks.", &bi, &t)) {
             if (bi < 0 || bi >= (int)St.blocks.size()) return set_error(HIPTS_ERR_INVALID, "tensor %s: block out of range", key_c);
             CnxBlock& B = St.blocks[bi];
-            const std::string t = sub.substr(d2 + 1);
             if (t == "conv_dw.weight") {
-                EXPECT((int64_t)C * 49);
+                EXPECT_NUMEL((int64_t)C * 49);
                 std::vector<float> w2((size_t)49 * C);          // [c][tap] -> [tap][c]
                 for (int cc = 0; cc < C; ++cc)
                     for (int tp = 0; tp < 49; ++tp) w2[(size_t)tp * C + cc] = data[(size_t)cc * 49 + tp];
-                st = cnx_upload_f32(B.dw, w2.data(), w2.size());
+                st = upload_f32(B.dw, w2.data(), w2.size());
                 if (st == HIPTS_OK && f16) {
                     const std::vector<uint32_t> tzv = dw_toeplitz_lanes(data, C);
-                    st = cnx_upload_f32(B.dwz, reinterpret_cast<const float*>(tzv.data()), tzv.size());
+                    st = upload_f32(B.dwz, reinterpret_cast<const float*>(tzv.data()), tzv.size());
                 }
             }
-            else if (t == "conv_dw.bias") { EXPECT(C); st = cnx_upload_f32(B.dw_b, data, C); }
-            else if (t == "norm.weight") { EXPECT(C); st = cnx_upload_f32(B.n_w, data, C); }
-            else if (t == "norm.bias") { EXPECT(C); st = cnx_upload_f32(B.n_b, data, C); }
-            else if (t == "gamma") { EXPECT(C); st = cnx_upload_f32(B.gamma, data, C); }
-            else if (t == "mlp.fc1.weight") { EXPECT((int64_t)4 * C * C); st = upload_matrix16(B.fc1, data, 4 * C, C, round_up(4 * C, 256), f16); }
-            else if (t == "mlp.fc1.bias") { EXPECT((int64_t)4 * C); st = cnx_upload_f32(B.fc1_b, data, (size_t)4 * C); }
-            else if (t == "mlp.fc2.weight") { EXPECT((int64_t)4 * C * C); st = upload_matrix16(B.fc2, data, C, 4 * C, round_up(C, 256), f16); }
-            else if (t == "mlp.fc2.bias") { EXPECT(C); st = cnx_upload_f32(B.fc2_b, data, C); }
+            else if (t == "conv_dw.bias") { EXPECT_NUMEL(C); st = upload_f32(B.dw_b, data, C); }
+            else if (t == "norm.weight") { EXPECT_NUMEL(C); st = upload_f32(B.n_w, data, C); }
+            else if (t == "norm.bias") { EXPECT_NUMEL(C); st = upload_f32(B.n_b, data, C); }
+            else if (t == "gamma") { EXPECT_NUMEL(C); st = upload_f32(B.gamma, data, C); }
+            else if (t == "mlp.fc1.weight") { EXPECT_NUMEL((int64_t)4 * C * C); st = upload_matrix16(B.fc1, data, 4 * C, C, round_up(4 * C, 256), f16); }
+            else if (t == "mlp.fc1.bias") { EXPECT_NUMEL((int64_t)4 * C); st = upload_f32(B.fc1_b, data, (size_t)4 * C); }
+            else if (t == "mlp.fc2.weight") { EXPECT_NUMEL((int64_t)4 * C * C); st = upload_matrix16(B.fc2, data, C, 4 * C, round_up(C, 256), f16); }
+            else if (t == "mlp.fc2.bias") { EXPECT_NUMEL(C); st = upload_f32(B.fc2_b, data, C); }
             else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
         } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
     } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-#undef EXPECT
     if (st) return st;
-    auto it = std::find(h->missing.begin(), h->missing.end(), key);
-    if (it != h->missing.end()) h->missing.erase(it);
+    h->ledger.mark_set(key);
     return HIPTS_OK;
 }
 

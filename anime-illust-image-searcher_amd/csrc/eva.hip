@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "vit_internal.h"
+#include "model_host.h"
 
 using namespace hipts;
 
@@ -46,14 +47,13 @@ struct hipts_eva {
     int grid = 0, np = 0, T = 0, TS = 0, Tp = 0, PK = 0, HN = 0, HK = 0;
     std::vector<EvaLayer> layers;
     DevBuf patch_w, patch_b, cls, pos, fcn_g, fcn_b, head_w, head_b, rope;
-    std::vector<std::string> missing;
+    TensorLedger ledger;
     DevBuf img_in, a0, tmp, x, xn, q, k, v, att, g1, stat_part, rowstat, xstat, pool_part, pooled2, logits, probs;
     DevBuf x0, x_rm;               // blocked residual stream (GemmArgs::x_blocked): the assembled rows row-major for layer 0's LayerNorm, the last layer's rows row-major for the pool
     bool fold_ln = false, fold_dirty = true;      // as in the ViT forward (vit.hip)
     bool split_att = false;                       // cfg.operand_f16 bit 4 (HIPTS_OPERAND_SPLIT_ATT), as in the ViT forward
     DevBuf sk_ws;                                 // split-K workspaces of proj / fc2 (GemmArgs::sk_ws), one per sub-batch stream, zeroed once
-    hipStream_t sub[2] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[2] = {};
+    SubStreams<2> streams;
 };
 
 namespace {
@@ -200,11 +200,6 @@ __global__ __launch_bounds__(1024) void eva_pool_kernel(const float* __restrict_
     }
 }
 
-int up_f32(DevBuf& buf, const float* data, size_t n) {
-    HIPTS_TRY(buf.alloc(n * 4));
-    return upload(buf.p, data, n * 4);
-}
-
 // rows x cols float block -> 16-bit operand bits at row offset `row0` of a [*, ld] matrix that was allocated zeroed
 int put_rows16(DevBuf& buf, const float* data, int rows, int cols, int row0, int ld, bool f16) {
     std::vector<uint16_t> h((size_t)rows * ld, 0);
@@ -345,9 +340,7 @@ int eva_run_images(hipts_eva* h, const void* in_dev, bool is_u8, int i0, int bat
     }
     float* part_p = h->pool_part.as<float>() + (size_t)i0 * POOL_SPLITS * D;
     eva_colsum_kernel<<<dim3(POOL_SPLITS, batch), 256, 0, s>>>(xb ? x_rm : x, part_p, np, TS, D);
-    if (f16) eva_pool_kernel<true><<<batch, 1024, 0, s>>>(part_p, h->fcn_g.as<float>(), h->fcn_b.as<float>(), pooled2_p, POOL_SPLITS, POOL_SPLITS, D, c.ln_eps, np);
-    else eva_pool_kernel<false><<<batch, 1024, 0, s>>>(part_p, h->fcn_g.as<float>(), h->fcn_b.as<float>(), pooled2_p, POOL_SPLITS, POOL_SPLITS, D, c.ln_eps, np);
-    HIPTS_LAUNCH_CHECK();
+    HIPTS_LAUNCH_F16(f16, eva_pool_kernel, batch, 1024, 0, s, part_p, h->fcn_g.as<float>(), h->fcn_b.as<float>(), pooled2_p, POOL_SPLITS, POOL_SPLITS, D, c.ln_eps, np);
     g = GemmArgs{};
     g.f16 = f16;
     g.shared_chip = shared_chip;
@@ -362,20 +355,14 @@ int eva_forward_impl(hipts_eva* h, const void* input, int in_memspace, bool is_u
                      int out_memspace, hipStream_t s) {
     HIPTS_REQUIRE(h && input && batch >= 1, "hipts_eva_forward: bad arguments");
     HIPTS_REQUIRE(batch <= h->cfg.max_batch, "batch %d exceeds max_batch %d", batch, h->cfg.max_batch);
-    if (!h->missing.empty())
-        return set_error(HIPTS_ERR_STATE, "hipts_eva_forward: %zu checkpoint tensors not set (first: %s)", h->missing.size(),
-                         h->missing[0].c_str());
+    HIPTS_TRY(h->ledger.require_complete("hipts_eva_forward"));
     HIPTS_TRY(use_device(h->device));
     const auto& c = h->cfg;
     const int S = c.image_size;
-    const void* in_dev = input;
-    if (in_memspace != HIPTS_DEVICE) {
-        const size_t bytes = (size_t)batch * S * S * 3 * (is_u8 ? 1 : 4);
-        HIPTS_TRY(h->img_in.reserve(bytes));
-        HIPTS_HIP(hipMemcpyAsync(h->img_in.p, input, bytes, hipMemcpyHostToDevice, s));
-        in_dev = h->img_in.p;
-    }
+    const void* in_dev = nullptr;
+    HIPTS_TRY(stage_input(h->img_in, input, in_memspace, (size_t)batch * S * S * 3 * (is_u8 ? 1 : 4), s, &in_dev));
     const bool dev_out = out_memspace == HIPTS_DEVICE;
+    // deliberate: logits are always computed, into the handle's own buffer when the caller passes none (ConvNeXt / SwinV2 pass null on)
     float* lg = (dev_out && logits_out) ? logits_out : h->logits.as<float>();
     float* pr = (probs_out || !dev_out) ? ((dev_out && probs_out) ? probs_out : h->probs.as<float>()) : nullptr;
     if (h->fold_ln && h->fold_dirty) {
@@ -391,32 +378,11 @@ int eva_forward_impl(hipts_eva* h, const void* input, int in_memspace, bool is_u
     static const int want_streams = getenv("HIPTS_EVA_STREAMS") ? atoi(getenv("HIPTS_EVA_STREAMS")) : 2;
     static const int min_sub = getenv("HIPTS_EVA_MINSUB") ? atoi(getenv("HIPTS_EVA_MINSUB")) : 5;      // images per sub-batch needed to split (the reference batch of 10 as two halves: 980 -> 1005 images/s)
     const int ns = std::min({want_streams, 2, batch / (min_sub > 0 ? min_sub : 5)});
-    if (ns >= 2) {
-        // two sub-batches on two internal streams, as in the ViT forward (partial last rounds of the persistent GEMMs)
-        if (!h->ev_fork) {
-            HIPTS_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            for (int i = 0; i < 2; ++i) {
-                HIPTS_HIP(hipStreamCreateWithFlags(&h->sub[i], hipStreamNonBlocking));
-                HIPTS_HIP(hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
-            }
-        }
-        HIPTS_HIP(hipEventRecord(h->ev_fork, s));
-        const int nb0 = (batch + 1) / 2;
-        for (int i = 0; i < 2; ++i) {
-            HIPTS_HIP(hipStreamWaitEvent(h->sub[i], h->ev_fork, 0));
-            HIPTS_TRY(eva_run_images(h, in_dev, is_u8, i ? nb0 : 0, i ? batch - nb0 : nb0, lg, pr, h->sub[i], true, i));
-            HIPTS_HIP(hipEventRecord(h->ev_join[i], h->sub[i]));
-            HIPTS_HIP(hipStreamWaitEvent(s, h->ev_join[i], 0));
-        }
-    } else {
-        HIPTS_TRY(eva_run_images(h, in_dev, is_u8, 0, batch, lg, pr, s, false));
-    }
-    if (!dev_out) {
-        const size_t bytes = (size_t)batch * c.num_classes * 4;
-        if (logits_out) HIPTS_HIP(hipMemcpyAsync(logits_out, lg, bytes, hipMemcpyDeviceToHost, s));
-        if (probs_out) HIPTS_HIP(hipMemcpyAsync(probs_out, pr, bytes, hipMemcpyDeviceToHost, s));
-        HIPTS_HIP(hipStreamSynchronize(s));
-    }
+    // two sub-batches on two internal streams, as in the ViT forward (partial last rounds of the persistent GEMMs)
+    HIPTS_TRY(run_split(h->streams, s, batch, ns, [&](int i0, int nb, hipStream_t st, bool shared_chip, int sub) {
+        return eva_run_images(h, in_dev, is_u8, i0, nb, lg, pr, st, shared_chip, sub);
+    }));
+    if (!dev_out) HIPTS_TRY(read_back(s, (size_t)batch * c.num_classes * 4, logits_out, lg, probs_out, pr));
     return HIPTS_OK;
 }
 
@@ -478,7 +444,7 @@ int hipts_eva_create(const hipts_eva_config_t* cfg, int device, hipts_eva_t** ou
                 tab[t * 64 + 2 * i] = sn[t * 64 + 2 * i];
                 tab[t * 64 + 2 * i + 1] = cs[t * 64 + 2 * i];
             }
-        if ((st = up_f32(h->rope, tab.data(), tab.size()))) {
+        if ((st = upload_f32(h->rope, tab.data(), tab.size()))) {
             delete h;
             return st;
         }
@@ -499,7 +465,7 @@ int hipts_eva_create(const hipts_eva_config_t* cfg, int device, hipts_eva_t** ou
         delete h;
         return st;
     }
-    auto need = [&](const std::string& k) { h->missing.push_back(k); };
+    auto need = [&](const std::string& k) { h->ledger.need(k); };
     for (const char* k : {"patch_embed.proj.weight", "patch_embed.proj.bias", "cls_token", "pos_embed", "fc_norm.weight", "fc_norm.bias", "head.weight",
                           "head.bias"})
         need(k);
@@ -518,11 +484,6 @@ int hipts_eva_destroy(hipts_eva_t* h) {
     if (h) {
         (void)hipSetDevice(h->device);
         (void)hipDeviceSynchronize();
-        for (int i = 0; i < 2; ++i) {
-            if (h->sub[i]) (void)hipStreamDestroy(h->sub[i]);
-            if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]);
-        }
-        if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
         delete h;
     }
     return HIPTS_OK;
@@ -535,86 +496,60 @@ int hipts_eva_set_tensor(hipts_eva_t* h, const char* key_c, const float* data, i
     const auto& c = h->cfg;
     const bool f16 = (c.operand_f16 & 1) != 0;
     const int D = c.dim, P = c.patch, Hd = c.mlp_hidden, C = c.num_classes;
-    int st = HIPTS_OK;
-#define EXPECT(n)                                                                                                         \
-    do {                                                                                                                  \
-        if (numel != (int64_t)(n)) return set_error(HIPTS_ERR_INVALID, "tensor %s: %lld elements, expected %lld", key_c, (long long)numel, (long long)(n)); \
-    } while (0)
+    int st = HIPTS_OK, li = 0;
+    std::string t;
     if (key == "patch_embed.proj.weight") {
-        EXPECT((int64_t)D * 3 * P * P);
-        // [n][c_model][ky][kx] -> [n][(ky*P + kx)*3 + c_mem], c_model = 2 - c_mem (BGR flip), duplicated for hi | lo
-        const int K1 = P * P * 3;
-        std::vector<float> w2((size_t)D * 2 * h->PK, 0.f);
-        for (int n = 0; n < D; ++n)
-            for (int cm = 0; cm < 3; ++cm)
-                for (int t = 0; t < P * P; ++t) {
-                    const float v = data[((size_t)n * 3 + (2 - cm)) * P * P + t];
-                    w2[(size_t)n * 2 * h->PK + t * 3 + cm] = v;
-                    w2[(size_t)n * 2 * h->PK + h->PK + t * 3 + cm] = v;
-                }
-        (void)K1;
+        EXPECT_NUMEL((int64_t)D * 3 * P * P);
+        const std::vector<float> w2 = stem_weight_hilo(data, D, P * P, h->PK, true);      // BGR flip; the hi | lo halves of eva_patchify_kernel
         st = put_rows16(h->patch_w, w2.data(), D, 2 * h->PK, 0, 2 * h->PK, f16);
-    } else if (key == "patch_embed.proj.bias") { EXPECT(D); st = up_f32(h->patch_b, data, D); }
-    else if (key == "cls_token") { EXPECT(D); st = up_f32(h->cls, data, D); }
-    else if (key == "pos_embed") { EXPECT((int64_t)h->T * D); st = up_f32(h->pos, data, (size_t)h->T * D); }
-    else if (key == "fc_norm.weight") { EXPECT(D); st = up_f32(h->fcn_g, data, D); }
-    else if (key == "fc_norm.bias") { EXPECT(D); st = up_f32(h->fcn_b, data, D); }
-    else if (key == "head.bias") { EXPECT(C); st = up_f32(h->head_b, data, C); }
+    } else if (key == "patch_embed.proj.bias") { EXPECT_NUMEL(D); st = upload_f32(h->patch_b, data, D); }
+    else if (key == "cls_token") { EXPECT_NUMEL(D); st = upload_f32(h->cls, data, D); }
+    else if (key == "pos_embed") { EXPECT_NUMEL((int64_t)h->T * D); st = upload_f32(h->pos, data, (size_t)h->T * D); }
+    else if (key == "fc_norm.weight") { EXPECT_NUMEL(D); st = upload_f32(h->fcn_g, data, D); }
+    else if (key == "fc_norm.bias") { EXPECT_NUMEL(D); st = upload_f32(h->fcn_b, data, D); }
+    else if (key == "head.bias") { EXPECT_NUMEL(C); st = upload_f32(h->head_b, data, C); }
     else if (key == "head.weight") {
-        EXPECT((int64_t)C * D);
-        std::vector<float> dup((size_t)C * 2 * D);
-        for (int n = 0; n < C; ++n)
-            for (int k2 = 0; k2 < D; ++k2) dup[(size_t)n * 2 * D + k2] = dup[(size_t)n * 2 * D + D + k2] = data[(size_t)n * D + k2];
-        st = upload_matrix16(h->head_w, dup.data(), C, 2 * D, round_up(C, 256), f16);
-    } else if (key.rfind("blocks.", 0) == 0) {
-        const size_t d1 = key.find('.', 7);
-        if (d1 == std::string::npos) return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-        const int li = atoi(key.substr(7, d1 - 7).c_str());
+        EXPECT_NUMEL((int64_t)C * D);
+        st = upload_matrix16_dup(h->head_w, data, C, D, round_up(C, 256), f16);
+    } else if (parse_indexed(key, "blocks.", &li, &t)) {
         if (li < 0 || li >= c.depth) return set_error(HIPTS_ERR_INVALID, "tensor %s: block out of range", key_c);
         EvaLayer& L = h->layers[li];
-        const std::string t = key.substr(d1 + 1);
-        if (t == "norm1.weight") { EXPECT(D); st = up_f32(L.ln1_g, data, D); }
-        else if (t == "norm1.bias") { EXPECT(D); st = up_f32(L.ln1_b, data, D); }
-        else if (t == "norm2.weight") { EXPECT(D); st = up_f32(L.ln2_g, data, D); }
-        else if (t == "norm2.bias") { EXPECT(D); st = up_f32(L.ln2_b, data, D); }
-        else if (t == "attn.q_proj.weight") { EXPECT((int64_t)D * D); st = put_rows16(L.qkv_w, data, D, D, 0, D, f16); }
-        else if (t == "attn.k_proj.weight") { EXPECT((int64_t)D * D); st = put_rows16(L.qkv_w, data, D, D, D, D, f16); }
-        else if (t == "attn.v_proj.weight") { EXPECT((int64_t)D * D); st = put_rows16(L.qkv_w, data, D, D, 2 * D, D, f16); }
-        else if (t == "attn.q_proj.bias") { EXPECT(D); st = upload(L.qkv_b.as<float>(), data, (size_t)D * 4); }
-        else if (t == "attn.v_proj.bias") { EXPECT(D); st = upload(L.qkv_b.as<float>() + 2 * D, data, (size_t)D * 4); }
+        if (t == "norm1.weight") { EXPECT_NUMEL(D); st = upload_f32(L.ln1_g, data, D); }
+        else if (t == "norm1.bias") { EXPECT_NUMEL(D); st = upload_f32(L.ln1_b, data, D); }
+        else if (t == "norm2.weight") { EXPECT_NUMEL(D); st = upload_f32(L.ln2_g, data, D); }
+        else if (t == "norm2.bias") { EXPECT_NUMEL(D); st = upload_f32(L.ln2_b, data, D); }
+        else if (t == "attn.q_proj.weight") { EXPECT_NUMEL((int64_t)D * D); st = put_rows16(L.qkv_w, data, D, D, 0, D, f16); }
+        else if (t == "attn.k_proj.weight") { EXPECT_NUMEL((int64_t)D * D); st = put_rows16(L.qkv_w, data, D, D, D, D, f16); }
+        else if (t == "attn.v_proj.weight") { EXPECT_NUMEL((int64_t)D * D); st = put_rows16(L.qkv_w, data, D, D, 2 * D, D, f16); }
+        else if (t == "attn.q_proj.bias") { EXPECT_NUMEL(D); st = upload(L.qkv_b.as<float>(), data, (size_t)D * 4); }
+        else if (t == "attn.v_proj.bias") { EXPECT_NUMEL(D); st = upload(L.qkv_b.as<float>() + 2 * D, data, (size_t)D * 4); }
         else if (t == "attn.proj.weight") {
-            EXPECT((int64_t)D * D);
+            EXPECT_NUMEL((int64_t)D * D);
             if (h->split_att) {      // [W | W] against the (hi | lo) halves of the attention output
-                std::vector<float> dup((size_t)D * 2 * D);
-                const float inv = 1.0f / split_lo_scale(f16);      // the low halves arrive multiplied by the scale
-                for (int n = 0; n < D; ++n) {
-                    memcpy(&dup[(size_t)n * 2 * D], &data[(size_t)n * D], (size_t)D * 4);
-                    for (int kk = 0; kk < D; ++kk) dup[(size_t)n * 2 * D + D + kk] = data[(size_t)n * D + kk] * inv;
-                }
-                st = upload_matrix16(L.proj_w, dup.data(), D, 2 * D, round_up(D, 256), f16);
+                st = upload_matrix16_dup(L.proj_w, data, D, D, round_up(D, 256), f16, split_lo_scale(f16));      // the low halves arrive multiplied by the scale
             } else {
                 st = upload_matrix16(L.proj_w, data, D, D, round_up(D, 256), f16);
             }
         }
-        else if (t == "attn.proj.bias") { EXPECT(D); st = up_f32(L.proj_b, data, D); }
+        else if (t == "attn.proj.bias") { EXPECT_NUMEL(D); st = upload_f32(L.proj_b, data, D); }
         else if (t == "mlp.fc1_g.weight" || t == "mlp.fc1_x.weight") {
             // hidden unit u -> physical row 64 (u / 32) + (u % 32), + 32 for the value half (EPI_SWIGLU)
-            EXPECT((int64_t)Hd * D);
+            EXPECT_NUMEL((int64_t)Hd * D);
             const int half = t == "mlp.fc1_x.weight" ? 32 : 0;
             for (int u0 = 0; u0 < Hd && !st; u0 += 32)
                 st = put_rows16(L.gx_w, data + (size_t)u0 * D, std::min(32, Hd - u0), D, (u0 / 32) * 64 + half, D, f16);
         }
         else if (t == "mlp.fc1_g.bias" || t == "mlp.fc1_x.bias") {
-            EXPECT(Hd);
+            EXPECT_NUMEL(Hd);
             const int half = t == "mlp.fc1_x.bias" ? 32 : 0;
             for (int u0 = 0; u0 < Hd && !st; u0 += 32)
                 st = upload(L.gx_b.as<float>() + (u0 / 32) * 64 + half, data + u0, (size_t)std::min(32, Hd - u0) * 4);
         }
         else if (t == "mlp.norm.weight" || t == "mlp.norm.bias" || t == "mlp.fc2.weight" || t == "mlp.fc2.bias") {
-            if (t == "mlp.norm.weight") { EXPECT(Hd); L.h_mn_g.assign(data, data + Hd); }
-            else if (t == "mlp.norm.bias") { EXPECT(Hd); L.h_mn_b.assign(data, data + Hd); }
-            else if (t == "mlp.fc2.weight") { EXPECT((int64_t)D * Hd); L.h_fc2_w.assign(data, data + (size_t)D * Hd); }
-            else { EXPECT(D); L.h_fc2_b.assign(data, data + D); }
+            if (t == "mlp.norm.weight") { EXPECT_NUMEL(Hd); L.h_mn_g.assign(data, data + Hd); }
+            else if (t == "mlp.norm.bias") { EXPECT_NUMEL(Hd); L.h_mn_b.assign(data, data + Hd); }
+            else if (t == "mlp.fc2.weight") { EXPECT_NUMEL((int64_t)D * Hd); L.h_fc2_w.assign(data, data + (size_t)D * Hd); }
+            else { EXPECT_NUMEL(D); L.h_fc2_b.assign(data, data + D); }
             if (!L.h_mn_g.empty() && !L.h_mn_b.empty() && !L.h_fc2_w.empty() && !L.h_fc2_b.empty()) {
                 // u and c from the rounded operand values of W, so that the mean term cancels against what the MFMA sums
                 std::vector<float> u(D), cc(D);
@@ -639,11 +574,9 @@ int hipts_eva_set_tensor(hipts_eva_t* h, const char* key_c, const float* data, i
         }
         else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
     } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-#undef EXPECT
     if (st) return st;
     h->fold_dirty = true;
-    auto it = std::find(h->missing.begin(), h->missing.end(), key);
-    if (it != h->missing.end()) h->missing.erase(it);
+    h->ledger.mark_set(key);
     return HIPTS_OK;
 }
 

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "vit_internal.h"
+#include "model_host.h"
 #include "convnet.h"
 
 using namespace hipts;
@@ -63,14 +64,12 @@ struct hipts_swinv2 {
     hipts_swinv2_config_t cfg{};
     SwStage st[4];
     DevBuf stem_w, stem_b, stem_nw, stem_nb, head_nw, head_nb, head_w, head_b, lut;
-    std::vector<std::string> missing;
+    TensorLedger ledger;
     bool cpb_ready = false;
     // workspace (sized for cfg.max_batch), carved per image with the stride of the largest stage
     DevBuf img_in, a0, x, xh, xh2, qkv, ao, br, m1, col, feat, feat2, logits, probs;
     size_t px = 0, p3c = 0, phid = 0, pcol = 0;
-    static constexpr int NSUB = 2;
-    hipStream_t sub[NSUB] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[NSUB] = {};
+    SubStreams<2> streams;
     double flops_per_image = 0.0;
 };
 
@@ -183,11 +182,6 @@ __global__ __launch_bounds__(256) void sw_mean_kernel(const float* __restrict__ 
     }
 }
 
-int sw_upload_f32(DevBuf& buf, const float* data, size_t n) {
-    HIPTS_TRY(buf.alloc(n * 4));
-    return upload(buf.p, data, n * 4);
-}
-
 // 16 sigmoid(cpb_mlp(table)) for one block: [heads][(2 w - 1)^2], table entry (dy, dx) = sign(t) log2(1 + |t|) / log2(8) with
 // t = 8 offset / (pw - 1) per axis (pw = the window, or cpb_pretrained_window when set).
 std::vector<float> sw_cpb_table(const SwBlock& B, int w, int pw, int heads) {
@@ -221,7 +215,7 @@ int sw_prepare_cpb(hipts_swinv2* h) {
     for (SwStage& St : h->st)
         for (SwBlock& B : St.blocks) {
             const std::vector<float> t = sw_cpb_table(B, St.win, pw_cfg > 0 ? pw_cfg : St.win, St.heads);
-            HIPTS_TRY(sw_upload_f32(B.cpb, t.data(), t.size()));
+            HIPTS_TRY(upload_f32(B.cpb, t.data(), t.size()));
         }
     h->cpb_ready = true;
     return HIPTS_OK;
@@ -269,13 +263,9 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
         g.A = a0; g.W = h->stem_w.as<bf16_t>(); g.M = (int)M; g.N = S0.C; g.K = CNX_STEM_K;
         g.bias = h->stem_b.as<float>(); g.out_f32 = x;
         HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
-        if (f16) cnx_ln_kernel<true><<<ceil_div(M, 4), 256, 0, s>>>(x, h->stem_nw.as<float>(), h->stem_nb.as<float>(), xh, M, S0.C, c.ln_eps);
-        else cnx_ln_kernel<false><<<ceil_div(M, 4), 256, 0, s>>>(x, h->stem_nw.as<float>(), h->stem_nb.as<float>(), xh, M, S0.C, c.ln_eps);
-        HIPTS_LAUNCH_CHECK();
+        HIPTS_LAUNCH_F16(f16, cnx_ln_kernel, ceil_div(M, 4), 256, 0, s, x, h->stem_nw.as<float>(), h->stem_nb.as<float>(), xh, M, S0.C, c.ln_eps);
         const int64_t n4 = M * S0.C / 4;
-        if (f16) sw_split_x_kernel<true><<<ceil_div(n4, 256), 256, 0, s>>>(x, xh2, n4, S0.C);
-        else sw_split_x_kernel<false><<<ceil_div(n4, 256), 256, 0, s>>>(x, xh2, n4, S0.C);
-        HIPTS_LAUNCH_CHECK();
+        HIPTS_LAUNCH_F16(f16, sw_split_x_kernel, ceil_div(n4, 256), 256, 0, s, x, xh2, n4, S0.C);
     }
 
     for (int si = 0; si < 4; ++si) {
@@ -286,20 +276,14 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
             // patch merging: 2x2 gather -> reduction GEMM -> LayerNorm (weight, bias) in place, with the 16-bit copy
             const SwStage& Pv = h->st[si - 1];
             const int64_t total4 = (int64_t)M * Pv.C;          // M rows of 4 Cprev, in float4
-            if (f16) sw_merge_kernel<true><<<ceil_div(total4, 256), 256, 0, s>>>(x, col, total4, Pv.H, Pv.C);
-            else sw_merge_kernel<false><<<ceil_div(total4, 256), 256, 0, s>>>(x, col, total4, Pv.H, Pv.C);
-            HIPTS_LAUNCH_CHECK();
+            HIPTS_LAUNCH_F16(f16, sw_merge_kernel, ceil_div(total4, 256), 256, 0, s, x, col, total4, Pv.H, Pv.C);
             GemmArgs g = gemm_args();
             g.A = col; g.W = St.ds_w.as<bf16_t>(); g.M = M; g.N = C; g.K = 8 * Pv.C;
             g.bias = St.ds_b.as<float>(); g.out_f32 = x;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
-            if (f16) cnx_ln_kernel<true><<<ceil_div(M, 4), 256, 0, s>>>(x, St.ds_nw.as<float>(), St.ds_nb.as<float>(), xh, M, C, c.ln_eps);
-            else cnx_ln_kernel<false><<<ceil_div(M, 4), 256, 0, s>>>(x, St.ds_nw.as<float>(), St.ds_nb.as<float>(), xh, M, C, c.ln_eps);
-            HIPTS_LAUNCH_CHECK();
+            HIPTS_LAUNCH_F16(f16, cnx_ln_kernel, ceil_div(M, 4), 256, 0, s, x, St.ds_nw.as<float>(), St.ds_nb.as<float>(), xh, M, C, c.ln_eps);
             const int64_t n4 = (int64_t)M * C / 4;
-            if (f16) sw_split_x_kernel<true><<<ceil_div(n4, 256), 256, 0, s>>>(x, xh2, n4, C);
-            else sw_split_x_kernel<false><<<ceil_div(n4, 256), 256, 0, s>>>(x, xh2, n4, C);
-            HIPTS_LAUNCH_CHECK();
+            HIPTS_LAUNCH_F16(f16, sw_split_x_kernel, ceil_div(n4, 256), 256, 0, s, x, xh2, n4, C);
         }
         for (SwBlock& B : St.blocks) {
             GemmArgs g = gemm_args();
@@ -309,9 +293,7 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
             g = gemm_args();
             g.A = ao; g.W = B.proj.as<bf16_t>(); g.M = M; g.N = C; g.K = C; g.bias = B.proj_b.as<float>(); g.out_f32 = br;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
-            if (f16) sw_postnorm_kernel<true><<<ceil_div(M, 4), 256, 0, s>>>(br, B.n1_w.as<float>(), B.n1_b.as<float>(), x, xh2, M, C, c.ln_eps);
-            else sw_postnorm_kernel<false><<<ceil_div(M, 4), 256, 0, s>>>(br, B.n1_w.as<float>(), B.n1_b.as<float>(), x, xh2, M, C, c.ln_eps);
-            HIPTS_LAUNCH_CHECK();
+            HIPTS_LAUNCH_F16(f16, sw_postnorm_kernel, ceil_div(M, 4), 256, 0, s, br, B.n1_w.as<float>(), B.n1_b.as<float>(), x, xh2, M, C, c.ln_eps);
             g = gemm_args();
             g.A = xh2; g.W = B.fc1.as<bf16_t>(); g.M = M; g.N = St.hid; g.K = 2 * C; g.bias = B.fc1_b.as<float>();
             g.out_bf16 = m1; g.gelu_tanh = c.gelu_tanh;
@@ -319,9 +301,7 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
             g = gemm_args();
             g.A = m1; g.W = B.fc2.as<bf16_t>(); g.M = M; g.N = C; g.K = St.hid; g.bias = B.fc2_b.as<float>(); g.out_f32 = br;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
-            if (f16) sw_postnorm_kernel<true><<<ceil_div(M, 4), 256, 0, s>>>(br, B.n2_w.as<float>(), B.n2_b.as<float>(), x, xh2, M, C, c.ln_eps);
-            else sw_postnorm_kernel<false><<<ceil_div(M, 4), 256, 0, s>>>(br, B.n2_w.as<float>(), B.n2_b.as<float>(), x, xh2, M, C, c.ln_eps);
-            HIPTS_LAUNCH_CHECK();
+            HIPTS_LAUNCH_F16(f16, sw_postnorm_kernel, ceil_div(M, 4), 256, 0, s, br, B.n2_w.as<float>(), B.n2_b.as<float>(), x, xh2, M, C, c.ln_eps);
         }
         if (si == stop_stage) return HIPTS_OK;
     }
@@ -334,9 +314,7 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
     HIPTS_LAUNCH_CHECK();
     sw_mean_kernel<<<batch, 256, 0, s>>>(br, feat, L.T, L.C);
     HIPTS_LAUNCH_CHECK();
-    if (f16) cnx_split_kernel<true><<<ceil_div((int64_t)batch * L.C, 256), 256, 0, s>>>(feat, feat2, batch, L.C);
-    else cnx_split_kernel<false><<<ceil_div((int64_t)batch * L.C, 256), 256, 0, s>>>(feat, feat2, batch, L.C);
-    HIPTS_LAUNCH_CHECK();
+    HIPTS_LAUNCH_F16(f16, cnx_split_kernel, ceil_div((int64_t)batch * L.C, 256), 256, 0, s, feat, feat2, batch, L.C);
     GemmArgs g = gemm_args();
     g.A = feat2; g.W = h->head_w.as<bf16_t>(); g.M = batch; g.N = c.num_classes; g.K = 2 * L.C;
     g.bias = h->head_b.as<float>(); g.out_f32 = lg ? lg + (size_t)i0 * c.num_classes : nullptr;
@@ -349,65 +327,26 @@ int sw_forward_impl(hipts_swinv2* h, const void* input, int in_memspace, bool is
                     int out_memspace, hipStream_t s, int stop_stage = -1) {
     HIPTS_REQUIRE(h && input && batch >= 1, "hipts_swinv2_forward: bad arguments");
     HIPTS_REQUIRE(batch <= h->cfg.max_batch, "batch %d exceeds max_batch %d", batch, h->cfg.max_batch);
-    if (!h->missing.empty())
-        return set_error(HIPTS_ERR_STATE, "hipts_swinv2_forward: %zu checkpoint tensors not set (first: %s)", h->missing.size(),
-                         h->missing[0].c_str());
+    HIPTS_TRY(h->ledger.require_complete("hipts_swinv2_forward"));
     HIPTS_TRY(use_device(h->device));
     HIPTS_TRY(sw_prepare_cpb(h));
     const auto& c = h->cfg;
     const int S = c.image_size, NC = c.num_classes;
-    const void* in_dev = input;
-    if (in_memspace != HIPTS_DEVICE) {
-        const size_t bytes = (size_t)batch * S * S * 3 * (is_u8 ? 1 : 4);
-        HIPTS_TRY(h->img_in.reserve(bytes));
-        HIPTS_HIP(hipMemcpyAsync(h->img_in.p, input, bytes, hipMemcpyHostToDevice, s));
-        in_dev = h->img_in.p;
-    }
+    const void* in_dev = nullptr;
+    HIPTS_TRY(stage_input(h->img_in, input, in_memspace, (size_t)batch * S * S * 3 * (is_u8 ? 1 : 4), s, &in_dev));
     const bool dev_out = out_memspace == HIPTS_DEVICE;
+    // deliberate: an output the caller does not ask for stays null and EPI_HEAD skips it (the ViT / EVA02 forwards always compute logits)
     float* lg = dev_out ? logits_out : (logits_out ? h->logits.as<float>() : nullptr);
     float* pr = dev_out ? probs_out : (probs_out ? h->probs.as<float>() : nullptr);
     // Two sub-batches on two internal streams from 32 images on (as the other forwards); the split changes which images share a
     // launch, never an image's arithmetic.
-    const int ns = (stop_stage < 0 && batch >= 32) ? hipts_swinv2::NSUB : 1;
-    if (ns >= 2) {
-        if (!h->ev_fork) {
-            HIPTS_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            for (int i = 0; i < hipts_swinv2::NSUB; ++i) {
-                HIPTS_HIP(hipStreamCreateWithFlags(&h->sub[i], hipStreamNonBlocking));
-                HIPTS_HIP(hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
-            }
-        }
-        HIPTS_HIP(hipEventRecord(h->ev_fork, s));
-        for (int i = 0; i < ns; ++i) {
-            const int a0 = i ? (batch + 1) / 2 : 0, a1 = i ? batch : (batch + 1) / 2;
-            HIPTS_HIP(hipStreamWaitEvent(h->sub[i], h->ev_fork, 0));
-            HIPTS_TRY(sw_run_images(h, in_dev, is_u8, a0, a1 - a0, lg, pr, h->sub[i], true, -1));
-            HIPTS_HIP(hipEventRecord(h->ev_join[i], h->sub[i]));
-            HIPTS_HIP(hipStreamWaitEvent(s, h->ev_join[i], 0));
-        }
-    } else {
-        HIPTS_TRY(sw_run_images(h, in_dev, is_u8, 0, batch, lg, pr, s, false, stop_stage));
-    }
-    if (stop_stage < 0 && !dev_out) {
-        if (logits_out) HIPTS_HIP(hipMemcpyAsync(logits_out, lg, (size_t)batch * NC * 4, hipMemcpyDeviceToHost, s));
-        if (probs_out) HIPTS_HIP(hipMemcpyAsync(probs_out, pr, (size_t)batch * NC * 4, hipMemcpyDeviceToHost, s));
-        HIPTS_HIP(hipStreamSynchronize(s));
-    }
+    // The debug entry (stop_stage >= 0) never splits and reads nothing back: its caller copies the residual stream itself.
+    const int ns = (stop_stage < 0 && batch >= 32) ? 2 : 1;
+    HIPTS_TRY(run_split(h->streams, s, batch, ns, [&](int i0, int nb, hipStream_t st, bool shared_chip, int) {
+        return sw_run_images(h, in_dev, is_u8, i0, nb, lg, pr, st, shared_chip, stop_stage);
+    }));
+    if (stop_stage < 0 && !dev_out) HIPTS_TRY(read_back(s, (size_t)batch * NC * 4, logits_out, lg, probs_out, pr));
     return HIPTS_OK;
-}
-
-float half_bits_to_f32(uint16_t v, bool f16) {
-    if (!f16) {
-        const uint32_t u = (uint32_t)v << 16;
-        float f;
-        memcpy(&f, &u, 4);
-        return f;
-    }
-    const int e = (v >> 10) & 31, m = v & 1023;
-    const float sgn = (v & 0x8000) ? -1.0f : 1.0f;
-    if (e == 0) return sgn * std::ldexp((float)m, -24);
-    if (e == 31) return m ? NAN : sgn * INFINITY;
-    return sgn * std::ldexp((float)(m | 1024), e - 25);
 }
 
 }  // namespace
@@ -473,11 +412,9 @@ int hipts_swinv2_create(const hipts_swinv2_config_t* cfg, int device, hipts_swin
     flops += 2.0 * cfg->dims[3] * (double)cfg->num_classes;
     h->flops_per_image = flops;
     const int C3 = cfg->dims[3];
-    std::vector<float> lut(3 * 256);
-    for (int cc = 0; cc < 3; ++cc)
-        for (int u = 0; u < 256; ++u) lut[cc * 256 + u] = ((float)u / 255.0f - cfg->norm_mean[cc]) / cfg->norm_std[cc];      // ToTensor + Normalize, float32
+    const std::vector<float> lut = norm_lut(cfg->norm_mean, cfg->norm_std);
     int st = 0;
-    if ((st = sw_upload_f32(h->lut, lut.data(), lut.size())) || (st = h->a0.alloc((size_t)B * h->st[0].T * CNX_STEM_K * 2)) ||
+    if ((st = upload_f32(h->lut, lut.data(), lut.size())) || (st = h->a0.alloc((size_t)B * h->st[0].T * CNX_STEM_K * 2)) ||
         (st = h->x.alloc((size_t)B * h->px * 4)) || (st = h->xh.alloc((size_t)B * h->px * 2)) || (st = h->xh2.alloc((size_t)B * h->px * 4)) || (st = h->qkv.alloc((size_t)B * h->p3c * 4)) ||
         (st = h->ao.alloc((size_t)B * h->px * 2)) || (st = h->br.alloc((size_t)B * h->px * 4)) || (st = h->m1.alloc((size_t)B * h->phid * 2)) ||
         (st = h->col.alloc((size_t)B * h->pcol * 2)) || (st = h->feat.alloc((size_t)B * C3 * 4)) || (st = h->feat2.alloc((size_t)B * 2 * C3 * 2)) ||
@@ -487,12 +424,12 @@ int hipts_swinv2_create(const hipts_swinv2_config_t* cfg, int device, hipts_swin
     }
     for (int s = 1; s < 4; ++s) {
         const std::vector<float> zero(h->st[s].C, 0.f);
-        if ((st = sw_upload_f32(h->st[s].ds_b, zero.data(), zero.size()))) {
+        if ((st = upload_f32(h->st[s].ds_b, zero.data(), zero.size()))) {
             delete h;
             return st;
         }
     }
-    auto need = [&](const std::string& k) { h->missing.push_back(k); };
+    auto need = [&](const std::string& k) { h->ledger.need(k); };
     need("patch_embed.proj.weight"); need("patch_embed.proj.bias"); need("patch_embed.norm.weight"); need("patch_embed.norm.bias");
     for (int s = 0; s < 4; ++s) {
         const std::string sp = "layers." + std::to_string(s) + ".";
@@ -516,11 +453,6 @@ int hipts_swinv2_destroy(hipts_swinv2_t* h) {
     if (h) {
         (void)hipSetDevice(h->device);
         (void)hipDeviceSynchronize();
-        for (int i = 0; i < hipts_swinv2::NSUB; ++i) {
-            if (h->sub[i]) (void)hipStreamDestroy(h->sub[i]);
-            if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]);
-        }
-        if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
         delete h;
     }
     return HIPTS_OK;
@@ -533,107 +465,75 @@ int hipts_swinv2_set_tensor(hipts_swinv2_t* h, const char* key_c, const float* d
     const auto& cf = h->cfg;
     const bool f16 = (cf.operand_f16 & 1) != 0;
     int st = HIPTS_OK;
-#define EXPECT(n)                                                                                                         \
-    do {                                                                                                                  \
-        if (numel != (int64_t)(n)) return set_error(HIPTS_ERR_INVALID, "tensor %s: %lld elements, expected %lld", key_c, (long long)numel, (long long)(n)); \
-    } while (0)
     const int C0 = cf.dims[0], C3 = cf.dims[3], NC = cf.num_classes;
+    int s = 0, bi = 0;
+    std::string sub, t;
     if (key == "patch_embed.proj.weight") {
-        EXPECT((int64_t)C0 * 48);
-        // [n][c_model][ky][kx] -> [n][(ky*4 + kx)*3 + c_mem], c_model = 2 - c_mem (BGR), duplicated for the hi | lo halves (cnx_stem_kernel)
-        std::vector<float> w2((size_t)C0 * CNX_STEM_K, 0.f);
-        for (int n = 0; n < C0; ++n)
-            for (int cm = 0; cm < 3; ++cm)
-                for (int t = 0; t < 16; ++t) {
-                    const float v = data[((size_t)n * 3 + (2 - cm)) * 16 + t];
-                    w2[(size_t)n * CNX_STEM_K + t * 3 + cm] = v;
-                    w2[(size_t)n * CNX_STEM_K + CNX_STEM_KH + t * 3 + cm] = v;
-                }
+        EXPECT_NUMEL((int64_t)C0 * 48);
+        const std::vector<float> w2 = stem_weight_hilo(data, C0, 16, CNX_STEM_KH, true);      // BGR; the hi | lo halves of cnx_stem_kernel
         st = upload_matrix16(h->stem_w, w2.data(), C0, CNX_STEM_K, round_up(C0, 256), f16);
-    } else if (key == "patch_embed.proj.bias") { EXPECT(C0); st = sw_upload_f32(h->stem_b, data, C0); }
-    else if (key == "patch_embed.norm.weight") { EXPECT(C0); st = sw_upload_f32(h->stem_nw, data, C0); }
-    else if (key == "patch_embed.norm.bias") { EXPECT(C0); st = sw_upload_f32(h->stem_nb, data, C0); }
-    else if (key == "norm.weight") { EXPECT(C3); st = sw_upload_f32(h->head_nw, data, C3); }
-    else if (key == "norm.bias") { EXPECT(C3); st = sw_upload_f32(h->head_nb, data, C3); }
-    else if (key == "head.fc.bias") { EXPECT(NC); st = sw_upload_f32(h->head_b, data, NC); }
+    } else if (key == "patch_embed.proj.bias") { EXPECT_NUMEL(C0); st = upload_f32(h->stem_b, data, C0); }
+    else if (key == "patch_embed.norm.weight") { EXPECT_NUMEL(C0); st = upload_f32(h->stem_nw, data, C0); }
+    else if (key == "patch_embed.norm.bias") { EXPECT_NUMEL(C0); st = upload_f32(h->stem_nb, data, C0); }
+    else if (key == "norm.weight") { EXPECT_NUMEL(C3); st = upload_f32(h->head_nw, data, C3); }
+    else if (key == "norm.bias") { EXPECT_NUMEL(C3); st = upload_f32(h->head_nb, data, C3); }
+    else if (key == "head.fc.bias") { EXPECT_NUMEL(NC); st = upload_f32(h->head_b, data, NC); }
     else if (key == "head.fc.weight") {
-        EXPECT((int64_t)NC * C3);
-        std::vector<float> dup((size_t)NC * 2 * C3);
-        for (int n = 0; n < NC; ++n)
-            for (int k = 0; k < C3; ++k) dup[(size_t)n * 2 * C3 + k] = dup[(size_t)n * 2 * C3 + C3 + k] = data[(size_t)n * C3 + k];
-        st = upload_matrix16(h->head_w, dup.data(), NC, 2 * C3, round_up(NC, 256), f16);
-    } else if (key.rfind("layers.", 0) == 0) {
-        const size_t d1 = key.find('.', 7);
-        if (d1 == std::string::npos) return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-        const int s = atoi(key.substr(7, d1 - 7).c_str());
+        EXPECT_NUMEL((int64_t)NC * C3);
+        st = upload_matrix16_dup(h->head_w, data, NC, C3, round_up(NC, 256), f16);
+    } else if (parse_indexed(key, "layers.", &s, &sub)) {
         if (s < 0 || s > 3) return set_error(HIPTS_ERR_INVALID, "tensor %s: stage out of range", key_c);
         SwStage& St = h->st[s];
         const int C = St.C;
-        const std::string sub = key.substr(d1 + 1);
         if (sub.rfind("downsample.", 0) == 0) {
             if (s == 0) return set_error(HIPTS_ERR_INVALID, "tensor %s: stage 0 has no downsample", key_c);
             const int Cp = cf.dims[s - 1];
-            if (sub == "downsample.norm.weight") { EXPECT(C); st = sw_upload_f32(St.ds_nw, data, C); }
-            else if (sub == "downsample.norm.bias") { EXPECT(C); st = sw_upload_f32(St.ds_nb, data, C); }
+            if (sub == "downsample.norm.weight") { EXPECT_NUMEL(C); st = upload_f32(St.ds_nw, data, C); }
+            else if (sub == "downsample.norm.bias") { EXPECT_NUMEL(C); st = upload_f32(St.ds_nb, data, C); }
             else if (sub == "downsample.reduction.weight") {
-                EXPECT((int64_t)C * 4 * Cp);            // columns in timm's (dx, dy, c) order: the order sw_merge_kernel writes; [W | W]
-                std::vector<float> dup((size_t)C * 8 * Cp);
-                for (int n = 0; n < C; ++n)
-                    for (int k = 0; k < 4 * Cp; ++k) dup[(size_t)n * 8 * Cp + k] = dup[(size_t)n * 8 * Cp + 4 * Cp + k] = data[(size_t)n * 4 * Cp + k];
-                st = upload_matrix16(St.ds_w, dup.data(), C, 8 * Cp, round_up(C, 256), f16);
+                EXPECT_NUMEL((int64_t)C * 4 * Cp);            // columns in timm's (dx, dy, c) order: the order sw_merge_kernel writes; [W | W]
+                st = upload_matrix16_dup(St.ds_w, data, C, 4 * Cp, round_up(C, 256), f16);
             } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-        } else if (sub.rfind("blocks.", 0) == 0) {
-            const size_t d2 = sub.find('.', 7);
-            if (d2 == std::string::npos) return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-            const int bi = atoi(sub.substr(7, d2 - 7).c_str());
+        } else if (parse_indexed(sub, "blocks.", &bi, &t)) {
             if (bi < 0 || bi >= (int)St.blocks.size()) return set_error(HIPTS_ERR_INVALID, "tensor %s: block out of range", key_c);
             SwBlock& B = St.blocks[bi];
-            const std::string t = sub.substr(d2 + 1);
             const int nh = St.heads;
             if (t == "attn.qkv.weight") {
-                EXPECT((int64_t)3 * C * C);
-                std::vector<float> dup((size_t)3 * C * 2 * C);       // against [hi | lo] of x: [W | W]
-                for (int n = 0; n < 3 * C; ++n)
-                    for (int k = 0; k < C; ++k) dup[(size_t)n * 2 * C + k] = dup[(size_t)n * 2 * C + C + k] = data[(size_t)n * C + k];
-                st = upload_matrix16(B.qkv2, dup.data(), 3 * C, 2 * C, round_up(3 * C, 256), f16);
+                EXPECT_NUMEL((int64_t)3 * C * C);
+                st = upload_matrix16_dup(B.qkv2, data, 3 * C, C, round_up(3 * C, 256), f16);       // against [hi | lo] of x: [W | W]
             }
             else if (t == "attn.q_bias" || t == "attn.v_bias") {
-                EXPECT(C);
+                EXPECT_NUMEL(C);
                 if (B.qkv_bh.empty()) B.qkv_bh.assign((size_t)3 * C, 0.f);        // [q_bias | 0 | v_bias]: timm's k bias is a zero buffer
                 std::copy(data, data + C, B.qkv_bh.begin() + (t == "attn.q_bias" ? 0 : 2 * C));
-                st = sw_upload_f32(B.qkv_b, B.qkv_bh.data(), B.qkv_bh.size());
+                st = upload_f32(B.qkv_b, B.qkv_bh.data(), B.qkv_bh.size());
             }
-            else if (t == "attn.logit_scale") { EXPECT(nh); st = sw_upload_f32(B.ls, data, nh); }
-            else if (t == "attn.cpb_mlp.0.weight") { EXPECT(2 * SW_CPB_HIDDEN); B.cpb_w1.assign(data, data + 2 * SW_CPB_HIDDEN); h->cpb_ready = false; }
-            else if (t == "attn.cpb_mlp.0.bias") { EXPECT(SW_CPB_HIDDEN); B.cpb_b1.assign(data, data + SW_CPB_HIDDEN); h->cpb_ready = false; }
+            else if (t == "attn.logit_scale") { EXPECT_NUMEL(nh); st = upload_f32(B.ls, data, nh); }
+            else if (t == "attn.cpb_mlp.0.weight") { EXPECT_NUMEL(2 * SW_CPB_HIDDEN); B.cpb_w1.assign(data, data + 2 * SW_CPB_HIDDEN); h->cpb_ready = false; }
+            else if (t == "attn.cpb_mlp.0.bias") { EXPECT_NUMEL(SW_CPB_HIDDEN); B.cpb_b1.assign(data, data + SW_CPB_HIDDEN); h->cpb_ready = false; }
             else if (t == "attn.cpb_mlp.2.weight") {
-                EXPECT((int64_t)nh * SW_CPB_HIDDEN);
+                EXPECT_NUMEL((int64_t)nh * SW_CPB_HIDDEN);
                 B.cpb_w2.assign(data, data + (size_t)nh * SW_CPB_HIDDEN);
                 h->cpb_ready = false;
             }
-            else if (t == "attn.proj.weight") { EXPECT((int64_t)C * C); st = upload_matrix16(B.proj, data, C, C, round_up(C, 256), f16); }
-            else if (t == "attn.proj.bias") { EXPECT(C); st = sw_upload_f32(B.proj_b, data, C); }
-            else if (t == "norm1.weight") { EXPECT(C); st = sw_upload_f32(B.n1_w, data, C); }
-            else if (t == "norm1.bias") { EXPECT(C); st = sw_upload_f32(B.n1_b, data, C); }
-            else if (t == "norm2.weight") { EXPECT(C); st = sw_upload_f32(B.n2_w, data, C); }
-            else if (t == "norm2.bias") { EXPECT(C); st = sw_upload_f32(B.n2_b, data, C); }
+            else if (t == "attn.proj.weight") { EXPECT_NUMEL((int64_t)C * C); st = upload_matrix16(B.proj, data, C, C, round_up(C, 256), f16); }
+            else if (t == "attn.proj.bias") { EXPECT_NUMEL(C); st = upload_f32(B.proj_b, data, C); }
+            else if (t == "norm1.weight") { EXPECT_NUMEL(C); st = upload_f32(B.n1_w, data, C); }
+            else if (t == "norm1.bias") { EXPECT_NUMEL(C); st = upload_f32(B.n1_b, data, C); }
+            else if (t == "norm2.weight") { EXPECT_NUMEL(C); st = upload_f32(B.n2_w, data, C); }
+            else if (t == "norm2.bias") { EXPECT_NUMEL(C); st = upload_f32(B.n2_b, data, C); }
             else if (t == "mlp.fc1.weight") {
-                EXPECT((int64_t)St.hid * C);
-                std::vector<float> dup((size_t)St.hid * 2 * C);      // against [hi | lo] of x: [W | W]
-                for (int n = 0; n < St.hid; ++n)
-                    for (int k = 0; k < C; ++k) dup[(size_t)n * 2 * C + k] = dup[(size_t)n * 2 * C + C + k] = data[(size_t)n * C + k];
-                st = upload_matrix16(B.fc1, dup.data(), St.hid, 2 * C, round_up(St.hid, 256), f16);
+                EXPECT_NUMEL((int64_t)St.hid * C);
+                st = upload_matrix16_dup(B.fc1, data, St.hid, C, round_up(St.hid, 256), f16);      // against [hi | lo] of x: [W | W]
             }
-            else if (t == "mlp.fc1.bias") { EXPECT(St.hid); st = sw_upload_f32(B.fc1_b, data, St.hid); }
-            else if (t == "mlp.fc2.weight") { EXPECT((int64_t)St.hid * C); st = upload_matrix16(B.fc2, data, C, St.hid, round_up(C, 256), f16); }
-            else if (t == "mlp.fc2.bias") { EXPECT(C); st = sw_upload_f32(B.fc2_b, data, C); }
+            else if (t == "mlp.fc1.bias") { EXPECT_NUMEL(St.hid); st = upload_f32(B.fc1_b, data, St.hid); }
+            else if (t == "mlp.fc2.weight") { EXPECT_NUMEL((int64_t)St.hid * C); st = upload_matrix16(B.fc2, data, C, St.hid, round_up(C, 256), f16); }
+            else if (t == "mlp.fc2.bias") { EXPECT_NUMEL(C); st = upload_f32(B.fc2_b, data, C); }
             else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
         } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
     } else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
-#undef EXPECT
     if (st) return st;
-    auto it = std::find(h->missing.begin(), h->missing.end(), key);
-    if (it != h->missing.end()) h->missing.erase(it);
+    h->ledger.mark_set(key);
     return HIPTS_OK;
 }
 
@@ -678,16 +578,19 @@ int hiptsdbg_swinv2_window_attention(const float* q, const float* k, const float
         std::copy(v + m * C, v + (m + 1) * C, packed.begin() + m * 3 * C + 2 * C);
     }
     DevBuf dqkv, dls, dcpb, dout;
-    HIPTS_TRY(sw_upload_f32(dqkv, packed.data(), packed.size()));
-    HIPTS_TRY(sw_upload_f32(dls, logit_scale, heads));
-    HIPTS_TRY(sw_upload_f32(dcpb, cpb, (size_t)heads * nb));
+    HIPTS_TRY(upload_f32(dqkv, packed.data(), packed.size()));
+    HIPTS_TRY(upload_f32(dls, logit_scale, heads));
+    HIPTS_TRY(upload_f32(dcpb, cpb, (size_t)heads * nb));
     HIPTS_TRY(dout.alloc(M * C * 2));
     HIPTS_TRY(launch_swin_attention(dqkv.as<float>(), dls.as<float>(), dcpb.as<float>(), dout.as<bf16_t>(), batch, side, window, shift, heads,
                                     operand_f16 == 1, nullptr));
     HIPTS_HIP(hipDeviceSynchronize());
     std::vector<uint16_t> o16(M * C);
     HIPTS_HIP(hipMemcpy(o16.data(), dout.p, M * C * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < M * C; ++i) out[i] = half_bits_to_f32(o16[i], operand_f16 == 1);
+    for (size_t i = 0; i < M * C; ++i) {
+        if (operand_f16 == 1) out[i] = f16_bits_to_f32(o16[i]);
+        else { const uint32_t bits = (uint32_t)o16[i] << 16; memcpy(&out[i], &bits, 4); }
+    }
     return HIPTS_OK;
 }
 

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "vit_internal.h"
+#include "model_host.h"
 
 using namespace hipts;
 
@@ -61,7 +62,7 @@ struct hipts_vit {
     std::vector<Layer> layers;
     DevBuf patch_w, patch_w2, patch_b, patch_b_u8, pos, norm_g, norm_b, head_w, head_b;
     std::vector<float> h_patch_bias, h_patch_rowsum;   // bias and sum_k W[n][k] (of the bf16 values)
-    std::vector<std::string> missing;   // tensors not yet set
+    TensorLedger ledger;                // tensors not yet set
     // workspace (sized for cfg.max_batch)
     DevBuf img_in, a0, x, xn, q, k, v, att, hmid, pool_part, pooled2, logits, probs, stat_part;
     DevBuf x_rm;                   // the last residual launch's rows, row-major, when the stream itself is blocked (GemmArgs::x_blocked)
@@ -75,8 +76,7 @@ struct hipts_vit {
     bool deferred_join = false;                   // hipts_vit_set_deferred_join
     int last_ns = 0;                              // sub-batch streams the last forward used (0: none to join)
     int pend_ns = 0, pend_batch = 0;              // an UNJOINED forward (deferred join) of pend_batch images on pend_ns streams may still run
-    hipStream_t sub[kMaxSub] = {};                // internal streams of the sub-batches
-    hipEvent_t ev_fork = nullptr, ev_join[kMaxSub] = {};
+    SubStreams<kMaxSub> streams;                  // owned here; this forward creates them piece by piece (its own fork / join loop below)
     hipEvent_t ev_stagger = nullptr;              // HIPTS_VIT_STAGGER: recorded on sub-batch stream 0 after a chosen launch, waited for by the later streams
 };
 
@@ -358,30 +358,6 @@ __global__ __launch_bounds__(256) void pool_finalize_kernel(const float* __restr
     }
 }
 
-int set_f32(DevBuf& buf, const float* data, size_t n) {
-    HIPTS_TRY(buf.alloc(n * 4));
-    return upload(buf.p, data, n * 4);
-}
-
-// rows x cols float32 -> bf16 (or half), rows zero-padded to rows_pad
-bool g_upload_f16 = false;      // set from the handle around hipts_vit_set_tensor (single caller per handle)
-int set_bf16_matrix(DevBuf& buf, const float* data, int rows, int cols, int rows_pad) {
-    std::vector<uint16_t> h((size_t)rows_pad * cols, 0);
-    if (g_upload_f16) for (size_t i = 0; i < (size_t)rows * cols; ++i) h[i] = f32_to_f16_rne(data[i]);
-    else for (size_t i = 0; i < (size_t)rows * cols; ++i) h[i] = f32_to_bf16_rne(data[i]);
-    HIPTS_TRY(buf.alloc(h.size() * 2));
-    return upload(buf.p, h.data(), h.size() * 2);
-}
-
-bool erase_missing(hipts_vit* h, const std::string& key) {
-    for (size_t i = 0; i < h->missing.size(); ++i)
-        if (h->missing[i] == key) {
-            h->missing.erase(h->missing.begin() + i);
-            return true;
-        }
-    return false;
-}
-
 }  // namespace
 
 extern "C" {
@@ -406,14 +382,14 @@ int hipts_vit_create(const hipts_vit_config_t* cfg, int device, hipts_vit_t** ou
     h->patch_k = cfg->patch * cfg->patch * 3;
     h->split_att = (cfg->operand_f16 & HIPTS_OPERAND_SPLIT_ATT) != 0;
     h->layers.resize(cfg->depth);
-    h->missing = {"patch_embed.proj.weight", "patch_embed.proj.bias", "pos_embed", "norm.weight", "norm.bias",
-                  "head.weight", "head.bias"};
+    for (const char* s : {"patch_embed.proj.weight", "patch_embed.proj.bias", "pos_embed", "norm.weight", "norm.bias", "head.weight", "head.bias"})
+        h->ledger.need(s);
     for (int i = 0; i < cfg->depth; ++i) {
         const std::string p = "blocks." + std::to_string(i) + ".";
         for (const char* s : {"norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight",
                               "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias",
                               "mlp.fc2.weight", "mlp.fc2.bias"})
-            h->missing.push_back(p + s);
+            h->ledger.need(p + s);
     }
     const size_t B = cfg->max_batch, M = B * h->tokens, D = cfg->dim;
     const size_t qkv_elems = B * cfg->heads * (size_t)h->tokens_pad * 64;
@@ -467,11 +443,6 @@ int hipts_vit_destroy(hipts_vit_t* h) {
     if (h) {
         (void)hipSetDevice(h->device);
         (void)hipDeviceSynchronize();
-        for (auto st : h->sub)
-            if (st) (void)hipStreamDestroy(st);
-        for (auto e : h->ev_join)
-            if (e) (void)hipEventDestroy(e);
-        if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
         if (h->ev_stagger) (void)hipEventDestroy(h->ev_stagger);
         delete h;
     }
@@ -481,14 +452,15 @@ int hipts_vit_destroy(hipts_vit_t* h) {
 int hipts_vit_set_tensor(hipts_vit_t* h, const char* key_c, const float* data, int64_t numel) {
     HIPTS_REQUIRE(h && key_c && data, "hipts_vit_set_tensor: null argument");
     HIPTS_TRY(use_device(h->device));
-    g_upload_f16 = (h->cfg.operand_f16 & 1) != 0;
+    const bool f16 = (h->cfg.operand_f16 & 1) != 0;
     const std::string key(key_c);
     const auto& c = h->cfg;
     const int D = c.dim, P = c.patch, Mlp = c.mlp_dim, C = c.num_classes;
 #define EXPECT(n)                                                                                                      \
     HIPTS_REQUIRE(numel == (int64_t)(n), "tensor %s: expected %lld elements, got %lld", key_c, (long long)(n),         \
                   (long long)numel)
-    int st = HIPTS_ERR_INVALID;
+    int st = HIPTS_ERR_INVALID, li = 0;
+    std::string sub;
     if (key == "patch_embed.proj.weight") {
         EXPECT((int64_t)D * 3 * P * P);
         // [D][3][P][P] (model channel order = BGR) -> [D][(ky*P + kx)*3 + c_rgb], model channel 2 - c_rgb
@@ -498,15 +470,14 @@ int hipts_vit_set_tensor(hipts_vit_t* h, const char* key_c, const float* data, i
                 for (int kx = 0; kx < P; ++kx)
                     for (int cr = 0; cr < 3; ++cr)
                         perm[(size_t)n * h->patch_k + (ky * P + kx) * 3 + cr] = data[(((size_t)n * 3 + (2 - cr)) * P + ky) * P + kx];
-        st = set_bf16_matrix(h->patch_w, perm.data(), D, h->patch_k, round_up(D, 256));
+        st = upload_matrix16(h->patch_w, perm.data(), D, h->patch_k, round_up(D, 256), f16);
         if (st == HIPTS_OK) {
-            std::vector<float> dup((size_t)D * 2 * h->patch_k);
             h->h_patch_rowsum.assign(D, 0.f);
             for (int n = 0; n < D; ++n) {
                 double rs = 0.0;
                 for (int kk = 0; kk < h->patch_k; ++kk) {
                     float wv;
-                    if (g_upload_f16) {
+                    if (f16) {
                         wv = f16_bits_to_f32(f32_to_f16_rne(perm[(size_t)n * h->patch_k + kk]));
                     } else {
                         const uint32_t bits = (uint32_t)f32_to_bf16_rne(perm[(size_t)n * h->patch_k + kk]) << 16;
@@ -515,80 +486,63 @@ int hipts_vit_set_tensor(hipts_vit_t* h, const char* key_c, const float* data, i
                     rs += (double)wv;
                 }
                 h->h_patch_rowsum[n] = (float)rs;
-                memcpy(&dup[(size_t)n * 2 * h->patch_k], &perm[(size_t)n * h->patch_k], (size_t)h->patch_k * 4);
-                memcpy(&dup[(size_t)n * 2 * h->patch_k + h->patch_k], &perm[(size_t)n * h->patch_k], (size_t)h->patch_k * 4);
             }
-            st = set_bf16_matrix(h->patch_w2, dup.data(), D, 2 * h->patch_k, round_up(D, 256));
+            st = upload_matrix16_dup(h->patch_w2, perm.data(), D, h->patch_k, round_up(D, 256), f16);
         }
     } else if (key == "patch_embed.proj.bias") {
         EXPECT(D);
         h->h_patch_bias.assign(data, data + D);
-        st = set_f32(h->patch_b, data, D);
+        st = upload_f32(h->patch_b, data, D);
     } else if (key == "pos_embed") {
         EXPECT((int64_t)h->tokens * D);
-        st = set_f32(h->pos, data, (size_t)h->tokens * D);
+        st = upload_f32(h->pos, data, (size_t)h->tokens * D);
     } else if (key == "norm.weight") {
         EXPECT(D);
-        st = set_f32(h->norm_g, data, D);
+        st = upload_f32(h->norm_g, data, D);
     } else if (key == "norm.bias") {
         EXPECT(D);
-        st = set_f32(h->norm_b, data, D);
+        st = upload_f32(h->norm_b, data, D);
     } else if (key == "head.weight") {
         EXPECT((int64_t)C * D);
         // [C][D] -> [C][2D] = [W | W]: multiplies the (hi | lo) split of the pooled feature
-        std::vector<float> dup((size_t)C * 2 * D);
-        for (int n = 0; n < C; ++n) {
-            memcpy(&dup[(size_t)n * 2 * D], &data[(size_t)n * D], (size_t)D * 4);
-            memcpy(&dup[(size_t)n * 2 * D + D], &data[(size_t)n * D], (size_t)D * 4);
-        }
-        st = set_bf16_matrix(h->head_w, dup.data(), C, 2 * D, round_up(C, 256));
+        st = upload_matrix16_dup(h->head_w, data, C, D, round_up(C, 256), f16);
     } else if (key == "head.bias") {
         EXPECT(C);
-        st = set_f32(h->head_b, data, C);
-    } else if (key.rfind("blocks.", 0) == 0) {
-        const size_t dot = key.find('.', 7);
-        HIPTS_REQUIRE(dot != std::string::npos, "unknown tensor key %s", key_c);
-        const int li = atoi(key.substr(7, dot - 7).c_str());
+        st = upload_f32(h->head_b, data, C);
+    } else if (parse_indexed(key, "blocks.", &li, &sub)) {
         HIPTS_REQUIRE(li >= 0 && li < c.depth, "tensor %s: block index out of range", key_c);
         Layer& L = h->layers[li];
-        const std::string sub = key.substr(dot + 1);
-        if (sub == "norm1.weight") { EXPECT(D); st = set_f32(L.ln1_g, data, D); }
-        else if (sub == "norm1.bias") { EXPECT(D); st = set_f32(L.ln1_b, data, D); }
-        else if (sub == "norm2.weight") { EXPECT(D); st = set_f32(L.ln2_g, data, D); }
-        else if (sub == "norm2.bias") { EXPECT(D); st = set_f32(L.ln2_b, data, D); }
-        else if (sub == "attn.qkv.weight") { EXPECT((int64_t)3 * D * D); st = set_bf16_matrix(L.qkv_w, data, 3 * D, D, round_up(2 * D, 256) + round_up(D, 256) + 256); }
-        else if (sub == "attn.qkv.bias") { EXPECT(3 * D); st = set_f32(L.qkv_b, data, 3 * D); }
+        if (sub == "norm1.weight") { EXPECT(D); st = upload_f32(L.ln1_g, data, D); }
+        else if (sub == "norm1.bias") { EXPECT(D); st = upload_f32(L.ln1_b, data, D); }
+        else if (sub == "norm2.weight") { EXPECT(D); st = upload_f32(L.ln2_g, data, D); }
+        else if (sub == "norm2.bias") { EXPECT(D); st = upload_f32(L.ln2_b, data, D); }
+        else if (sub == "attn.qkv.weight") { EXPECT((int64_t)3 * D * D); st = upload_matrix16(L.qkv_w, data, 3 * D, D, round_up(2 * D, 256) + round_up(D, 256) + 256, f16); }
+        else if (sub == "attn.qkv.bias") { EXPECT(3 * D); st = upload_f32(L.qkv_b, data, 3 * D); }
         else if (sub == "attn.proj.weight") {
             EXPECT((int64_t)D * D);
             if (h->split_att) {      // [D][2D] = [W | W]: multiplies the (hi | lo) halves of the attention output
-                std::vector<float> dup((size_t)D * 2 * D);
-                const float inv = 1.0f / split_lo_scale(g_upload_f16);      // the low halves arrive multiplied by the scale
-                for (int n = 0; n < D; ++n) {
-                    memcpy(&dup[(size_t)n * 2 * D], &data[(size_t)n * D], (size_t)D * 4);
-                    for (int kk = 0; kk < D; ++kk) dup[(size_t)n * 2 * D + D + kk] = data[(size_t)n * D + kk] * inv;
-                }
-                st = set_bf16_matrix(L.proj_w, dup.data(), D, 2 * D, round_up(D, 256));
+                st = upload_matrix16_dup(L.proj_w, data, D, D, round_up(D, 256), f16, split_lo_scale(f16));      // the low halves arrive multiplied by the scale
             } else {
-                st = set_bf16_matrix(L.proj_w, data, D, D, round_up(D, 256));
+                st = upload_matrix16(L.proj_w, data, D, D, round_up(D, 256), f16);
             }
         }
-        else if (sub == "attn.proj.bias") { EXPECT(D); st = set_f32(L.proj_b, data, D); }
-        else if (sub == "mlp.fc1.weight") { EXPECT((int64_t)Mlp * D); st = set_bf16_matrix(L.fc1_w, data, Mlp, D, round_up(Mlp, 256)); }
-        else if (sub == "mlp.fc1.bias") { EXPECT(Mlp); st = set_f32(L.fc1_b, data, Mlp); }
-        else if (sub == "mlp.fc2.weight") { EXPECT((int64_t)D * Mlp); st = set_bf16_matrix(L.fc2_w, data, D, Mlp, round_up(D, 256)); }
-        else if (sub == "mlp.fc2.bias") { EXPECT(D); st = set_f32(L.fc2_b, data, D); }
+        else if (sub == "attn.proj.bias") { EXPECT(D); st = upload_f32(L.proj_b, data, D); }
+        else if (sub == "mlp.fc1.weight") { EXPECT((int64_t)Mlp * D); st = upload_matrix16(L.fc1_w, data, Mlp, D, round_up(Mlp, 256), f16); }
+        else if (sub == "mlp.fc1.bias") { EXPECT(Mlp); st = upload_f32(L.fc1_b, data, Mlp); }
+        else if (sub == "mlp.fc2.weight") { EXPECT((int64_t)D * Mlp); st = upload_matrix16(L.fc2_w, data, D, Mlp, round_up(D, 256), f16); }
+        else if (sub == "mlp.fc2.bias") { EXPECT(D); st = upload_f32(L.fc2_b, data, D); }
         else return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
     } else {
         return set_error(HIPTS_ERR_INVALID, "unknown tensor key %s", key_c);
     }
 #undef EXPECT
-    if (st == HIPTS_OK) erase_missing(h, key);
+    if (st == HIPTS_OK) h->ledger.mark_set(key);
     if (st == HIPTS_OK) h->fold_dirty = true;
     if (st == HIPTS_OK && (key == "patch_embed.proj.weight" || key == "patch_embed.proj.bias") &&
         !h->h_patch_bias.empty() && !h->h_patch_rowsum.empty()) {
         std::vector<float> eff(D);
         for (int n = 0; n < D; ++n) eff[n] = (float)((double)h->h_patch_bias[n] - (double)h->h_patch_rowsum[n]);
-        st = set_f32(h->patch_b_u8, eff.data(), D);   // bias of the u8 path: b - rowsum(W)
+        st = upload_f32(h->patch_b_u8, eff.data(), D);   // bias of the u8 path: b - rowsum(W)
     }
     return st;
 }
@@ -747,9 +701,7 @@ int vit_run_images(hipts_vit* h, const void* in_dev, bool is_u8, int i0, int nb,
     };
     auto layernorm = [&](const float* gamma, const float* beta) -> int {
         ProfScope ps(h, s, PC_LAYERNORM, 0.0, dM * dD * 6);
-        if (f16) layernorm_kernel<true><<<ln_blocks, 256, 0, s>>>(x, gamma, beta, xn, M, D, c.ln_eps);
-        else layernorm_kernel<false><<<ln_blocks, 256, 0, s>>>(x, gamma, beta, xn, M, D, c.ln_eps);
-        HIPTS_LAUNCH_CHECK();
+        HIPTS_LAUNCH_F16(f16, layernorm_kernel, ln_blocks, 256, 0, s, x, gamma, beta, xn, M, D, c.ln_eps);
         return HIPTS_OK;
     };
     // x += A W^T + b; with next_gamma also xn = 16bit(gamma * x) and the row statistics of x for the consumer of that norm
@@ -855,9 +807,7 @@ int vit_forward_impl(hipts_vit* h, const void* input, int in_memspace, bool is_u
                      float* probs_out, int out_memspace, hipStream_t s) {
     HIPTS_REQUIRE(h && input && batch >= 1, "hipts_vit_forward: bad arguments");
     HIPTS_REQUIRE(batch <= h->cfg.max_batch, "batch %d exceeds max_batch %d", batch, h->cfg.max_batch);
-    if (!h->missing.empty())
-        return set_error(HIPTS_ERR_STATE, "hipts_vit_forward: %zu checkpoint tensors not set (first: %s)", h->missing.size(),
-                         h->missing[0].c_str());
+    HIPTS_TRY(h->ledger.require_complete("hipts_vit_forward"));
     HIPTS_TRY(use_device(h->device));
     h->prof = h->prof_every > 0 && (h->prof_calls++ % h->prof_every) == 0;
     const auto& c = h->cfg;
@@ -871,17 +821,13 @@ int vit_forward_impl(hipts_vit* h, const void* input, int in_memspace, bool is_u
     // ordered against this one only stream by stream, which is enough exactly when sub-batch i covers the same images as
     // before and nothing is staged through the shared input buffer; otherwise this call waits for all of it first.
     if (h->pend_ns > 0 && (h->pend_ns != ns || h->pend_batch != batch || in_memspace != HIPTS_DEVICE))
-        for (int i = 0; i < h->pend_ns; ++i) HIPTS_HIP(hipStreamWaitEvent(s, h->ev_join[i], 0));
+        for (int i = 0; i < h->pend_ns; ++i) HIPTS_HIP(hipStreamWaitEvent(s, h->streams.ev_join[i], 0));
     h->pend_ns = 0;
 
-    const void* in_dev = input;
-    if (in_memspace != HIPTS_DEVICE) {
-        const size_t bytes = (size_t)batch * S * S * 3 * (is_u8 ? 1 : 4);
-        HIPTS_TRY(h->img_in.reserve(bytes));
-        HIPTS_HIP(hipMemcpyAsync(h->img_in.p, input, bytes, hipMemcpyHostToDevice, s));
-        in_dev = h->img_in.p;
-    }
+    const void* in_dev = nullptr;
+    HIPTS_TRY(stage_input(h->img_in, input, in_memspace, (size_t)batch * S * S * 3 * (is_u8 ? 1 : 4), s, &in_dev));
     const bool dev_out = out_memspace == HIPTS_DEVICE;
+    // deliberate: logits are always computed, into the handle's own buffer when the caller passes none (ConvNeXt / SwinV2 pass null on)
     float* lg = (dev_out && logits_out) ? logits_out : h->logits.as<float>();
     float* pr = (probs_out || !dev_out) ? ((dev_out && probs_out) ? probs_out : h->probs.as<float>()) : nullptr;
     if (h->fold_ln && h->fold_dirty) {
@@ -896,22 +842,22 @@ int vit_forward_impl(hipts_vit* h, const void* input, int in_memspace, bool is_u
     }
 
     if (ns >= 2) {
-        if (!h->ev_fork) HIPTS_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+        if (!h->streams.ev_fork) HIPTS_HIP(hipEventCreateWithFlags(&h->streams.ev_fork, hipEventDisableTiming));
         for (int i = 0; i < ns; ++i)
-            if (!h->sub[i]) {
-                HIPTS_HIP(hipStreamCreateWithFlags(&h->sub[i], hipStreamNonBlocking));
-                if (!h->ev_join[i]) HIPTS_HIP(hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming));
+            if (!h->streams.sub[i]) {
+                HIPTS_HIP(hipStreamCreateWithFlags(&h->streams.sub[i], hipStreamNonBlocking));
+                if (!h->streams.ev_join[i]) HIPTS_HIP(hipEventCreateWithFlags(&h->streams.ev_join[i], hipEventDisableTiming));
             }
-        HIPTS_HIP(hipEventRecord(h->ev_fork, s));
+        HIPTS_HIP(hipEventRecord(h->streams.ev_fork, s));
         static const int stagger_at = getenv("HIPTS_VIT_STAGGER") ? atoi(getenv("HIPTS_VIT_STAGGER")) : 0;
         if (stagger_at > 0 && !h->ev_stagger) HIPTS_HIP(hipEventCreateWithFlags(&h->ev_stagger, hipEventDisableTiming));
         for (int i = 0; i < ns; ++i) {
             const int i0 = (int)((int64_t)batch * i / ns), i1 = (int)((int64_t)batch * (i + 1) / ns);
-            HIPTS_HIP(hipStreamWaitEvent(h->sub[i], h->ev_fork, 0));
-            if (i > 0 && stagger_at > 0) HIPTS_HIP(hipStreamWaitEvent(h->sub[i], h->ev_stagger, 0));
-            HIPTS_TRY(vit_run_images(h, in_dev, is_u8, i0, i1 - i0, lg, pr, h->sub[i], true, i == 0 ? stagger_at : 0, i));
-            HIPTS_HIP(hipEventRecord(h->ev_join[i], h->sub[i]));
-            if (!h->deferred_join || !dev_out) HIPTS_HIP(hipStreamWaitEvent(s, h->ev_join[i], 0));
+            HIPTS_HIP(hipStreamWaitEvent(h->streams.sub[i], h->streams.ev_fork, 0));
+            if (i > 0 && stagger_at > 0) HIPTS_HIP(hipStreamWaitEvent(h->streams.sub[i], h->ev_stagger, 0));
+            HIPTS_TRY(vit_run_images(h, in_dev, is_u8, i0, i1 - i0, lg, pr, h->streams.sub[i], true, i == 0 ? stagger_at : 0, i));
+            HIPTS_HIP(hipEventRecord(h->streams.ev_join[i], h->streams.sub[i]));
+            if (!h->deferred_join || !dev_out) HIPTS_HIP(hipStreamWaitEvent(s, h->streams.ev_join[i], 0));
         }
         h->last_ns = (h->deferred_join && dev_out) ? ns : 0;
         h->pend_ns = h->last_ns;
@@ -922,17 +868,12 @@ int vit_forward_impl(hipts_vit* h, const void* input, int in_memspace, bool is_u
         if (h->deferred_join && dev_out) {
             // one stream (small batch, HIPTS_VIT_STREAMS=1): the work sits on the caller's stream, but hipts_vit_join's contract is that
             // ANY consuming stream may join -- give it an event to wait for
-            if (!h->ev_join[0]) HIPTS_HIP(hipEventCreateWithFlags(&h->ev_join[0], hipEventDisableTiming));
-            HIPTS_HIP(hipEventRecord(h->ev_join[0], s));
+            if (!h->streams.ev_join[0]) HIPTS_HIP(hipEventCreateWithFlags(&h->streams.ev_join[0], hipEventDisableTiming));
+            HIPTS_HIP(hipEventRecord(h->streams.ev_join[0], s));
             h->last_ns = 1;
         }
     }
-    if (!dev_out) {
-        const size_t bytes = (size_t)batch * c.num_classes * 4;
-        if (logits_out) HIPTS_HIP(hipMemcpyAsync(logits_out, lg, bytes, hipMemcpyDeviceToHost, s));
-        if (probs_out) HIPTS_HIP(hipMemcpyAsync(probs_out, pr, bytes, hipMemcpyDeviceToHost, s));
-        HIPTS_HIP(hipStreamSynchronize(s));
-    }
+    if (!dev_out) HIPTS_TRY(read_back(s, (size_t)batch * c.num_classes * 4, logits_out, lg, probs_out, pr));
     return HIPTS_OK;
 }
 
@@ -1003,9 +944,7 @@ int launch_rowstat(const float* part, float* rowstat, int M, int stride, int blo
 
 int launch_fold_ln(const bf16_t* W, bool f16, const float* gamma, const float* beta, const float* bias, float* u, float* c, int N, int K,
                    hipStream_t s) {
-    if (f16) fold_ln_kernel<true><<<(N + 3) / 4, 256, 0, s>>>(W, gamma, beta, bias, u, c, N, K);
-    else fold_ln_kernel<false><<<(N + 3) / 4, 256, 0, s>>>(W, gamma, beta, bias, u, c, N, K);
-    HIPTS_LAUNCH_CHECK();
+    HIPTS_LAUNCH_F16(f16, fold_ln_kernel, (N + 3) / 4, 256, 0, s, W, gamma, beta, bias, u, c, N, K);
     return HIPTS_OK;
 }
 
@@ -1013,9 +952,7 @@ int launch_layernorm(const float* x, const float* g, const float* b, bf16_t* out
                      hipStream_t s) {
     HIPTS_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "layernorm: D=%d must be a multiple of 4, at most 1024", D);
     const int blocks = (int)((rows + 3) / 4);
-    if (f16) layernorm_kernel<true><<<blocks, 256, 0, s>>>(x, g, b, out, rows, D, eps);
-    else layernorm_kernel<false><<<blocks, 256, 0, s>>>(x, g, b, out, rows, D, eps);
-    HIPTS_LAUNCH_CHECK();
+    HIPTS_LAUNCH_F16(f16, layernorm_kernel, blocks, 256, 0, s, x, g, b, out, rows, D, eps);
     return HIPTS_OK;
 }
 
@@ -1046,7 +983,7 @@ int hipts_vit_set_deferred_join(hipts_vit_t* h, int on) {
 int hipts_vit_join(hipts_vit_t* h, void* stream) {
     HIPTS_REQUIRE(h, "null handle");
     HIPTS_TRY(use_device(h->device));
-    for (int i = 0; i < h->last_ns; ++i) HIPTS_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_join[i], 0));
+    for (int i = 0; i < h->last_ns; ++i) HIPTS_HIP(hipStreamWaitEvent((hipStream_t)stream, h->streams.ev_join[i], 0));
     return HIPTS_OK;
 }
 

@@ -174,7 +174,7 @@ def load():
         fn.argtypes = argtypes
         fn.restype = c_int
     lib.hipts_jpeg_slot_bytes.restype = ctypes.c_int64      # the one entry point that returns a size, not a status
-    # the three configuration structures are passed by pointer: a layout that differs from the library's would be read past
+    # the five configuration structures are passed by pointer: a layout that differs from the library's would be read past
     for kind, st in enumerate((VitConfig, EvaConfig, CcipConfig, ConvnextConfig, Swinv2Config)):
         n = c_size_t(0)
         if lib.hipts_sizeof_config(kind, ctypes.byref(n)) != 0 or n.value != ctypes.sizeof(st):

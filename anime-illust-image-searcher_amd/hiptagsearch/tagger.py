@@ -32,21 +32,39 @@ class ViTTagger:
     its subnormal range), activations keep 11 instead of 8 significant bits at the same matrix rate.  With bf16 activations the
     logit error against the float32 oracle is 4-6e-4 on noise images but ~4e-3 on flat / cel-shaded ones -- every token then carries
     the SAME rounding error, which the mean pool does not average out -- i.e. outside the 1e-3 of BASELINE.json on the images the
-    product is for (tests/test_gpu_vit.py::test_vit_default_config_structured_images).  cfg["operand_f16"] = 0 selects bf16."""
+    product is for (tests/test_gpu_vit.py::test_vit_default_config_structured_images).  cfg["operand_f16"] = 0 selects bf16.
+
+    Also the base of the other taggers: a subclass names its entry points (`_PREFIX`), builds its configuration structure (`_config`)
+    and tells Predictor.load_model what it needs to know about it (the three attributes below)."""
+
+    _PREFIX = "hipts_vit"               # <_PREFIX>_create / _set_tensor / _forward_u8 / _forward_f32 / _flops_per_image / _destroy
+    DISPLAY_NAME = "ViT"
+    PRECISE_REFUSAL: Optional[str] = None       # why Predictor(precise=True) does not apply to this model; None: it does
+    synth_weights = staticmethod(synth.vit_weights)
 
     def __init__(self, cfg: Dict, weights: Dict[str, np.ndarray], max_batch: int = 64, device: int = 0):
         self.cfg = dict(cfg)
         self.device = device
         self.max_batch = max_batch
         self.num_classes = cfg["num_classes"]
-        c = VitConfig(cfg["image_size"], cfg["patch"], cfg["dim"], cfg["depth"], cfg["heads"], cfg["mlp_dim"],
-                      cfg["num_classes"], cfg.get("ln_eps", 1e-6), cfg.get("gelu_tanh", 1), cfg.get("pool_then_norm", 0),
-                      max_batch, cfg.get("operand_f16", 1))
+        c = self._config(cfg, max_batch)
         self._h = c_void_p()
-        _lib.call("hipts_vit_create", ctypes.byref(c), device, ctypes.byref(self._h))
+        _lib.call(self._PREFIX + "_create", ctypes.byref(c), device, ctypes.byref(self._h))
         for key, val in weights.items():
+            if not self._loads(key):
+                continue
             arr = np.ascontiguousarray(val, dtype=np.float32)
-            _lib.call("hipts_vit_set_tensor", self._h, key.encode(), _lib.ptr(arr), ctypes.c_int64(arr.size))
+            _lib.call(self._PREFIX + "_set_tensor", self._h, key.encode(), _lib.ptr(arr), ctypes.c_int64(arr.size))
+
+    @staticmethod
+    def _config(cfg: Dict, max_batch: int):
+        return VitConfig(cfg["image_size"], cfg["patch"], cfg["dim"], cfg["depth"], cfg["heads"], cfg["mlp_dim"],
+                         cfg["num_classes"], cfg.get("ln_eps", 1e-6), cfg.get("gelu_tanh", 1), cfg.get("pool_then_norm", 0),
+                         max_batch, cfg.get("operand_f16", 1))
+
+    def _loads(self, key: str) -> bool:
+        """Whether the checkpoint entry `key` is a tensor of the model (every one, unless a subclass knows better)."""
+        return True
 
     @classmethod
     def from_safetensors(cls, path: str, cfg: Dict, **kw) -> "ViTTagger":
@@ -56,15 +74,15 @@ class ViTTagger:
 
     def flops_per_image(self) -> float:
         f = c_double()
-        _lib.call("hipts_vit_flops_per_image", self._h, ctypes.byref(f))
+        _lib.call(self._PREFIX + "_flops_per_image", self._h, ctypes.byref(f))
         return f.value
 
-    def _run(self, fn: str, x, batch: int, logits, probs):
+    def _run(self, entry: str, x, batch: int, logits, probs):
         out_space = _lib.HOST
         for o in (logits, probs):
             if o is not None:
                 out_space = _lib.memspace_of(o)
-        _lib.call(fn, self._h, _lib.ptr(x), _lib.memspace_of(x), batch, _lib.ptr(logits), _lib.ptr(probs), out_space,
+        _lib.call(self._PREFIX + entry, self._h, _lib.ptr(x), _lib.memspace_of(x), batch, _lib.ptr(logits), _lib.ptr(probs), out_space,
                   _lib.current_stream_ptr())
 
     def forward_u8(self, images, logits=None, probs=None, want: str = "both"):
@@ -77,7 +95,7 @@ class ViTTagger:
             probs = np.empty((B, self.num_classes), dtype=np.float32)
         if isinstance(images, np.ndarray):
             images = np.ascontiguousarray(images, dtype=np.uint8)
-        self._run("hipts_vit_forward_u8", images, B, logits, probs)
+        self._run("_forward_u8", images, B, logits, probs)
         return logits, probs
 
     def forward(self, x, logits=None, probs=None):
@@ -89,12 +107,12 @@ class ViTTagger:
             probs = np.empty((B, self.num_classes), dtype=np.float32)
         if isinstance(x, np.ndarray):
             x = np.ascontiguousarray(x, dtype=np.float32)
-        self._run("hipts_vit_forward_f32", x, B, logits, probs)
+        self._run("_forward_f32", x, B, logits, probs)
         return logits, probs
 
     def close(self):
-        if self._h:
-            _lib.call("hipts_vit_destroy", self._h)
+        if getattr(self, "_h", None):
+            _lib.call(self._PREFIX + "_destroy", self._h)
             self._h = c_void_p()
 
     def __del__(self):
@@ -111,32 +129,16 @@ class EvaTagger(ViTTagger):
     instead of 1.7e-2 on EVA02-L/14 (tests/test_gpu_eva.py); operand_f16 = 0 selects bf16."""
 
     _PREFIX = "hipts_eva"
+    DISPLAY_NAME = "EVA02"
+    synth_weights = staticmethod(synth.eva_weights)
 
     def __init__(self, cfg: Dict, weights: Dict[str, np.ndarray], max_batch: int = 32, device: int = 0):
-        self.cfg = dict(cfg)
-        self.device = device
-        self.max_batch = max_batch
-        self.num_classes = cfg["num_classes"]
-        c = _lib.EvaConfig(cfg["image_size"], cfg["patch"], cfg["dim"], cfg["depth"], cfg["heads"], cfg["mlp_hidden"], cfg["num_classes"],
-                           cfg.get("ln_eps", 1e-6), cfg.get("rope_ref_grid", 16), max_batch, cfg.get("operand_f16", 1))
-        self._h = c_void_p()
-        _lib.call("hipts_eva_create", ctypes.byref(c), device, ctypes.byref(self._h))
-        for key, val in weights.items():
-            arr = np.ascontiguousarray(val, dtype=np.float32)
-            _lib.call("hipts_eva_set_tensor", self._h, key.encode(), _lib.ptr(arr), ctypes.c_int64(arr.size))
+        super().__init__(cfg, weights, max_batch, device)
 
-    def flops_per_image(self) -> float:
-        f = c_double()
-        _lib.call("hipts_eva_flops_per_image", self._h, ctypes.byref(f))
-        return f.value
-
-    def _run(self, fn: str, x, batch: int, logits, probs):
-        super()._run(fn.replace("hipts_vit", "hipts_eva"), x, batch, logits, probs)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.call("hipts_eva_destroy", self._h)
-            self._h = c_void_p()
+    @staticmethod
+    def _config(cfg: Dict, max_batch: int):
+        return _lib.EvaConfig(cfg["image_size"], cfg["patch"], cfg["dim"], cfg["depth"], cfg["heads"], cfg["mlp_hidden"], cfg["num_classes"],
+                              cfg.get("ln_eps", 1e-6), cfg.get("rope_ref_grid", 16), max_batch, cfg.get("operand_f16", 1))
 
 
 class ConvNeXtTagger(ViTTagger):
@@ -144,11 +146,13 @@ class ConvNeXtTagger(ViTTagger):
     `weights` uses timm `ConvNeXt` state_dict keys.  cfg: image_size, dims, depths, num_classes, ln_eps, norm_mean / norm_std (the
     uint8 entry point's Normalize, RGB order) and operand_f16 (1 = IEEE half operands, the default; 0 = bf16)."""
 
-    def __init__(self, cfg: Dict, weights: Dict[str, np.ndarray], max_batch: int = 64, device: int = 0):
-        self.cfg = dict(cfg)
-        self.device = device
-        self.max_batch = max_batch
-        self.num_classes = cfg["num_classes"]
+    _PREFIX = "hipts_convnext"
+    DISPLAY_NAME = "ConvNeXt"
+    PRECISE_REFUSAL = "precise is an attention-output option (ViT, EVA02); the ConvNeXt tagger has no attention"
+    synth_weights = staticmethod(synth.convnext_weights)
+
+    @staticmethod
+    def _config(cfg: Dict, max_batch: int):
         c = _lib.ConvnextConfig()
         c.image_size = cfg["image_size"]
         c.dims[:] = list(cfg["dims"])
@@ -159,24 +163,7 @@ class ConvNeXtTagger(ViTTagger):
         c.norm_std[:] = list(cfg.get("norm_std", (0.5, 0.5, 0.5)))
         c.max_batch = max_batch
         c.operand_f16 = cfg.get("operand_f16", 1)
-        self._h = c_void_p()
-        _lib.call("hipts_convnext_create", ctypes.byref(c), device, ctypes.byref(self._h))
-        for key, val in weights.items():
-            arr = np.ascontiguousarray(val, dtype=np.float32)
-            _lib.call("hipts_convnext_set_tensor", self._h, key.encode(), _lib.ptr(arr), ctypes.c_int64(arr.size))
-
-    def flops_per_image(self) -> float:
-        f = c_double()
-        _lib.call("hipts_convnext_flops_per_image", self._h, ctypes.byref(f))
-        return f.value
-
-    def _run(self, fn: str, x, batch: int, logits, probs):
-        super()._run(fn.replace("hipts_vit", "hipts_convnext"), x, batch, logits, probs)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.call("hipts_convnext_destroy", self._h)
-            self._h = c_void_p()
+        return c
 
 
 class SwinV2Tagger(ViTTagger):
@@ -185,14 +172,18 @@ class SwinV2Tagger(ViTTagger):
     dims, depths, heads, mlp_ratio, num_classes, ln_eps, gelu_tanh, cpb_pretrained_window, norm_mean / norm_std (the uint8 entry
     point's Normalize, RGB order) and operand_f16 (1 = IEEE half operands, the default; 0 = bf16)."""
 
+    _PREFIX = "hipts_swinv2"
+    DISPLAY_NAME = "SwinV2"
+    PRECISE_REFUSAL = "precise is an attention-output option of the ViT and EVA02 taggers; the SwinV2 window attention has none"
+    synth_weights = staticmethod(synth.swinv2_weights)
     # timm's non-persistent buffers, which a checkpoint file may still hold: derived from the configuration, never loaded
     BUFFER_SUFFIXES = ("relative_position_index", "relative_coords_table", "attn_mask", "k_bias")
 
-    def __init__(self, cfg: Dict, weights: Dict[str, np.ndarray], max_batch: int = 64, device: int = 0):
-        self.cfg = dict(cfg)
-        self.device = device
-        self.max_batch = max_batch
-        self.num_classes = cfg["num_classes"]
+    def _loads(self, key: str) -> bool:
+        return not key.endswith(self.BUFFER_SUFFIXES)
+
+    @staticmethod
+    def _config(cfg: Dict, max_batch: int):
         c = _lib.Swinv2Config()
         c.image_size = cfg["image_size"]
         c.patch = cfg.get("patch", 4)
@@ -209,26 +200,7 @@ class SwinV2Tagger(ViTTagger):
         c.norm_std[:] = list(cfg.get("norm_std", (0.5, 0.5, 0.5)))
         c.max_batch = max_batch
         c.operand_f16 = cfg.get("operand_f16", 1)
-        self._h = c_void_p()
-        _lib.call("hipts_swinv2_create", ctypes.byref(c), device, ctypes.byref(self._h))
-        for key, val in weights.items():
-            if key.endswith(self.BUFFER_SUFFIXES):
-                continue
-            arr = np.ascontiguousarray(val, dtype=np.float32)
-            _lib.call("hipts_swinv2_set_tensor", self._h, key.encode(), _lib.ptr(arr), ctypes.c_int64(arr.size))
-
-    def flops_per_image(self) -> float:
-        f = c_double()
-        _lib.call("hipts_swinv2_flops_per_image", self._h, ctypes.byref(f))
-        return f.value
-
-    def _run(self, fn: str, x, batch: int, logits, probs):
-        super()._run(fn.replace("hipts_vit", "hipts_swinv2"), x, batch, logits, probs)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.call("hipts_swinv2_destroy", self._h)
-            self._h = c_void_p()
+        return c
 
 
 def model_class(cfg: Dict):
@@ -390,26 +362,16 @@ class Predictor:
         # an EVA02 configuration (the reference's MODEL_REPO, tagging.py:45) is recognised by its SwiGLU width, a ConvNeXt one by its
         # stage widths
         cls_ = model_class(self.cfg)
-        eva = cls_ is EvaTagger
         if self.precise:
-            if cls_ is ConvNeXtTagger:
-                raise ValueError("precise is an attention-output option (ViT, EVA02); the ConvNeXt tagger has no attention")
-            if cls_ is SwinV2Tagger:
-                raise ValueError("precise is an attention-output option of the ViT and EVA02 taggers; the SwinV2 window attention has none")
+            if cls_.PRECISE_REFUSAL:
+                raise ValueError(cls_.PRECISE_REFUSAL)
             self.cfg["operand_f16"] = int(self.cfg.get("operand_f16", 1)) | 16
         if checkpoint:
             self.tagger_model = cls_.from_safetensors(checkpoint, self.cfg, max_batch=self.max_batch, device=self.device)
         else:
-            name = {EvaTagger: "EVA02", ConvNeXtTagger: "ConvNeXt", SwinV2Tagger: "SwinV2"}.get(cls_, "ViT")
-            print("No checkpoint given: using the seeded synthetic %s weights (no network in this environment)." % name)
+            print("No checkpoint given: using the seeded synthetic %s weights (no network in this environment)." % cls_.DISPLAY_NAME)
             # the trained-like variant (peaked attention, sparse probabilities: tens of labels per image, as a real tagger selects)
-            if cls_ is ConvNeXtTagger:
-                weights = synth.convnext_weights(self.cfg, seed, trained_like=True)
-            elif cls_ is SwinV2Tagger:
-                weights = synth.swinv2_weights(self.cfg, seed, trained_like=True)
-            else:
-                weights = synth.eva_weights(self.cfg, seed, trained_like=True) if eva else synth.vit_weights(self.cfg, seed, trained_like=True)
-            self.tagger_model = cls_(self.cfg, weights, self.max_batch, self.device)
+            self.tagger_model = cls_(self.cfg, cls_.synth_weights(self.cfg, seed, trained_like=True), self.max_batch, self.device)
         if labels_csv:
             import pandas as pd
             df = pd.read_csv(labels_csv, usecols=["name", "category"])
