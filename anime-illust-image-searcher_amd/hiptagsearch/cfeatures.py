@@ -287,3 +287,152 @@ def cfeatures_rerank(final_scores_top10: Sequence[Tuple[int, float]], top10_feat
             out.append((filepath_docid[path], float(np.float32(1.0) - diffs[idx])))   # :325-328
     out = sorted(out, key=lambda it: -it[1])                                          # :330
     return list(final_scores_top10) + out                                            # :332-335
+
+
+# ---- the same on the device (hipts_crerank_*) --------------------------------------------------------------------------------
+CRERANK_MAX_TAGS = 64                                    # HIPTS_CRERANK_MAX_TAGS: required / excluded tags of one query the filter kernel holds
+
+
+def build_rerank_tables(paths: Sequence[str], image_files_name_tags_arr: Sequence[str]):
+    """The tag file as the filter kernel reads it, one entry per FEATURE row: (row_doc int32 [R], row_tag_ptr int64 [R + 1],
+    row_tags int32, tag_vocab {tag string: id}).  row_doc[r] is the doc id of paths[r] (-1: the path is not in the tag file) and
+    row_tags[row_tag_ptr[r]:row_tag_ptr[r + 1]] the ids of its tags, both as the dicts of SearchEngine.__init__ have them: for a
+    path on several lines the LAST line wins.  Tags are strings here, nothing else: every distinct tag string of the file gets an
+    id of this vocabulary (the empty string too), independent of the BM25 dictionary."""
+    last: Dict[str, int] = {}
+    tag_vocab: Dict[str, int] = {}
+    for i, line in enumerate(image_files_name_tags_arr):
+        sp = line.split(",")
+        last[sp[0]] = i
+        for t in sp[1:]:
+            if t not in tag_vocab:
+                tag_vocab[t] = len(tag_vocab)
+    R = len(paths)
+    row_doc = np.full(R, -1, dtype=np.int32)
+    row_tag_ptr = np.zeros(R + 1, dtype=np.int64)
+    line_ids: Dict[int, List[int]] = {}
+    chunks: List[List[int]] = []
+    for r, path in enumerate(paths):
+        i = last.get(path, -1)
+        ids: List[int] = []
+        if i >= 0:
+            row_doc[r] = i
+            ids = line_ids.get(i)
+            if ids is None:
+                ids = line_ids[i] = [tag_vocab[t] for t in dict.fromkeys(image_files_name_tags_arr[i].split(",")[1:])]
+        chunks.append(ids)
+        row_tag_ptr[r + 1] = row_tag_ptr[r] + len(ids)
+    row_tags = np.fromiter((t for ids in chunks for t in ids), dtype=np.int32, count=int(row_tag_ptr[R]))
+    return row_doc, row_tag_ptr, row_tags, tag_vocab
+
+
+def _threshold_f32(threshold) -> np.float32:
+    """The float32 value T with  d < T  <=>  `d < threshold` as numpy evaluates it for a float32 d (cfeatures_rerank's test).  A Python
+    float is a weak scalar there: it is rounded to float32 first.  A numpy float64 scalar is not: the comparison runs in float64, which
+    for float32 d equals comparing with the smallest float32 that is not below the threshold."""
+    if isinstance(threshold, np.floating) and threshold.dtype.itemsize > 4:
+        t = np.float32(threshold)
+        if float(t) < float(threshold):
+            t = np.nextafter(t, np.float32(np.inf), dtype=np.float32)
+        return t
+    return np.float32(threshold)
+
+
+class DeviceReranker:
+    """cfeatures_rerank with everything after the mean feature on the device: the index product, the threshold, the tag filter and the
+    ranking (hipts_crerank_*).  Returns exactly what cfeatures_rerank returns for the same arguments -- same documents, same order,
+    the same float scores.  Queries with more than CRERANK_MAX_TAGS required or excluded tags take the host path."""
+
+    def __init__(self, cindex: CharacterFeatureIndex, image_files_name_tags_arr: Sequence[str], device: int = 0,
+                 file_tag_index: Optional[Dict[str, Dict[str, bool]]] = None, filepath_docid: Optional[Dict[str, int]] = None):
+        from . import _lib
+        self._lib = _lib
+        self.cindex = cindex
+        self.device = device
+        self.lines = list(image_files_name_tags_arr)
+        self._file_tag_index, self._filepath_docid = file_tag_index, filepath_docid       # for the host fallback; built on first use if not given
+        self._h = None
+        self.rows = -1
+        self.stats = {"device_queries": 0, "host_fallbacks": 0, "table_rebuilds": 0}
+        self._build()
+
+    def _build(self):
+        import ctypes
+        self._close()
+        row_doc, row_tag_ptr, row_tags, self.tag_vocab = build_rerank_tables(self.cindex.paths, self.lines)
+        if len(self.cindex.index) != len(row_doc):
+            raise ValueError("the feature index holds %d rows but lists %d paths" % (len(self.cindex.index), len(row_doc)))
+        h = ctypes.c_void_p()
+        self._lib.call("hipts_crerank_create", self._lib.ptr(row_doc), self._lib.ptr(row_tag_ptr), self._lib.ptr(row_tags),
+                       ctypes.c_int64(len(row_doc)), self.device, ctypes.byref(h))
+        self._h = h
+        self.rows = len(row_doc)
+
+    def _host_dicts(self):
+        if self._file_tag_index is None:                   # search.py:67-68
+            self._file_tag_index = {l.split(",")[0]: {t: True for t in l.split(",")[1:]} for l in self.lines}
+            self._filepath_docid = {l.split(",")[0]: i for i, l in enumerate(self.lines)}
+        return self._file_tag_index, self._filepath_docid
+
+    def rerank(self, final_scores_top10, top10_features, required_tags, exclude_tags, threshold=None, topn=None):
+        return self.rerank_batch([final_scores_top10], [top10_features], [required_tags], [exclude_tags],
+                                 None if threshold is None else [threshold], topn)[0]
+
+    def rerank_batch(self, final_scores_top10_list, top10_features_list, required_tags_list, exclude_tags_list, thresholds=None,
+                     topn=None) -> List[List[Tuple[int, float]]]:
+        """Several queries in one call: one index product for all of them.  thresholds: None (the index's own cut), one value, or one
+        per query.  topn=None: every survivor, like the reference; otherwise the pinned pairs and the first `topn` survivors."""
+        import ctypes
+        nq = len(final_scores_top10_list)
+        if thresholds is None or np.isscalar(thresholds):
+            thresholds = [thresholds] * nq
+        thresholds = [self.cindex.cosine_diff_threshold if t is None else t for t in thresholds]
+        if len(self.cindex.paths) != self.rows:            # rows were added since the tables were built
+            self.stats["table_rebuilds"] += 1
+            self._build()
+        if any(len(r) > CRERANK_MAX_TAGS or len(e) > CRERANK_MAX_TAGS for r, e in zip(required_tags_list, exclude_tags_list)):
+            tags, docid = self._host_dicts()
+            self.stats["host_fallbacks"] += nq
+            outs = [cfeatures_rerank(f, x, self.cindex, tags, docid, r, e, t)
+                    for f, x, r, e, t in zip(final_scores_top10_list, top10_features_list, required_tags_list, exclude_tags_list, thresholds)]
+            return [o if topn is None else o[:len(f) + topn] for o, f in zip(outs, final_scores_top10_list)]
+        _lib = self._lib
+        qs = np.empty((nq, self.cindex.index.num_features), dtype=np.float32)
+        for i, feats in enumerate(top10_features_list):    # the query as cfeatures_rerank + CharacterFeatureIndex.differences make it
+            q = np.asarray(np.average(np.stack(feats), axis=0), dtype=np.float32)
+            n = np.float32(np.sqrt(np.sum(q * q)))
+            qs[i] = q / n if n > 0 else q
+        thr = np.array([_threshold_f32(t) for t in thresholds], dtype=np.float32)
+        vocab = self.tag_vocab
+        req = [[vocab.get(t, -1) for t in r] for r in required_tags_list]                  # unknown required tag: -1, nothing passes
+        exc = [[vocab[t] for t in e if t in vocab] for e in exclude_tags_list]             # unknown excluded tag: no effect
+        req_ptr = np.zeros(nq + 1, dtype=np.int32)
+        exc_ptr = np.zeros(nq + 1, dtype=np.int32)
+        np.cumsum([len(r) for r in req], out=req_ptr[1:])
+        np.cumsum([len(e) for e in exc], out=exc_ptr[1:])
+        req_ids = np.array([t for r in req for t in r] or [0], dtype=np.int32)
+        exc_ids = np.array([t for e in exc for t in e] or [0], dtype=np.int32)
+        counts = np.zeros(nq, dtype=np.int64)
+        _lib.call("hipts_crerank_run", self._h, self.cindex.index._h, _lib.ptr(qs), _lib.HOST, nq, _lib.ptr(thr), _lib.ptr(req_ptr),
+                  _lib.ptr(req_ids), _lib.ptr(exc_ptr), _lib.ptr(exc_ids), _lib.ptr(counts), _lib.current_stream_ptr())
+        self.stats["device_queries"] += nq
+        outs = []
+        for i in range(nq):
+            n = int(counts[i]) if topn is None else min(int(counts[i]), max(int(topn), 0))
+            docs = np.empty(n, dtype=np.int32)
+            scores = np.empty(n, dtype=np.float64)
+            if n:
+                _lib.call("hipts_crerank_read", self._h, i, ctypes.c_int64(0), ctypes.c_int64(n), _lib.ptr(docs), _lib.ptr(scores))
+            outs.append(list(final_scores_top10_list[i]) + list(zip(docs.tolist(), scores.tolist())))
+        return outs
+
+    def _close(self):
+        if getattr(self, "_h", None):
+            self._lib.call("hipts_crerank_destroy", self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self._close()
+        except Exception:
+            pass

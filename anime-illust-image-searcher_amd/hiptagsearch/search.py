@@ -60,6 +60,7 @@ class SearchEngine:
         self.search_mode = search_mode
         self.compat_rerank = compat_rerank
         self.cindex = None                     # cfeatures.CharacterFeatureIndex for 'character oriented' mode
+        self.crerank = None                    # cfeatures.DeviceReranker once enable_device_crerank() was called (default: the host loop)
         self.stats = {"queries": 0, "full_rank_fallbacks": 0, "rank_continuations": 0}     # full_rank_fallbacks: always 0 since round 3
         self._search_fn = _lib.load().hipts_search
         self._w_bm25, self._w_sim = c_double(BM25_WEIGHT), c_double(DOC2VEC_WEIGHT)
@@ -185,6 +186,19 @@ class SearchEngine:
         return self._doc2vec_rerank(final_dev, ids[0], vals[0], topn)                 # :390
 
     # ---- webui.py:255-342 -----------------------------------------------------------------------
+    def enable_device_crerank(self, enable: bool = True):
+        """Character-oriented mode: threshold, tag filter and ranking (webui.py:311-335) on the device instead of the host loop of
+        cfeatures_rerank -- the same list, bit for bit (cfeatures.DeviceReranker, built from this engine's lines and cindex)."""
+        from .cfeatures import DeviceReranker
+        if not enable:
+            self.crerank = None
+            return None
+        if self.cindex is None:
+            raise RuntimeError("enable_device_crerank needs engine.cindex (a cfeatures.CharacterFeatureIndex)")
+        self.crerank = DeviceReranker(self.cindex, self.image_files_name_tags_arr, self.cindex.index.device, self.file_tag_index_dict,
+                                      self.filepath_docid_dict)
+        return self.crerank
+
     def _cfeatures_rerank(self, ids: np.ndarray, vals: np.ndarray, topn: int, required: List[str], exclude: List[str]):
         from .cfeatures import cfeatures_rerank, gen_image_ndarray
         if self.cindex is None:
@@ -203,6 +217,8 @@ class SearchEngine:
             feats.append(self.cindex.ccip_batch_extract_features([arr])[0])
         if not feats:
             return top10
+        if self.crerank is not None and self.crerank.cindex is self.cindex:
+            return self.crerank.rerank(top10, feats, required, exclude, self.cindex.cosine_diff_threshold)
         return cfeatures_rerank(top10, feats, self.cindex, self.file_tag_index_dict, self.filepath_docid_dict, required, exclude,
                                 self.cindex.cosine_diff_threshold)        # own parameter: gen_cfeatures.py:298-299's constant is the metric model's
 

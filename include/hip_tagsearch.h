@@ -493,6 +493,37 @@ int hipts_search_submit(hipts_bm25_t* bm25, hipts_index_t* index, const int32_t*
                         int slot, void* stream);
 int hipts_search_collect(hipts_bm25_t* bm25, int slot, int32_t* ids_out, double* vals_out);
 
+/* ------------------------------------------------------------------------------------------
+ * Character-oriented rerank on the device.   Replaces the host loop of   webui.py:303-335:
+ * difference of every feature row to the query feature, `difference < threshold`, required and
+ * excluded tags, sort by similarity.  The product is hipts_index_query's; what follows it runs as
+ * three kernel stages per query (filter, ordered compaction, ranking) without a host synchronisation.
+ *
+ * Tables (host arrays, copied at create): for feature row r, row_doc[r] is the doc id of the row's path in the
+ * tag file (-1: the path does not occur there, the row never passes) and row_tags[row_tag_ptr[r] ..
+ * row_tag_ptr[r + 1]) are the ids of that path's tags in a vocabulary of the caller's making (tags are compared
+ * by id only).  rows < 2^31.
+ *
+ * run: queries float32 [nq][dim] as hipts_index_query takes them (one product for all nq); thresholds float32
+ * [nq]; the queries' required and excluded tag ids in CSR form (req_ptr / exc_ptr int32 [nq + 1] from 0, ids
+ * int32; all host arrays).  Row r passes for query q when, in float32,  1.0f - sim[q][r] < thresholds[q],
+ * row_doc[r] >= 0, every required id is among the row's tags and no excluded id is.  A NEGATIVE required id
+ * stands for a tag the vocabulary does not know: nothing passes.  A query may carry at most
+ * HIPTS_CRERANK_MAX_TAGS required and as many excluded ids (they live in LDS); more is HIPTS_ERR_INVALID, as is
+ * a feature index whose length differs from `rows`.  The survivors of query q, ranked by score descending with
+ * ties in ascending row order, stay in the handle as (row_doc[r], (double)(1.0f - (1.0f - sim[q][r]))) until the
+ * next run; counts_out int64 [nq] (host) receives how many there are -- the call's one synchronisation.
+ * read: entries [first, first + count) of one query's ranking of the LAST run into host arrays. */
+#define HIPTS_CRERANK_MAX_TAGS 64
+typedef struct hipts_crerank hipts_crerank_t;
+int hipts_crerank_create(const int32_t* row_doc, const int64_t* row_tag_ptr, const int32_t* row_tags, int64_t rows, int device,
+                         hipts_crerank_t** out);
+int hipts_crerank_destroy(hipts_crerank_t* h);
+int hipts_crerank_run(hipts_crerank_t* h, hipts_index_t* features, const float* queries, int queries_memspace, int nq,
+                      const float* thresholds, const int32_t* req_ptr, const int32_t* req_ids, const int32_t* exc_ptr,
+                      const int32_t* exc_ids, int64_t* counts_out, void* stream);
+int hipts_crerank_read(hipts_crerank_t* h, int query, int64_t first, int64_t count, int32_t* docs_out, double* scores_out);
+
 /* Per-kernel timing of the query path for roofline accounting (bench.py), as hipts_vit_profile_* above: while enabled, every
  * kernel hipts_search launches is bracketed by HIP events on the stream it is launched on.  read() resolves them (synchronises) and
  * returns, for one kernel category, the summed device time, the launches and the ALGORITHMIC bytes those launches stand for
