@@ -114,9 +114,7 @@ __global__ __launch_bounds__(256) void stem_im2col_kernel(const void* __restrict
                 if constexpr (U8) v = slut[c * 256 + reinterpret_cast<const uint8_t*>(img)[(((int64_t)b * S + iy) * S + ix) * 3 + c]];
                 else v = reinterpret_cast<const float*>(img)[(((int64_t)b * 3 + c) * S + iy) * S + ix];
             }
-            const bf16_t hi = to_op<F16>(v);
-            row[kx * 3 + c] = hi;
-            row[STEM_KH + kx * 3 + c] = to_op<F16>(v - from_op<F16>(hi));
+            split_hilo<F16>(v, row[kx * 3 + c], row[STEM_KH + kx * 3 + c]);
         }
     }
 }
@@ -169,9 +167,7 @@ __global__ __launch_bounds__(256) void stem_im2col_u8_kernel(const uint8_t* __re
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float v = in ? slut[c * 256 + tile[ky][(tok * 4 + kx) * 3 + c]] : 0.f;
-                const bf16_t hi = to_op<F16>(v);
-                row[kx * 3 + c] = hi;
-                row[STEM_KH + kx * 3 + c] = to_op<F16>(v - from_op<F16>(hi));
+                split_hilo<F16>(v, row[kx * 3 + c], row[STEM_KH + kx * 3 + c]);
             }
         }
     }
@@ -181,88 +177,6 @@ __global__ __launch_bounds__(256) void stem_im2col_u8_kernel(const uint8_t* __re
     const uint4* src = reinterpret_cast<const uint4*>(&orow[0][0]);
     uint4* dst = reinterpret_cast<uint4*>(a0 + m0 * STEM_K);
     for (int i = tid; i < ntok * (STEM_K * 2 / 16); i += 256) dst[i] = src[i];
-}
-
-// Bias-free LayerNorm of float32 rows, in place (the stem's norm: its output IS the residual stream).
-// float4 c of row `row` of the fp32 residual stream: row-major, or (blk) in 16 x 16 blocks of 1 KB (csrc/gemm_epi.h::x_off)
-__device__ __forceinline__ float4* x_vec(float* x, int64_t row, int c, int D, int blk) {
-    if (blk) return reinterpret_cast<float4*>(x + ((((row >> 4) * (int64_t)(D >> 4)) + (c >> 2)) << 8) + (row & 15) * 16 + (c & 3) * 4);
-    return reinterpret_cast<float4*>(x + row * D) + c;
-}
-
-__global__ __launch_bounds__(256) void ln_inplace_kernel(float* __restrict__ x, const float* __restrict__ g, int64_t rows, int D,
-                                                         float eps, int blk) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nvec = D >> 2;
-    float4 v[4];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        v[i] = c < nvec ? *x_vec(x, row, c, D, blk) : make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-    const float mean = wave_sum_f(s) / (float)D;
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        if (lane + 64 * i < nvec) {
-            const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-            ss += (a * a + b * b) + (c * c + d * d);
-        }
-    const float rstd = 1.0f / sqrtf(wave_sum_f(ss) / (float)D + eps);
-    const float4* gr = reinterpret_cast<const float4*>(g);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec) {
-            const float4 gg = gr[c];
-            *x_vec(x, row, c, D, blk) = make_float4((v[i].x - mean) * rstd * gg.x, (v[i].y - mean) * rstd * gg.y, (v[i].z - mean) * rstd * gg.z,
-                                (v[i].w - mean) * rstd * gg.w);
-        }
-    }
-}
-
-// vit.hip's layernorm_kernel (bias-free, 16-bit output, same operations in the same order) reading the BLOCKED residual stream: the
-// downsample norms of the stages whose stream is stored in 16 x 16 blocks (two launches per forward)
-template <bool F16>
-__global__ __launch_bounds__(256) void layernorm_blk_kernel(float* __restrict__ x, const float* __restrict__ g, bf16_t* __restrict__ out,
-                                                            int64_t rows, int D, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nvec = D >> 2;
-    float4 v[4];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        v[i] = c < nvec ? *x_vec(x, row, c, D, 1) : make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-    const float mean = wave_sum_f(s) / (float)D;
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (lane + 64 * i < nvec) {
-            const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-            ss += (a * a + b * b) + (c * c + d * d);
-        }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum_f(ss) / (float)D + eps);
-    const float4* gr = reinterpret_cast<const float4*>(g);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec) {
-            const float4 gg = gr[c];
-            *reinterpret_cast<bf16x4*>(out + row * D + 4 * c) =
-                pack4<F16>((v[i].x - mean) * rstd * gg.x + 0.f, (v[i].y - mean) * rstd * gg.y + 0.f, (v[i].z - mean) * rstd * gg.z + 0.f,
-                           (v[i].w - mean) * rstd * gg.w + 0.f);
-        }
-    }
 }
 
 // Downsampling patch matrix: col[m'][(ky*3 + kx)*C + c] = xn[b][2 oy - 1 + ky][2 ox - 1 + kx][c] (zero outside).
@@ -329,9 +243,12 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
         return xblk_env && Sg.C <= 256 && Sg.C % 16 == 0 && Sg.T % 16 == 0;
     };
     bool xblk = false;          // layout of x right now (the stage being processed)
+    // xn = 16bit(LN(x) * gamma): launch_layernorm without beta -- it adds + 0.f, so -0 becomes +0 -- or, where the stream is stored in
+    // 16 x 16 blocks (two downsample norms per forward), the same row_ln_kernel reading blocks, with the same + 0.f
     auto layernorm_xn = [&](const float* gamma, int64_t rows, int D) -> int {
         if (xblk) {
-            HIPTS_LAUNCH_F16(f16, layernorm_blk_kernel, ceil_div(rows, 4), 256, 0, s, x, gamma, xn, rows, D, c.ln_eps);
+            const LnGamma<true> norm{gamma};
+            HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(rows, 4), 256, 0, s, FromF32Blocked{x}, norm, To16{xn}, rows, D, c.ln_eps);
             return HIPTS_OK;
         }
         return launch_layernorm(x, gamma, nullptr, xn, rows, D, c.ln_eps, f16, s);
@@ -371,7 +288,10 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
         xblk = stage_blocked(0);
         g.x_blocked = xblk ? 1 : 0;
         HIPTS_TRY(gemm(EPI_BIAS, g, s));
-        ln_inplace_kernel<<<ceil_div(M, 4), 256, 0, s>>>(x, h->stem_norm.as<float>(), M, S0.C, c.ln_eps, xblk ? 1 : 0);
+        // bias-free LayerNorm in place: its output IS the residual stream (no + 0.f here: a -0 product stays -0 in the fp32 stream)
+        const F32InPlace stream{x, xblk ? 1 : 0};
+        const LnGamma<false> norm{h->stem_norm.as<float>()};
+        row_ln_kernel<false><<<ceil_div(M, 4), 256, 0, s>>>(stream, norm, BackToSource{}, M, S0.C, c.ln_eps);
         HIPTS_LAUNCH_CHECK();
     }
 
@@ -411,7 +331,7 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
         // Wide stages (rows of more than one 256-column tile: C = 512, 768; round 5): the LayerNorms are folded as in the ViT -- the residual
         // GEMM that finishes a row (EPI_RESID_XG, here with the CAFormer's res_scale) also writes gamma * x as the consumer's 16-bit operand
         // and the row's partial sums; q | k, v and fc1 apply rstd / mean in their epilogues (col_u = W gamma; the CAFormer's norms have no
-        // beta).  40 of a forward's 45 layernorm_kernel launches (5.2 % of its kernel time, each a pass over the fp32 stream) go; a stage's
+        // beta).  40 of a forward's 45 row_ln_kernel launches (5.2 % of its kernel time, each a pass over the fp32 stream) go; a stage's
         // first norm1 (its rows come from the downsample GEMM) and the downsample norms (their consumer is the im2col) stay.  Only when the
         // stage's residual launches are not the two-workgroups-per-CU kernel's anyway (that loop has no statistics epilogue): more tiles
         // than half the CUs.  HIPTS_CCIP_LN_FOLD=0: off (A/B).

@@ -1,7 +1,8 @@
 // convnet.h -- kernels shared by the convolutional forwards (ccip.hip: the CAFormer encoder; convnext.hip: the ConvNeXt tagger;
 // swinv2.hip: the SwinV2 tagger's stem): the depthwise 7x7 convolution (VALU and matrix-core forms, and the Toeplitz lane images of its
-// weights), the pooled LayerNorm head, and the 4 x 4 patch stem with its LayerNorm.  Everything lives in an anonymous namespace, so each
-// including object gets its own copy under the same symbol names.
+// weights), the pooled LayerNorm head, and the 4 x 4 patch stem.  The per-row LayerNorm (row_ln_kernel), the wave reduction and the
+// hi | lo split come with row_ln.h.  Everything lives in an anonymous namespace, so each including object gets its own copy under the
+// same symbol names.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -9,16 +10,11 @@
 #include <vector>
 
 #include "vit_internal.h"
+#include "row_ln.h"
 
 namespace {
 
 using namespace hipts;
-
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Depthwise 7x7, padding 3, NHWC: out[b][y][x][c] = sum_{ky,kx} in[b][y+ky-3][x+kx-3][c] * w[ky*7+kx][c].
@@ -402,7 +398,7 @@ __global__ __launch_bounds__(1024) void pool_ln_kernel(const float* __restrict__
             m[u] = ((part[0][c] + part[1][c]) + (part[2][c] + part[3][c])) / (float)T;
             if (c < C) s += m[u];
         }
-        s = wave_sum_f(s);
+        s = wave_sum(s);
         if ((tid & 63) == 0) red[tid >> 6] = s;
     }
     __syncthreads();
@@ -413,7 +409,7 @@ __global__ __launch_bounds__(1024) void pool_ln_kernel(const float* __restrict__
 #pragma unroll
         for (int u = 0; u < 4; ++u)
             if (tid + 256 * u < C) ss += (m[u] - mean) * (m[u] - mean);
-        ss = wave_sum_f(ss);
+        ss = wave_sum(ss);
         if ((tid & 63) == 0) red[tid >> 6] = ss;
     }
     __syncthreads();
@@ -427,8 +423,9 @@ __global__ __launch_bounds__(1024) void pool_ln_kernel(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
-// The 4 x 4 s4 patch stem and its LayerNorm, shared by the ConvNeXt (convnext.hip) and SwinV2 (swinv2.hip) taggers, and the
-// hi | lo split of the pooled features in front of their head GEMM.
+// The 4 x 4 s4 patch stem, shared by the ConvNeXt (convnext.hip) and SwinV2 (swinv2.hip) taggers (its LayerNorm, in place with the
+// 16-bit copy, is row_ln_kernel with FromF32 / LnGammaBeta / ToF32And16), and the hi | lo split of the pooled features in front of their
+// head GEMM.
 // ---------------------------------------------------------------------------------------------
 constexpr int CNX_STEM_KH = 64;                  // 4*4*3 = 48 taps padded to 64; K = hi | lo = 128
 constexpr int CNX_STEM_K = 2 * CNX_STEM_KH;
@@ -458,9 +455,7 @@ __global__ __launch_bounds__(256) void cnx_stem_kernel(const void* __restrict__ 
             float v;
             if constexpr (U8) v = lut[c * 256 + reinterpret_cast<const uint8_t*>(img)[((b * S + iy) * S + ix) * 3 + c]];
             else v = reinterpret_cast<const float*>(img)[((b * 3 + (2 - c)) * S + iy) * (int64_t)S + ix];
-            const bf16_t hi = to_op<F16>(v);
-            row[(ky * 4 + kx) * 3 + c] = hi;
-            row[CNX_STEM_KH + (ky * 4 + kx) * 3 + c] = to_op<F16>(v - from_op<F16>(hi));
+            split_hilo<F16>(v, row[(ky * 4 + kx) * 3 + c], row[CNX_STEM_KH + (ky * 4 + kx) * 3 + c]);
         }
     }
     if (ky == 0) {
@@ -472,67 +467,13 @@ __global__ __launch_bounds__(256) void cnx_stem_kernel(const void* __restrict__ 
     }
 }
 
-// Row statistics of one row held by a wave as up to four float4 per lane (D <= 1024, D % 4 == 0): the two-pass mean / variance of
-// ln_inplace_kernel (ccip.hip), same operations in the same order.
-__device__ __forceinline__ void row_mean_rstd(const float4 (&v)[4], int lane, int D, float eps, float& mean, float& rstd) {
-    const int nvec = D >> 2;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    mean = wave_sum_f(s) / (float)D;
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        if (lane + 64 * i < nvec) {
-            const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-            ss += (a * a + b * b) + (c * c + d * d);
-        }
-    rstd = 1.0f / sqrtf(wave_sum_f(ss) / (float)D + eps);
-}
-
-__device__ __forceinline__ float4 ln_apply(float4 v, float mean, float rstd, float4 g, float4 b) {
-    return make_float4((v.x - mean) * rstd * g.x + b.x, (v.y - mean) * rstd * g.y + b.y, (v.z - mean) * rstd * g.z + b.z,
-                       (v.w - mean) * rstd * g.w + b.w);
-}
-
-// The stem's LayerNorm (weight and bias) of float32 rows in place; also the 16-bit copy xh.  One wave per row.
-template <bool F16>
-__global__ __launch_bounds__(256) void cnx_ln_kernel(float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ bt,
-                                                     bf16_t* __restrict__ xh, int64_t rows, int D, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nvec = D >> 2;
-    float4* xr = reinterpret_cast<float4*>(x + row * D);
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        v[i] = c < nvec ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float mean, rstd;
-    row_mean_rstd(v, lane, D, eps, mean, rstd);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec) {
-            const float4 o = ln_apply(v[i], mean, rstd, reinterpret_cast<const float4*>(g)[c], reinterpret_cast<const float4*>(bt)[c]);
-            xr[c] = o;
-            *reinterpret_cast<bf16x4*>(xh + row * D + 4 * c) = pack4<F16>(o.x, o.y, o.z, o.w);
-        }
-    }
-}
-
 // Pooled features as hi | lo halves (the head GEMM runs K = 2 C against [W | W]): f2[b][c] = hi, f2[b][C + c] = lo.
 template <bool F16>
 __global__ __launch_bounds__(256) void cnx_split_kernel(const float* __restrict__ f, bf16_t* __restrict__ f2, int batch, int C) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= batch * C) return;
     const int b = i / C, c = i - b * C;
-    const float v = f[i];
-    const bf16_t hi = to_op<F16>(v);
-    f2[(size_t)b * 2 * C + c] = hi;
-    f2[(size_t)b * 2 * C + C + c] = to_op<F16>(v - from_op<F16>(hi));
+    split_hilo<F16>(f[i], f2[(size_t)b * 2 * C + c], f2[(size_t)b * 2 * C + C + c]);
 }
 
 }  // namespace

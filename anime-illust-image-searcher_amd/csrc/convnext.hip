@@ -10,10 +10,13 @@
 // operands 16-bit (bf16, or IEEE half with operand_f16 bit 0).  Every 1 x 1 convolution / Linear is the shared persistent MFMA
 // GEMM (gemm.hip) with a fused epilogue:
 //   stem 4x4 s4      patch gather (hi | lo halves against [W | W], K = 2 x 64)  -> EPI_BIAS, then LayerNorm with bias in place
-//                    (convnet.h: cnx_stem_kernel, cnx_ln_kernel, which also writes the 16-bit copy of x the first depthwise convolution reads)
-//   downsample       LayerNorm fused with the 2 x 2 s2 gather (cnx_ds_kernel writes the GEMM's A matrix) -> EPI_BIAS, 16-bit copy
-//   depthwise 7x7    convnet.h: the matrix-core kernel (half operands, side >= 16) or the VALU kernel; then cnx_dwln_kernel adds the
-//                    depthwise bias and applies the block's LayerNorm (weight, bias) into the 16-bit operand of fc1
+//                    (convnet.h: cnx_stem_kernel; row_ln.h: row_ln_kernel, whose ToF32And16 sink also writes the 16-bit copy of x the
+//                    first depthwise convolution reads)
+//   downsample       LayerNorm fused with the 2 x 2 s2 gather (row_ln_kernel with the ToPatch2x2 sink writes the GEMM's A matrix: every
+//                    token is normalised once and lands in one row) -> EPI_BIAS, 16-bit copy
+//   depthwise 7x7    convnet.h: the matrix-core kernel (half operands, side >= 16) or the VALU kernel; then row_ln_kernel with the
+//                    From16Bias source adds the depthwise bias in fp32 and applies the block's LayerNorm (weight, bias) into the 16-bit
+//                    operand of fc1
 //   fc1              EPI_GELU with gelu_tanh = 0 (erf GELU, the epilogue's rational approximation)
 //   fc2              EPI_RESID_LS: x += gamma * (acc + b2) in fp32 -- the layer scale is NOT folded into W2 (timm initialises it at
 //                    1e-6, and gamma W2 rounded to half lands in the subnormal range, which the MFMA reads as zero) -- and the 16-bit
@@ -67,39 +70,6 @@ struct hipts_convnext {
 namespace {
 
 
-// Downsample: LayerNorm (weight, bias) of input token (b, iy, ix) written straight into the 2 x 2 s2 patch matrix,
-// col[(b, iy / 2, ix / 2)][((iy & 1) * 2 + (ix & 1)) * C + c].  The patches do not overlap: every token is normalised once and lands
-// in one row.  One wave per input token.
-template <bool F16>
-__global__ __launch_bounds__(256) void cnx_ds_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ bt,
-                                                     bf16_t* __restrict__ col, int64_t rows, int H, int D, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nvec = D >> 2;
-    const float4* xr = reinterpret_cast<const float4*>(x + row * D);
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        v[i] = c < nvec ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float mean, rstd;
-    row_mean_rstd(v, lane, D, eps, mean, rstd);
-    const int ix = (int)(row % H), iy = (int)((row / H) % H);
-    const int64_t b = row / ((int64_t)H * H);
-    const int Ho = H >> 1;
-    bf16_t* dst = col + (((b * Ho + (iy >> 1)) * Ho + (ix >> 1)) * 4 + ((iy & 1) * 2 + (ix & 1))) * (int64_t)D;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec) {
-            const float4 o = ln_apply(v[i], mean, rstd, reinterpret_cast<const float4*>(g)[c], reinterpret_cast<const float4*>(bt)[c]);
-            *reinterpret_cast<bf16x4*>(dst + 4 * c) = pack4<F16>(o.x, o.y, o.z, o.w);
-        }
-    }
-}
-
 // 16-bit copy of the fp32 stream (behind the downsample GEMM, whose EPI_BIAS epilogue writes fp32 only).  One thread per float4.
 template <bool F16>
 __global__ __launch_bounds__(256) void cnx_cast_kernel(const float* __restrict__ x, bf16_t* __restrict__ xh, int64_t n4) {
@@ -107,40 +77,6 @@ __global__ __launch_bounds__(256) void cnx_cast_kernel(const float* __restrict__
     if (i >= n4) return;
     const float4 v = reinterpret_cast<const float4*>(x)[i];
     reinterpret_cast<bf16x4*>(xh)[i] = pack4<F16>(v.x, v.y, v.z, v.w);
-}
-
-// The block's LayerNorm: xn = LN(dw + b_dw) * w + b, dw the 16-bit output of the depthwise convolution; the bias is added in float32
-// before the statistics.  One wave per row.
-template <bool F16>
-__global__ __launch_bounds__(256) void cnx_dwln_kernel(const bf16_t* __restrict__ dw, const float* __restrict__ bdw, const float* __restrict__ g,
-                                                       const float* __restrict__ bt, bf16_t* __restrict__ xn, int64_t rows, int D, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nvec = D >> 2;
-    const bf16x4* dr = reinterpret_cast<const bf16x4*>(dw + row * D);
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec) {
-            const bf16x4 h = dr[c];
-            const float4 bb = reinterpret_cast<const float4*>(bdw)[c];
-            v[i] = make_float4(from_op<F16>(h[0]) + bb.x, from_op<F16>(h[1]) + bb.y, from_op<F16>(h[2]) + bb.z, from_op<F16>(h[3]) + bb.w);
-        } else {
-            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    float mean, rstd;
-    row_mean_rstd(v, lane, D, eps, mean, rstd);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec) {
-            const float4 o = ln_apply(v[i], mean, rstd, reinterpret_cast<const float4*>(g)[c], reinterpret_cast<const float4*>(bt)[c]);
-            *reinterpret_cast<bf16x4*>(xn + row * D + 4 * c) = pack4<F16>(o.x, o.y, o.z, o.w);
-        }
-    }
 }
 
 // The kernel sequence for images [i0, i0 + batch) on stream s.  stop_stage >= 0 (debug entry): return after that stage's last block,
@@ -183,7 +119,8 @@ int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, in
         g.A = a0; g.W = h->stem_w.as<bf16_t>(); g.M = (int)M; g.N = S0.C; g.K = CNX_STEM_K;
         g.bias = h->stem_b.as<float>(); g.out_f32 = x;
         HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
-        HIPTS_LAUNCH_F16(f16, cnx_ln_kernel, ceil_div(M, 4), 256, 0, s, x, h->stem_nw.as<float>(), h->stem_nb.as<float>(), xh, M, S0.C, c.ln_eps);
+        const LnGammaBeta norm{h->stem_nw.as<float>(), h->stem_nb.as<float>()};
+        HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(M, 4), 256, 0, s, FromF32{x}, norm, ToF32And16{x, xh}, M, S0.C, c.ln_eps);
     }
 
     for (int si = 0; si < 4; ++si) {
@@ -194,7 +131,8 @@ int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, in
             // downsample: LN(x) gathered into 2x2 s2 patches -> GEMM (+bias) -> x, then its 16-bit copy
             const CnxStage& Pv = h->st[si - 1];
             const int64_t rows_in = (int64_t)batch * Pv.T;
-            HIPTS_LAUNCH_F16(f16, cnx_ds_kernel, ceil_div(rows_in, 4), 256, 0, s, x, St.ds_nw.as<float>(), St.ds_nb.as<float>(), col, rows_in, Pv.H, Pv.C, c.ln_eps);
+            const LnGammaBeta norm{St.ds_nw.as<float>(), St.ds_nb.as<float>()};
+            HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(rows_in, 4), 256, 0, s, FromF32{x}, norm, ToPatch2x2{col, Pv.H}, rows_in, Pv.C, c.ln_eps);
             GemmArgs g = gemm_args();
             g.A = col; g.W = St.ds_w.as<bf16_t>(); g.M = M; g.N = C; g.K = 4 * Pv.C;
             g.bias = St.ds_b.as<float>(); g.out_f32 = x;
@@ -212,7 +150,9 @@ int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, in
                 HIPTS_LAUNCH_F16(f16, dwconv7_kernel, dw_grid, 256, DW_LDS_BYTES, s, xh, B.dw.as<float>(), dwo, H, C, tiles_x, tiles_y);
             }
             // + depthwise bias -> LayerNorm (weight, bias) -> the 16-bit operand of fc1
-            HIPTS_LAUNCH_F16(f16, cnx_dwln_kernel, ceil_div(M, 4), 256, 0, s, dwo, B.dw_b.as<float>(), B.n_w.as<float>(), B.n_b.as<float>(), xn, M, C, c.ln_eps);
+            const From16Bias dw{dwo, B.dw_b.as<float>()};
+            const LnGammaBeta norm{B.n_w.as<float>(), B.n_b.as<float>()};
+            HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(M, 4), 256, 0, s, dw, norm, To16{xn}, (int64_t)M, C, c.ln_eps);
             GemmArgs g = gemm_args();
             g.A = xn; g.W = B.fc1.as<bf16_t>(); g.M = M; g.N = 4 * C; g.K = C; g.bias = B.fc1_b.as<float>();
             g.out_bf16 = m1; g.gelu_tanh = 0;

@@ -22,6 +22,7 @@
 
 #include "vit_internal.h"
 #include "model_host.h"
+#include "row_ln.h"
 
 using namespace hipts;
 
@@ -58,12 +59,6 @@ struct hipts_eva {
 
 namespace {
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // Patch matrix, hi | lo halves of the normalised pixel (K = 2 PK, PK = P*P*3 rounded up to 64, pad columns stay
 // zero).  Column (ky*P + kx)*3 + c holds memory channel c (RGB); the BGR flip of tagging.py:243 lives in the
 // weight permutation.  U8: ToTensor (/255) and Normalize ((x - .5) / .5) in float32 like the reference.
@@ -90,9 +85,7 @@ __global__ __launch_bounds__(256) void eva_patchify_kernel(const void* __restric
             } else {
                 v = reinterpret_cast<const float*>(img)[((b * 3 + (2 - c)) * S + iy) * (int64_t)S + ix];
             }
-            const bf16_t hi = to_op<F16>(v);
-            dst[kx * 3 + c] = hi;
-            dst[PK + kx * 3 + c] = to_op<F16>(v - from_op<F16>(hi));
+            split_hilo<F16>(v, dst[kx * 3 + c], dst[PK + kx * 3 + c]);
         }
     }
 }
@@ -171,7 +164,7 @@ __global__ __launch_bounds__(1024) void eva_pool_kernel(const float* __restrict_
             m[u] = ((part[0][c] + part[1][c]) + (part[2][c] + part[3][c])) / (float)count;
             if (c < D) s += m[u];
         }
-        s = wsum(s);
+        s = wave_sum(s);
         if ((tid & 63) == 0) red[tid >> 6] = s;
     }
     __syncthreads();
@@ -182,7 +175,7 @@ __global__ __launch_bounds__(1024) void eva_pool_kernel(const float* __restrict_
 #pragma unroll
         for (int u = 0; u < 4; ++u)
             if (tid + 256 * u < D) ss += (m[u] - mean) * (m[u] - mean);
-        ss = wsum(ss);
+        ss = wave_sum(ss);
         if ((tid & 63) == 0) red[tid >> 6] = ss;
     }
     __syncthreads();
@@ -193,9 +186,7 @@ __global__ __launch_bounds__(1024) void eva_pool_kernel(const float* __restrict_
         const int c = tid + 256 * u;
         if (c < D) {
             const float f = (m[u] - mean) * rstd * g[c] + bta[c];
-            const bf16_t hi = to_op<F16>(f);
-            out[(int64_t)b * 2 * D + c] = hi;
-            out[(int64_t)b * 2 * D + D + c] = to_op<F16>(f - from_op<F16>(hi));
+            split_hilo<F16>(f, out[(int64_t)b * 2 * D + c], out[(int64_t)b * 2 * D + D + c]);
         }
     }
 }

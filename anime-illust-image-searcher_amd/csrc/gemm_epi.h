@@ -515,7 +515,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
             }
             // ---- pass 2 / 3: row mean and variance.  A row's N <= 256 columns are spread over the four waves
             // of a wave group (64 each) and, inside a wave, over the four lane quarters: butterfly over the
-            // quarters, then the wave partials meet in LDS (red[row][wave_n]).  Two passes like layernorm_kernel.
+            // quarters, then the wave partials meet in LDS (red[row][wave_n]).  Two passes like row_mean_rstd (row_ln.h).
             float* red = reinterpret_cast<float*>(scratch);
             const float inv_n = 1.0f / (float)a.N;
             float mean[MR], rstd[MR];

@@ -23,6 +23,7 @@
 //                 read from LDS in that order (two 8-byte reads).  O^T keeps the query on the lane: the final 1 / l is lane-local.
 // The whole row (<= 256 keys, padded to a multiple of 32, padded keys masked) sits in registers: the softmax is exact two-pass.
 #include "vit_internal.h"
+#include "row_ln.h"
 
 namespace hipts {
 namespace {
@@ -99,9 +100,7 @@ __global__ __launch_bounds__(256) void swin_attn_kernel(const float* __restrict_
         const float vn[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const bf16_t hi = to_op<F16>(kn[i]);
-            khi[t * SW_KS + d0 + i] = hi;
-            klo[t * SW_KS + d0 + i] = to_op<F16>((kn[i] - from_op<F16>(hi)) * SW_LO);
+            split_hilo<F16>(kn[i], khi[t * SW_KS + d0 + i], klo[t * SW_KS + d0 + i], SW_LO);
             vt[(d0 + i) * SW_VS + t] = to_op<F16>(vn[i]);
         }
     }
@@ -133,10 +132,10 @@ __global__ __launch_bounds__(256) void swin_attn_kernel(const float* __restrict_
         bf16x8 qhi, qlo;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const float v = qf[i] * qinv * SW_U;
-            const bf16_t hb = to_op<F16>(v);
+            bf16_t hb, lb;
+            split_hilo<F16>(qf[i] * qinv * SW_U, hb, lb, SW_LO);
             qhi[i] = hb;
-            qlo[i] = to_op<F16>((v - from_op<F16>(hb)) * SW_LO);
+            qlo[i] = lb;
         }
         const SwMeta mq = meta[qi < TP ? qi : 0];
         const int boff = (mq.py + w - 1) * (2 * w - 1) + (mq.px + w - 1);

@@ -10,22 +10,22 @@
 //
 // Data layout as in the ConvNeXt forward: token-major NHWC, the residual stream x float32 [B*H*W][C], its hi | lo 16-bit halves xh2
 // [B*H*W][2 C] the A operand of q | k | v and fc1.  Every Linear is the shared persistent MFMA GEMM (gemm.hip):
-//   stem          convnet.h's cnx_stem_kernel (hi | lo patch gather) -> EPI_BIAS -> cnx_ln_kernel (LayerNorm with bias in place; its
-//                 16-bit copy xh is not read here) -> sw_split_x_kernel (xh2)
+//   stem          convnet.h's cnx_stem_kernel (hi | lo patch gather) -> EPI_BIAS -> row_ln.h's row_ln_kernel (LayerNorm with bias in
+//                 place, the ToF32And16 sink the ConvNeXt stem uses; its 16-bit copy xh is not read here) -> sw_split_x_kernel (xh2)
 //   merging       sw_merge_kernel (2 x 2 gather in timm's order as hi | lo halves of the fp32 stream) -> EPI_BIAS (K = 8 C, zero bias)
-//                 -> cnx_ln_kernel in place
+//                 -> row_ln_kernel in place, as the stem
 //   q | k | v     EPI_BIAS into float32 [M][3 C] (bias [q_bias | 0 | v_bias]) from the hi | lo halves of x (xh2, K = 2 C against
 //                 [W | W]).  The cosine multiplies q and k by up to 100 after normalisation: a single 16-bit rounding of x moves a score
 //                 by ~2e-2 (measured: 0.6 max |dlogit| on the trained-like checkpoint).  q and k reach the attention in float32, which
 //                 normalises them before its own hi | lo rounding (swin_attn.hip)
 //   attention     launch_swin_attention: windows, shift, cosine, position bias and the -100 mask as index math; 16-bit output
-//   proj, fc2     EPI_BIAS into the float32 branch buffer, then sw_postnorm_kernel: x += LN(branch) (weight, bias) and xh2 = the hi | lo
-//                 halves of the new x, the operand of fc1 / of the next block's q | k | v.  One form for every stage: which kernels run
+//   proj, fc2     EPI_BIAS into the float32 branch buffer, then row_ln_kernel with the AddToStreamHiLo sink (one wave per row):
+//                 x += LN(branch) (weight, bias) and xh2 = the hi | lo halves of the new x, the operand of fc1 / of the next block's q | k | v.  One form for every stage: which kernels run
 //                 depends on the configuration only, never on the batch or its split.
 //   fc1           EPI_GELU from xh2 (K = 2 C against [W | W]; gelu_tanh from the configuration, 0 = the erf form).  The hi | lo operands
 //                 of merging, q | k | v and fc1 are what brings a flat picture's logits within 1e-3 of float64: its tokens share every
 //                 rounding error, which the mean over tokens then cannot average out
-//   head          sw_ln_rows_kernel (per-token LayerNorm, float32) -> sw_mean_kernel -> cnx_split_kernel (hi | lo) -> EPI_HEAD
+//   head          row_ln_kernel with the ToF32 sink (per-token LayerNorm, float32) -> sw_mean_kernel -> cnx_split_kernel (hi | lo) -> EPI_HEAD
 // The position-bias tables 16 sigmoid(cpb_mlp(table)) depend on the weights only: computed on the host (double, stored float32) at the
 // first forward after the last cpb_mlp tensor was set, [heads][(2 w - 1)^2] per block.
 #include <algorithm>
@@ -92,45 +92,8 @@ __global__ __launch_bounds__(256) void sw_merge_kernel(const float* __restrict__
     const int64_t b = r / ((int64_t)Ho * Ho);
     const int dy = q & 1, dx = q >> 1;
     const float4 v = *reinterpret_cast<const float4*>(x + ((b * H + 2 * oy + dy) * H + 2 * ox + dx) * C + c);
-    const bf16x4 hi = pack4<F16>(v.x, v.y, v.z, v.w);
     bf16_t* dst = col + r * 8 * C + q * C + c;
-    *reinterpret_cast<bf16x4*>(dst) = hi;
-    *reinterpret_cast<bf16x4*>(dst + 4 * C) =
-        pack4<F16>(v.x - from_op<F16>(hi[0]), v.y - from_op<F16>(hi[1]), v.z - from_op<F16>(hi[2]), v.w - from_op<F16>(hi[3]));
-}
-
-// Post-norm residual: x += LN(branch) * w + b over rows of D (<= 1024) float32, then the hi | lo halves of the new x.  One wave per row.
-template <bool F16>
-__global__ __launch_bounds__(256) void sw_postnorm_kernel(const float* __restrict__ br, const float* __restrict__ g, const float* __restrict__ bt,
-                                                          float* __restrict__ x, bf16_t* __restrict__ xh2, int64_t rows, int D, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nvec = D >> 2;
-    const float4* bv = reinterpret_cast<const float4*>(br + row * D);
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        v[i] = c < nvec ? bv[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float mean, rstd;
-    row_mean_rstd(v, lane, D, eps, mean, rstd);
-    float4* xr = reinterpret_cast<float4*>(x + row * D);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec) {
-            const float4 o = ln_apply(v[i], mean, rstd, reinterpret_cast<const float4*>(g)[c], reinterpret_cast<const float4*>(bt)[c]);
-            float4 n = xr[c];
-            n.x += o.x; n.y += o.y; n.z += o.z; n.w += o.w;
-            xr[c] = n;
-            const bf16x4 hi = pack4<F16>(n.x, n.y, n.z, n.w);
-            *reinterpret_cast<bf16x4*>(xh2 + row * 2 * D + 4 * c) = hi;
-            *reinterpret_cast<bf16x4*>(xh2 + row * 2 * D + D + 4 * c) =
-                pack4<F16>(n.x - from_op<F16>(hi[0]), n.y - from_op<F16>(hi[1]), n.z - from_op<F16>(hi[2]), n.w - from_op<F16>(hi[3]));
-        }
-    }
+    split_hilo4<F16>(v, *reinterpret_cast<bf16x4*>(dst), *reinterpret_cast<bf16x4*>(dst + 4 * C));
 }
 
 // x as hi | lo halves, xh2[m] = [16bit(x[m]) | 16bit(x[m] - hi)] (behind the stem and merging LayerNorms).  One thread per float4.
@@ -141,35 +104,7 @@ __global__ __launch_bounds__(256) void sw_split_x_kernel(const float* __restrict
     const int64_t row = i / (D >> 2);
     const int c = (int)(i - row * (D >> 2)) * 4;
     const float4 v = reinterpret_cast<const float4*>(x)[i];
-    const bf16x4 hi = pack4<F16>(v.x, v.y, v.z, v.w);
-    *reinterpret_cast<bf16x4*>(xh2 + row * 2 * D + c) = hi;
-    *reinterpret_cast<bf16x4*>(xh2 + row * 2 * D + D + c) =
-        pack4<F16>(v.x - from_op<F16>(hi[0]), v.y - from_op<F16>(hi[1]), v.z - from_op<F16>(hi[2]), v.w - from_op<F16>(hi[3]));
-}
-
-// The head's LayerNorm of every token, float32 out.  One wave per row.
-__global__ __launch_bounds__(256) void sw_ln_rows_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ bt,
-                                                         float* __restrict__ y, int64_t rows, int D, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nvec = D >> 2;
-    const float4* xr = reinterpret_cast<const float4*>(x + row * D);
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        v[i] = c < nvec ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float mean, rstd;
-    row_mean_rstd(v, lane, D, eps, mean, rstd);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec)
-            reinterpret_cast<float4*>(y + row * D)[c] =
-                ln_apply(v[i], mean, rstd, reinterpret_cast<const float4*>(g)[c], reinterpret_cast<const float4*>(bt)[c]);
-    }
+    split_hilo4<F16>(v, *reinterpret_cast<bf16x4*>(xh2 + row * 2 * D + c), *reinterpret_cast<bf16x4*>(xh2 + row * 2 * D + D + c));
 }
 
 // Mean over an image's T tokens, tokens summed in order (one workgroup per image).
@@ -263,7 +198,8 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
         g.A = a0; g.W = h->stem_w.as<bf16_t>(); g.M = (int)M; g.N = S0.C; g.K = CNX_STEM_K;
         g.bias = h->stem_b.as<float>(); g.out_f32 = x;
         HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
-        HIPTS_LAUNCH_F16(f16, cnx_ln_kernel, ceil_div(M, 4), 256, 0, s, x, h->stem_nw.as<float>(), h->stem_nb.as<float>(), xh, M, S0.C, c.ln_eps);
+        const LnGammaBeta norm{h->stem_nw.as<float>(), h->stem_nb.as<float>()};
+        HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(M, 4), 256, 0, s, FromF32{x}, norm, ToF32And16{x, xh}, M, S0.C, c.ln_eps);
         const int64_t n4 = M * S0.C / 4;
         HIPTS_LAUNCH_F16(f16, sw_split_x_kernel, ceil_div(n4, 256), 256, 0, s, x, xh2, n4, S0.C);
     }
@@ -281,10 +217,12 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
             g.A = col; g.W = St.ds_w.as<bf16_t>(); g.M = M; g.N = C; g.K = 8 * Pv.C;
             g.bias = St.ds_b.as<float>(); g.out_f32 = x;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
-            HIPTS_LAUNCH_F16(f16, cnx_ln_kernel, ceil_div(M, 4), 256, 0, s, x, St.ds_nw.as<float>(), St.ds_nb.as<float>(), xh, M, C, c.ln_eps);
+            const LnGammaBeta norm{St.ds_nw.as<float>(), St.ds_nb.as<float>()};
+            HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(M, 4), 256, 0, s, FromF32{x}, norm, ToF32And16{x, xh}, (int64_t)M, C, c.ln_eps);
             const int64_t n4 = (int64_t)M * C / 4;
             HIPTS_LAUNCH_F16(f16, sw_split_x_kernel, ceil_div(n4, 256), 256, 0, s, x, xh2, n4, C);
         }
+        const AddToStreamHiLo to_stream{x, xh2, xh2 + C};       // x += LN(branch); xh2 = [hi | lo] of the new x
         for (SwBlock& B : St.blocks) {
             GemmArgs g = gemm_args();
             g.A = xh2; g.W = B.qkv2.as<bf16_t>(); g.M = M; g.N = 3 * C; g.K = 2 * C; g.bias = B.qkv_b.as<float>(); g.out_f32 = qkv;
@@ -293,7 +231,8 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
             g = gemm_args();
             g.A = ao; g.W = B.proj.as<bf16_t>(); g.M = M; g.N = C; g.K = C; g.bias = B.proj_b.as<float>(); g.out_f32 = br;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
-            HIPTS_LAUNCH_F16(f16, sw_postnorm_kernel, ceil_div(M, 4), 256, 0, s, br, B.n1_w.as<float>(), B.n1_b.as<float>(), x, xh2, M, C, c.ln_eps);
+            const LnGammaBeta norm1{B.n1_w.as<float>(), B.n1_b.as<float>()};
+            HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(M, 4), 256, 0, s, FromF32{br}, norm1, to_stream, (int64_t)M, C, c.ln_eps);
             g = gemm_args();
             g.A = xh2; g.W = B.fc1.as<bf16_t>(); g.M = M; g.N = St.hid; g.K = 2 * C; g.bias = B.fc1_b.as<float>();
             g.out_bf16 = m1; g.gelu_tanh = c.gelu_tanh;
@@ -301,7 +240,8 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
             g = gemm_args();
             g.A = m1; g.W = B.fc2.as<bf16_t>(); g.M = M; g.N = C; g.K = St.hid; g.bias = B.fc2_b.as<float>(); g.out_f32 = br;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
-            HIPTS_LAUNCH_F16(f16, sw_postnorm_kernel, ceil_div(M, 4), 256, 0, s, br, B.n2_w.as<float>(), B.n2_b.as<float>(), x, xh2, M, C, c.ln_eps);
+            const LnGammaBeta norm2{B.n2_w.as<float>(), B.n2_b.as<float>()};
+            HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(M, 4), 256, 0, s, FromF32{br}, norm2, to_stream, (int64_t)M, C, c.ln_eps);
         }
         if (si == stop_stage) return HIPTS_OK;
     }
@@ -310,7 +250,8 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
     const int64_t ML = (int64_t)batch * L.T;
     float* feat = h->feat.as<float>() + (size_t)i0 * L.C;
     bf16_t* feat2 = h->feat2.as<bf16_t>() + (size_t)i0 * 2 * L.C;
-    sw_ln_rows_kernel<<<ceil_div(ML, 4), 256, 0, s>>>(x, h->head_nw.as<float>(), h->head_nb.as<float>(), br, ML, L.C, c.ln_eps);
+    const LnGammaBeta head_norm{h->head_nw.as<float>(), h->head_nb.as<float>()};
+    row_ln_kernel<false><<<ceil_div(ML, 4), 256, 0, s>>>(FromF32{x}, head_norm, ToF32{br}, ML, L.C, c.ln_eps);
     HIPTS_LAUNCH_CHECK();
     sw_mean_kernel<<<batch, 256, 0, s>>>(br, feat, L.T, L.C);
     HIPTS_LAUNCH_CHECK();

@@ -19,6 +19,7 @@
 
 #include "vit_internal.h"
 #include "model_host.h"
+#include "row_ln.h"
 
 using namespace hipts;
 
@@ -179,66 +180,7 @@ __global__ __launch_bounds__(256) void patchify_f32_kernel(const float* __restri
     for (int c = 0; c < 3; ++c) {
         const float* src = x + (((int64_t)b * 3 + (2 - c)) * size + (py * P + ky)) * size + px * P;
         for (int kx = 0; kx < P; ++kx) {
-            const float v = src[kx];
-            const bf16_t hi = to_op<F16>(v);
-            dst[kx * 3 + c] = hi;
-            dst[K + kx * 3 + c] = to_op<F16>(v - from_op<F16>(hi));
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// LayerNorm over the last dim (eps inside the sqrt, biased variance -- torch F.layer_norm), one
-// wave per row, float4 loads, two-pass statistics in registers, bf16 output.  D % 4 == 0, D <= 1024.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-template <bool F16, bool OUT8 = false>
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                        const float* __restrict__ bta, bf16_t* __restrict__ out, int64_t rows,
-                                                        int D, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nvec = D >> 2;
-    const float4* xr = reinterpret_cast<const float4*>(x + row * D);
-    float4 v[4];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        v[i] = c < nvec ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-    const float mean = wave_sum(s) / (float)D;
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (lane + 64 * i < nvec) {
-            const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-            ss += (a * a + b * b) + (c * c + d * d);
-        }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(ss) / (float)D + eps);
-    const float4* gr = reinterpret_cast<const float4*>(g);
-    const float4* br = reinterpret_cast<const float4*>(bta);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec) {
-            const float4 gg = gr[c], bb = bta ? br[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (OUT8)
-                reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(out) + row * D)[c] =
-                    pack4_e4m3((v[i].x - mean) * rstd * gg.x + bb.x, (v[i].y - mean) * rstd * gg.y + bb.y,
-                               (v[i].z - mean) * rstd * gg.z + bb.z, (v[i].w - mean) * rstd * gg.w + bb.w);
-            else
-            *reinterpret_cast<bf16x4*>(out + row * D + 4 * c) =
-                pack4<F16>((v[i].x - mean) * rstd * gg.x + bb.x, (v[i].y - mean) * rstd * gg.y + bb.y,
-                           (v[i].z - mean) * rstd * gg.z + bb.z, (v[i].w - mean) * rstd * gg.w + bb.w);
+            split_hilo<F16>(src[kx], dst[kx * 3 + c], dst[K + kx * 3 + c]);
         }
     }
 }
@@ -273,25 +215,11 @@ __global__ __launch_bounds__(256) void pool_partial_kernel(const float* __restri
     if (t0 + wave < t1) load_row(t0 + wave, vn);
     for (int t = t0 + wave; t < t1; t += 4) {
         float4 v[4];
-        float s = 0.f;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[i] = vn[i];
-            s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-        }
+        for (int i = 0; i < 4; ++i) v[i] = vn[i];
         if (t + 4 < t1) load_row(t + 4, vn);
         float mean = 0.f, rstd = 1.f;
-        if (normalize) {
-            mean = wave_sum(s) / (float)D;
-            float ss = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (lane + 64 * i < nvec) {
-                    const float a = v[i].x - mean, bq = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-                    ss += (a * a + bq * bq) + (c * c + d * d);
-                }
-            rstd = 1.0f / sqrtf(wave_sum(ss) / (float)D + eps);
-        }
+        if (normalize) row_mean_rstd(v, lane, D, eps, mean, rstd);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             acc[i].x += (v[i].x - mean) * rstd;
@@ -351,10 +279,7 @@ __global__ __launch_bounds__(256) void pool_finalize_kernel(const float* __restr
     }
     for (int d = threadIdx.x; d < D; d += 256) {
         const float f = (feat[d] - mean) * rstd * g[d] + bta[d];
-        const bf16_t hi = to_op<F16>(f);
-        const bf16_t lo = to_op<F16>(f - from_op<F16>(hi));
-        out[(int64_t)b * 2 * D + d] = hi;
-        out[(int64_t)b * 2 * D + D + d] = lo;
+        split_hilo<F16>(f, out[(int64_t)b * 2 * D + d], out[(int64_t)b * 2 * D + D + d]);
     }
 }
 
@@ -701,7 +626,8 @@ int vit_run_images(hipts_vit* h, const void* in_dev, bool is_u8, int i0, int nb,
     };
     auto layernorm = [&](const float* gamma, const float* beta) -> int {
         ProfScope ps(h, s, PC_LAYERNORM, 0.0, dM * dD * 6);
-        HIPTS_LAUNCH_F16(f16, layernorm_kernel, ln_blocks, 256, 0, s, x, gamma, beta, xn, M, D, c.ln_eps);
+        const LnGammaOptBeta norm{gamma, beta};
+        HIPTS_LAUNCH_F16(f16, row_ln_kernel, ln_blocks, 256, 0, s, FromF32{x}, norm, To16{xn}, (int64_t)M, D, c.ln_eps);
         return HIPTS_OK;
     };
     // x += A W^T + b; with next_gamma also xn = 16bit(gamma * x) and the row statistics of x for the consumer of that norm
@@ -952,14 +878,16 @@ int launch_layernorm(const float* x, const float* g, const float* b, bf16_t* out
                      hipStream_t s) {
     HIPTS_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "layernorm: D=%d must be a multiple of 4, at most 1024", D);
     const int blocks = (int)((rows + 3) / 4);
-    HIPTS_LAUNCH_F16(f16, layernorm_kernel, blocks, 256, 0, s, x, g, b, out, rows, D, eps);
+    const LnGammaOptBeta norm{g, b};
+    HIPTS_LAUNCH_F16(f16, row_ln_kernel, blocks, 256, 0, s, FromF32{x}, norm, To16{out}, rows, D, eps);
     return HIPTS_OK;
 }
 
 int launch_layernorm8(const float* x, const float* g, const float* b, uint8_t* out, int64_t rows, int D, float eps, hipStream_t s) {
     HIPTS_REQUIRE(D % 4 == 0 && D >= 4 && D <= 1024, "layernorm: D=%d must be a multiple of 4, at most 1024", D);
     const int blocks = (int)((rows + 3) / 4);
-    layernorm_kernel<true, true><<<blocks, 256, 0, s>>>(x, g, b, reinterpret_cast<bf16_t*>(out), rows, D, eps);
+    const LnGammaOptBeta norm{g, b};
+    row_ln_kernel<false><<<blocks, 256, 0, s>>>(FromF32{x}, norm, ToE4m3{out}, rows, D, eps);
     HIPTS_LAUNCH_CHECK();
     return HIPTS_OK;
 }
