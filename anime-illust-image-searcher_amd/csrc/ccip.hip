@@ -81,49 +81,18 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // Stem patch matrix.  A0[m][(ky*7 + kx)*3 + c] = hi, A0[m][160 + ...] = lo of the normalised pixel at
 // (4 oy - 2 + ky, 4 ox - 2 + kx), zero outside the image (Conv2d padding = 2 pads the NORMALISED input).
-// U8: images uint8 NHWC RGB; /255 in float32, (x - mean) / std in float64, cast (gen_cfeatures.py:100-110,156) --
+// The float32 entry gathers it with patch_rows.h's patch_gather_kernel (Window7x7; the planes are read in
+// memory order, no BGR flip; one thread per (token, ky): 21 values; the pad columns 147..159 stay zero as allocated).
+// uint8 images (NHWC RGB): /255 in float32, (x - mean) / std in float64, cast (gen_cfeatures.py:100-110,156) --
 // 3 x 256 possible values, tabulated once on the host with exactly that arithmetic.
-// One thread per (token, ky): 21 values.
 // ---------------------------------------------------------------------------------------------
-template <bool U8, bool F16>
-__global__ __launch_bounds__(256) void stem_im2col_kernel(const void* __restrict__ img, const float* __restrict__ lut,
-                                                          bf16_t* __restrict__ a0, int batch, int S, int H0) {
-    // lut[c][u] = normalised value of byte u in channel c, built on the host with the reference's arithmetic
-    __shared__ float slut[3 * 256];
-    if constexpr (U8) {
-        for (int i = threadIdx.x; i < 3 * 256; i += 256) slut[i] = lut[i];
-        __syncthreads();
-    }
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t total = (int64_t)batch * H0 * H0 * 7;
-    if (idx >= total) return;
-    const int ky = (int)(idx % 7);
-    const int64_t m = idx / 7;
-    const int ox = (int)(m % H0), oy = (int)((m / H0) % H0), b = (int)(m / ((int64_t)H0 * H0));
-    const int iy = 4 * oy - 2 + ky;
-    bf16_t* row = a0 + m * STEM_K + ky * 21;
-    const bool iny = iy >= 0 && iy < S;
-#pragma unroll
-    for (int kx = 0; kx < 7; ++kx) {
-        const int ix = 4 * ox - 2 + kx;
-        const bool in = iny && ix >= 0 && ix < S;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float v = 0.f;
-            if (in) {
-                if constexpr (U8) v = slut[c * 256 + reinterpret_cast<const uint8_t*>(img)[(((int64_t)b * S + iy) * S + ix) * 3 + c]];
-                else v = reinterpret_cast<const float*>(img)[(((int64_t)b * 3 + c) * S + iy) * S + ix];
-            }
-            split_hilo<F16>(v, row[kx * 3 + c], row[STEM_KH + kx * 3 + c]);
-        }
-    }
-}
+static_assert(Window7x7::half() == STEM_KH, "the stem weight's half width");
 
 // The uint8 entry point's version: a workgroup owns 64 adjacent output pixels of one output row.  It loads
 // the 7 x (64*4+3) x 3 input bytes they touch with coalesced byte loads into LDS, builds the 64 patch rows
 // (hi | lo halves, zero pad columns included) in LDS through the normalisation table, and writes them out
 // as ONE contiguous 40 KB block with 16 B stores (consecutive pixels are consecutive rows of A0).  The
-// one-thread-per-kernel-row version above spends its time on scattered byte loads and 2-byte stores
+// one-thread-per-kernel-row gather spends its time on scattered byte loads and 2-byte stores
 // (628 us for 64 images).
 template <bool F16>
 __global__ __launch_bounds__(256) void stem_im2col_u8_kernel(const uint8_t* __restrict__ img, const float* __restrict__ lut,
@@ -273,16 +242,11 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
         if (is_u8) {
             const int xtiles = ceil_div(S0.H, 64);
             const int grid_u8 = batch * S0.H * xtiles;
-            if (f16) stem_im2col_u8_kernel<true><<<grid_u8, 256, 0, s>>>((const uint8_t*)in_dev, h->lut.as<float>(), a0, S, S0.H, xtiles);
-            else stem_im2col_u8_kernel<false><<<grid_u8, 256, 0, s>>>((const uint8_t*)in_dev, h->lut.as<float>(), a0, S, S0.H, xtiles);
+            HIPTS_LAUNCH_F16(f16, stem_im2col_u8_kernel, grid_u8, 256, 0, s, (const uint8_t*)in_dev, h->lut.as<float>(), a0, S, S0.H, xtiles);
         } else {
-            if (f16) stem_im2col_kernel<false, true><<<blocks, 256, 0, s>>>(in_dev, nullptr, a0, batch, S, S0.H);
-            else stem_im2col_kernel<false, false><<<blocks, 256, 0, s>>>(in_dev, nullptr, a0, batch, S, S0.H);
+            HIPTS_LAUNCH_F16(f16, patch_gather_kernel, blocks, 256, 0, s, PixelF32Planes<false>{(const float*)in_dev}, Window7x7{}, a0, M * 7, S, S0.H);
         }
-        HIPTS_LAUNCH_CHECK();
-        g = GemmArgs{};
-        g.f16 = f16;
-        g.shared_chip = shared_chip;
+        g = gemm_args(f16, shared_chip);
         g.A = a0; g.W = h->stem_w.as<bf16_t>(); g.M = (int)M; g.N = S0.C; g.K = STEM_K;
         g.bias = h->stem_b.as<float>(); g.out_f32 = x;
         xblk = stage_blocked(0);
@@ -307,9 +271,7 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
             const int64_t chunks = (int64_t)M * 9 * (Pv.C / 8);
             ds_im2col_kernel<<<ceil_div(chunks, 256), 256, 0, s>>>(xn, col, batch, Pv.H, Pv.C);
             HIPTS_LAUNCH_CHECK();
-            g = GemmArgs{};
-            g.f16 = f16;
-            g.shared_chip = shared_chip;
+            g = gemm_args(f16, shared_chip);
             g.A = col; g.W = St.ds_w.as<bf16_t>(); g.M = M; g.N = C; g.K = 9 * Pv.C;
             g.bias = St.ds_b.as<float>(); g.out_f32 = x;
             xblk = stage_blocked(si);           // (the norm above read the previous stage's layout)
@@ -362,9 +324,7 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
                                       : (si < 3 ? h->st[si + 1].ds_norm.as<float>() : nullptr);
             if (!B.attn) {
                 // SepConv: 1x1 (C -> 2C) + StarReLU -> depthwise 7x7 -> 1x1 (2C -> C) + residual
-                g = GemmArgs{};
-                g.f16 = f16;
-                g.shared_chip = shared_chip;
+                g = gemm_args(f16, shared_chip);
                 g.A = xn; g.W = B.w_in.as<bf16_t>(); g.M = M; g.N = 2 * C; g.K = C; g.bias = zeros;
                 g.out_bf16 = h1; g.star_scale = B.s1; g.star_bias = B.b1;
                 HIPTS_TRY(gemm(EPI_STAR, g, s));
@@ -372,25 +332,19 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
                 const int dw_grid = batch * tiles_y * tiles_x * (2 * C / DW_CS);
                 if (f16 && H >= 16 && dw_mfma && B.dwz.p) HIPTS_TRY(launch_dwconv7_mfma(h1, B.dwz.as<uint32_t>(), h2, batch, H, 2 * C, dw_mfma, s));
                 else HIPTS_LAUNCH_F16(f16, dwconv7_kernel, dw_grid, 256, DW_LDS_BYTES, s, h1, B.dw.as<float>(), h2, H, 2 * C, tiles_x, tiles_y);
-                g = GemmArgs{};
-                g.f16 = f16;
-                g.shared_chip = shared_chip;
+                g = gemm_args(f16, shared_chip);
                 g.A = h2; g.W = B.w_out.as<bf16_t>(); g.M = M; g.N = C; g.K = 2 * C; g.bias = zeros; g.out_f32 = x;
                 HIPTS_TRY(residual(g, B.has_rs1 ? B.rs1.as<float>() : nullptr, fuse_ln ? B.n2.as<float>() : nullptr));
             } else {
                 const int heads = C / c.head_dim;
-                g = GemmArgs{};
-                g.f16 = f16;
-                g.shared_chip = shared_chip;
+                g = gemm_args(f16, shared_chip);
                 g.A = xn; g.W = B.w_in.as<bf16_t>(); g.M = M; g.N = 2 * C; g.K = C; g.bias = zeros;
                 g.out_bf16 = qb; g.out2_bf16 = kb;
                 g.tokens = T; g.tokens_pad = Tp; g.heads = heads; g.dim = C; g.hd_log2 = 5;
                 g.qscale = 0.17677669529663687f * 1.4426950408889634f;      // 32^-0.5 * log2(e): attention works in base 2
                 if (in_folded) folded(g, B.u_qk.as<float>());
                 HIPTS_TRY(gemm(EPI_QK, g, s));
-                g = GemmArgs{};
-                g.f16 = f16;
-                g.shared_chip = shared_chip;
+                g = gemm_args(f16, shared_chip);
                 g.A = xn; g.W = B.w_in.as<bf16_t>() + (size_t)2 * C * C; g.M = M; g.N = C; g.K = C; g.bias = zeros;
                 g.out_bf16 = vb;
                 g.tokens = T; g.tokens_pad = Tp; g.heads = heads; g.dim = C; g.hd_log2 = 5;
@@ -398,9 +352,7 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
                 HIPTS_TRY(gemm(EPI_VT, g, s));
                 HIPTS_TRY(launch_attention(qb, kb, vb, h1, batch, heads, T, Tp,
                                            f16, s, 32));
-                g = GemmArgs{};
-                g.f16 = f16;
-                g.shared_chip = shared_chip;
+                g = gemm_args(f16, shared_chip);
                 g.A = h1; g.W = B.w_out.as<bf16_t>(); g.M = M; g.N = C; g.K = C; g.bias = zeros; g.out_f32 = x;
                 if (fold23) HIPTS_TRY(residual_xg(g, B.has_rs1 ? B.rs1.as<float>() : nullptr, B.n2.as<float>()));
                 else HIPTS_TRY(residual(g, B.has_rs1 ? B.rs1.as<float>() : nullptr, fuse_ln ? B.n2.as<float>() : nullptr));
@@ -416,16 +368,12 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
                 xn_ready = fuse_next;
                 continue;
             }
-            g = GemmArgs{};
-            g.f16 = f16;
-            g.shared_chip = shared_chip;
+            g = gemm_args(f16, shared_chip);
             g.A = xn; g.W = B.fc1.as<bf16_t>(); g.M = M; g.N = 4 * C; g.K = C; g.bias = zeros;
             g.out_bf16 = m1; g.star_scale = B.s2; g.star_bias = B.b2;
             if (mlp_folded) folded(g, B.u_fc1.as<float>());
             HIPTS_TRY(gemm(EPI_STAR, g, s));
-            g = GemmArgs{};
-            g.f16 = f16;
-            g.shared_chip = shared_chip;
+            g = gemm_args(f16, shared_chip);
             g.A = m1; g.W = B.fc2.as<bf16_t>(); g.M = M; g.N = C; g.K = 4 * C; g.bias = zeros; g.out_f32 = x;
             const bool fuse_next = fuse_ln && next_gamma != nullptr;
             // folded: the next block's norm1 (same stage: an attention block too) is prepared here
@@ -438,7 +386,8 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
     }
     // ---- head: global average pool -> LayerNorm
     const Stage& L = h->st[3];
-    pool_ln_kernel<<<batch, 1024, 0, s>>>(x, h->head_g.as<float>(), h->head_b.as<float>(), f_dev + (size_t)i0 * L.C, L.T, L.C, c.ln_eps, xblk ? 1 : 0);
+    pool_ln_kernel<false><<<batch, 1024, 0, s>>>(x, h->head_g.as<float>(), h->head_b.as<float>(), PooledF32{f_dev + (size_t)i0 * L.C}, L.T, L.C, c.ln_eps,
+                                                 xblk ? 1 : 0, L.T);
     HIPTS_LAUNCH_CHECK();
     return HIPTS_OK;
 }

@@ -1,8 +1,8 @@
 // convnet.h -- kernels shared by the convolutional forwards (ccip.hip: the CAFormer encoder; convnext.hip: the ConvNeXt tagger;
 // swinv2.hip: the SwinV2 tagger's stem): the depthwise 7x7 convolution (VALU and matrix-core forms, and the Toeplitz lane images of its
-// weights), the pooled LayerNorm head, and the 4 x 4 patch stem.  The per-row LayerNorm (row_ln_kernel), the wave reduction and the
-// hi | lo split come with row_ln.h.  Everything lives in an anonymous namespace, so each including object gets its own copy under the
-// same symbol names.
+// weights).  The per-row LayerNorm (row_ln_kernel), the pooled LayerNorm head (pool_ln_kernel), the wave reduction and the hi | lo
+// split come with row_ln.h, the 4 x 4 patch stem of the ConvNeXt and SwinV2 taggers with patch_rows.h.  Everything lives in an
+// anonymous namespace, so each including object gets its own copy under the same symbol names.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -11,6 +11,7 @@
 
 #include "vit_internal.h"
 #include "row_ln.h"
+#include "patch_rows.h"
 
 namespace {
 
@@ -369,111 +370,13 @@ std::vector<uint32_t> dw_toeplitz_lanes(const float* w, int channels) {
     return tzv;
 }
 
-// Head: out[b][:] = LN(mean over the T tokens of x[b])  (with bias).  One 1024-thread workgroup per image:
-// four row groups x 256 channel threads sum a quarter of the tokens each (the loop is load-latency bound,
-// so more rows in flight is what matters), partial sums meet in LDS, the first 256 threads normalise.
-__global__ __launch_bounds__(1024) void pool_ln_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                       const float* __restrict__ bta, float* __restrict__ out, int T, int C, float eps, int blk) {
-    __shared__ float part[4][1024];
-    __shared__ float red[4];
-    const int b = blockIdx.x, tid = threadIdx.x & 255, rg = threadIdx.x >> 8;
-    const float* xb = x + (int64_t)b * T * C;
-    float m[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int r = rg; r < T; r += 4)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = tid + 256 * u;
-            if (c < C) m[u] += blk ? xb[((((int64_t)(r >> 4) * (C >> 4)) + (c >> 4)) << 8) + (r & 15) * 16 + (c & 15)] : xb[(int64_t)r * C + c];
-        }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) part[rg][tid + 256 * u] = m[u];
-    __syncthreads();
-    // (every thread keeps walking to the barriers; only row group 0 does the arithmetic)
-    float s = 0.f;
-    if (rg == 0) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = tid + 256 * u;
-            m[u] = ((part[0][c] + part[1][c]) + (part[2][c] + part[3][c])) / (float)T;
-            if (c < C) s += m[u];
-        }
-        s = wave_sum(s);
-        if ((tid & 63) == 0) red[tid >> 6] = s;
-    }
-    __syncthreads();
-    const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)C;
-    __syncthreads();
-    if (rg == 0) {
-        float ss = 0.f;
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (tid + 256 * u < C) ss += (m[u] - mean) * (m[u] - mean);
-        ss = wave_sum(ss);
-        if ((tid & 63) == 0) red[tid >> 6] = ss;
-    }
-    __syncthreads();
-    if (rg != 0) return;
-    const float rstd = 1.0f / sqrtf((red[0] + red[1] + red[2] + red[3]) / (float)C + eps);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int c = tid + 256 * u;
-        if (c < C) out[(int64_t)b * C + c] = (m[u] - mean) * rstd * g[c] + bta[c];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The 4 x 4 s4 patch stem, shared by the ConvNeXt (convnext.hip) and SwinV2 (swinv2.hip) taggers (its LayerNorm, in place with the
-// 16-bit copy, is row_ln_kernel with FromF32 / LnGammaBeta / ToF32And16), and the hi | lo split of the pooled features in front of their
-// head GEMM.
-// ---------------------------------------------------------------------------------------------
+// The 4 x 4 s4 patch stem shared by the ConvNeXt (convnext.hip) and SwinV2 (swinv2.hip) taggers is patch_gather_kernel with Window4x4
+// (patch_rows.h; its LayerNorm, in place with the 16-bit copy, is row_ln_kernel with FromF32 / LnGammaBeta / ToF32And16): A0[m][(ky*4 +
+// kx)*3 + c] = hi, A0[m][64 + ...] = lo of the normalised pixel (4 oy + ky, 4 ox + kx) of memory channel c (RGB), columns 48..63 of each
+// half zero.  uint8 images go through the normalisation table lut[c][u] (built on the host from the configuration's mean / std), a
+// float32 input is already normalised and BGR.
 constexpr int CNX_STEM_KH = 64;                  // 4*4*3 = 48 taps padded to 64; K = hi | lo = 128
 constexpr int CNX_STEM_K = 2 * CNX_STEM_KH;
-
-// Stem patch matrix: A0[m][(ky*4 + kx)*3 + c] = hi, A0[m][64 + ...] = lo of the normalised pixel (4 oy + ky, 4 ox + kx) of memory
-// channel c (RGB); the BGR order of the model lives in the weight permutation.  Columns 48..63 of each half are zero.
-// U8: images uint8 NHWC RGB through the normalisation table lut[c][u] (built on the host from the configuration's mean / std);
-// F32: float32 [B][3][S][S], already normalised, BGR (channel 2 - c holds memory channel c).
-// One thread per (token, ky): 12 values.
-// ---------------------------------------------------------------------------------------------
-template <bool U8, bool F16>
-__global__ __launch_bounds__(256) void cnx_stem_kernel(const void* __restrict__ img, const float* __restrict__ lut, bf16_t* __restrict__ a0,
-                                                       int64_t total, int S, int H0) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int ky = (int)(idx & 3);
-    const int64_t m = idx >> 2;
-    const int ox = (int)(m % H0), oy = (int)((m / H0) % H0);
-    const int64_t b = m / ((int64_t)H0 * H0);
-    bf16_t* row = a0 + m * CNX_STEM_K;
-    const int iy = 4 * oy + ky;
-#pragma unroll
-    for (int kx = 0; kx < 4; ++kx) {
-        const int ix = 4 * ox + kx;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float v;
-            if constexpr (U8) v = lut[c * 256 + reinterpret_cast<const uint8_t*>(img)[((b * S + iy) * S + ix) * 3 + c]];
-            else v = reinterpret_cast<const float*>(img)[((b * 3 + (2 - c)) * S + iy) * (int64_t)S + ix];
-            split_hilo<F16>(v, row[(ky * 4 + kx) * 3 + c], row[CNX_STEM_KH + (ky * 4 + kx) * 3 + c]);
-        }
-    }
-    if (ky == 0) {
-#pragma unroll
-        for (int k = 48; k < CNX_STEM_KH; ++k) {
-            row[k] = to_op<F16>(0.f);
-            row[CNX_STEM_KH + k] = to_op<F16>(0.f);
-        }
-    }
-}
-
-// Pooled features as hi | lo halves (the head GEMM runs K = 2 C against [W | W]): f2[b][c] = hi, f2[b][C + c] = lo.
-template <bool F16>
-__global__ __launch_bounds__(256) void cnx_split_kernel(const float* __restrict__ f, bf16_t* __restrict__ f2, int batch, int C) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= batch * C) return;
-    const int b = i / C, c = i - b * C;
-    split_hilo<F16>(f[i], f2[(size_t)b * 2 * C + c], f2[(size_t)b * 2 * C + C + c]);
-}
+static_assert(Window4x4::half() == CNX_STEM_KH, "the stem weight's half width");
 
 }  // namespace

@@ -10,8 +10,8 @@
 // operands 16-bit (bf16, or IEEE half with operand_f16 bit 0).  Every 1 x 1 convolution / Linear is the shared persistent MFMA
 // GEMM (gemm.hip) with a fused epilogue:
 //   stem 4x4 s4      patch gather (hi | lo halves against [W | W], K = 2 x 64)  -> EPI_BIAS, then LayerNorm with bias in place
-//                    (convnet.h: cnx_stem_kernel; row_ln.h: row_ln_kernel, whose ToF32And16 sink also writes the 16-bit copy of x the
-//                    first depthwise convolution reads)
+//                    (patch_rows.h: patch_gather_kernel with Window4x4; row_ln.h: row_ln_kernel, whose ToF32And16 sink also writes the
+//                    16-bit copy of x the first depthwise convolution reads)
 //   downsample       LayerNorm fused with the 2 x 2 s2 gather (row_ln_kernel with the ToPatch2x2 sink writes the GEMM's A matrix: every
 //                    token is normalised once and lands in one row) -> EPI_BIAS, 16-bit copy
 //   depthwise 7x7    convnet.h: the matrix-core kernel (half operands, side >= 16) or the VALU kernel; then row_ln_kernel with the
@@ -21,7 +21,7 @@
 //   fc2              EPI_RESID_LS: x += gamma * (acc + b2) in fp32 -- the layer scale is NOT folded into W2 (timm initialises it at
 //                    1e-6, and gamma W2 rounded to half lands in the subnormal range, which the MFMA reads as zero) -- and the 16-bit
 //                    copy of the new x, the next block's depthwise input
-//   head             pool_ln_kernel (convnet.h) -> hi | lo split -> EPI_HEAD (logits and sigmoid)
+//   head             pool_ln_kernel with the PooledHiLo sink (convnet.h) -> EPI_HEAD (logits and sigmoid)
 // Every kernel choice is a function of the configuration and the stage only; an image's bits do not depend on the batch or the
 // sub-batch split (tests/test_gpu_convnext.py).
 #include <algorithm>
@@ -61,7 +61,7 @@ struct hipts_convnext {
     DevBuf stem_w, stem_b, stem_nw, stem_nb, head_nw, head_nb, head_w, head_b, lut;
     TensorLedger ledger;
     // workspace (sized for cfg.max_batch), carved per image with the stride of the largest stage
-    DevBuf img_in, a0, x, xh, dwo, xn, m1, col, feat, feat2, logits, probs;
+    DevBuf img_in, a0, x, xh, dwo, xn, m1, col, feat2, logits, probs;
     size_t px = 0, p4c = 0, pcol = 0;
     SubStreams<2> streams;
     double flops_per_image = 0.0;
@@ -95,27 +95,16 @@ int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, in
     bf16_t* m1 = h->m1.as<bf16_t>() + (size_t)i0 * h->p4c;
     bf16_t* col = h->col.as<bf16_t>() + (size_t)i0 * h->pcol;
     bf16_t* a0 = h->a0.as<bf16_t>() + (size_t)i0 * h->st[0].T * CNX_STEM_K;
-    auto gemm_args = [&]() {
-        GemmArgs g{};
-        g.f16 = f16;
-        g.shared_chip = shared_chip;
-        return g;
-    };
 
     // ---- stem: conv 4x4 s4 (+bias) -> LayerNorm (weight, bias) = the residual stream of stage 0
     {
         const CnxStage& S0 = h->st[0];
         const int64_t M = (int64_t)batch * S0.T;
         const int blocks = ceil_div(M * 4, 256);
-        if (is_u8) {
-            if (f16) cnx_stem_kernel<true, true><<<blocks, 256, 0, s>>>(in_dev, h->lut.as<float>(), a0, M * 4, S, S0.H);
-            else cnx_stem_kernel<true, false><<<blocks, 256, 0, s>>>(in_dev, h->lut.as<float>(), a0, M * 4, S, S0.H);
-        } else {
-            if (f16) cnx_stem_kernel<false, true><<<blocks, 256, 0, s>>>(in_dev, nullptr, a0, M * 4, S, S0.H);
-            else cnx_stem_kernel<false, false><<<blocks, 256, 0, s>>>(in_dev, nullptr, a0, M * 4, S, S0.H);
-        }
-        HIPTS_LAUNCH_CHECK();
-        GemmArgs g = gemm_args();
+        const PixelU8Table from_u8{(const uint8_t*)in_dev, h->lut.as<float>()};
+        const PixelF32Planes<true> from_f32{(const float*)in_dev};
+        HIPTS_LAUNCH_U8_F16(is_u8, f16, patch_gather_kernel, blocks, 256, 0, s, from_u8, from_f32, Window4x4{}, a0, M * 4, S, S0.H);
+        GemmArgs g = gemm_args(f16, shared_chip);
         g.A = a0; g.W = h->stem_w.as<bf16_t>(); g.M = (int)M; g.N = S0.C; g.K = CNX_STEM_K;
         g.bias = h->stem_b.as<float>(); g.out_f32 = x;
         HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
@@ -133,7 +122,7 @@ int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, in
             const int64_t rows_in = (int64_t)batch * Pv.T;
             const LnGammaBeta norm{St.ds_nw.as<float>(), St.ds_nb.as<float>()};
             HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(rows_in, 4), 256, 0, s, FromF32{x}, norm, ToPatch2x2{col, Pv.H}, rows_in, Pv.C, c.ln_eps);
-            GemmArgs g = gemm_args();
+            GemmArgs g = gemm_args(f16, shared_chip);
             g.A = col; g.W = St.ds_w.as<bf16_t>(); g.M = M; g.N = C; g.K = 4 * Pv.C;
             g.bias = St.ds_b.as<float>(); g.out_f32 = x;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
@@ -153,11 +142,11 @@ int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, in
             const From16Bias dw{dwo, B.dw_b.as<float>()};
             const LnGammaBeta norm{B.n_w.as<float>(), B.n_b.as<float>()};
             HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(M, 4), 256, 0, s, dw, norm, To16{xn}, (int64_t)M, C, c.ln_eps);
-            GemmArgs g = gemm_args();
+            GemmArgs g = gemm_args(f16, shared_chip);
             g.A = xn; g.W = B.fc1.as<bf16_t>(); g.M = M; g.N = 4 * C; g.K = C; g.bias = B.fc1_b.as<float>();
             g.out_bf16 = m1; g.gelu_tanh = 0;
             HIPTS_TRY(launch_gemm(EPI_GELU, g, s));
-            g = gemm_args();
+            g = gemm_args(f16, shared_chip);
             g.A = m1; g.W = B.fc2.as<bf16_t>(); g.M = M; g.N = C; g.K = 4 * C; g.bias = B.fc2_b.as<float>();
             g.out_f32 = x; g.res_scale = B.gamma.as<float>(); g.out_bf16 = xh;
             HIPTS_TRY(launch_gemm(EPI_RESID_LS, g, s));
@@ -166,12 +155,10 @@ int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, in
     }
     // ---- head: mean over tokens -> LayerNorm (weight, bias) -> hi | lo -> fc (+bias) with sigmoid
     const CnxStage& L = h->st[3];
-    float* feat = h->feat.as<float>() + (size_t)i0 * L.C;
     bf16_t* feat2 = h->feat2.as<bf16_t>() + (size_t)i0 * 2 * L.C;
-    pool_ln_kernel<<<batch, 1024, 0, s>>>(x, h->head_nw.as<float>(), h->head_nb.as<float>(), feat, L.T, L.C, c.ln_eps, 0);
-    HIPTS_LAUNCH_CHECK();
-    HIPTS_LAUNCH_F16(f16, cnx_split_kernel, ceil_div((int64_t)batch * L.C, 256), 256, 0, s, feat, feat2, batch, L.C);
-    GemmArgs g = gemm_args();
+    HIPTS_LAUNCH_F16(f16, pool_ln_kernel, batch, 1024, 0, s, x, h->head_nw.as<float>(), h->head_nb.as<float>(), PooledHiLo{feat2}, L.T, L.C, c.ln_eps, 0,
+                     L.T);
+    GemmArgs g = gemm_args(f16, shared_chip);
     g.A = feat2; g.W = h->head_w.as<bf16_t>(); g.M = batch; g.N = c.num_classes; g.K = 2 * L.C;
     g.bias = h->head_b.as<float>(); g.out_f32 = lg ? lg + (size_t)i0 * c.num_classes : nullptr;
     g.out2_f32 = pr ? pr + (size_t)i0 * c.num_classes : nullptr;
@@ -256,7 +243,7 @@ int hipts_convnext_create(const hipts_convnext_config_t* cfg, int device, hipts_
     if ((st = upload_f32(h->lut, lut.data(), lut.size())) || (st = h->a0.alloc((size_t)B * h->st[0].T * CNX_STEM_K * 2)) ||
         (st = h->x.alloc((size_t)B * h->px * 4)) || (st = h->xh.alloc((size_t)B * h->px * 2)) || (st = h->dwo.alloc((size_t)B * h->px * 2)) ||
         (st = h->xn.alloc((size_t)B * h->px * 2)) || (st = h->m1.alloc((size_t)B * h->p4c * 2)) || (st = h->col.alloc((size_t)B * h->pcol * 2)) ||
-        (st = h->feat.alloc((size_t)B * C3 * 4)) || (st = h->feat2.alloc((size_t)B * 2 * C3 * 2)) ||
+        (st = h->feat2.alloc((size_t)B * 2 * C3 * 2)) ||
         (st = h->logits.alloc((size_t)B * cfg->num_classes * 4)) || (st = h->probs.alloc((size_t)B * cfg->num_classes * 4))) {
         delete h;
         return st;
@@ -307,7 +294,7 @@ int hipts_convnext_set_tensor(hipts_convnext_t* h, const char* key_c, const floa
     std::string sub, t;
     if (key == "stem.0.weight") {
         EXPECT_NUMEL((int64_t)C0 * 48);
-        const std::vector<float> w2 = stem_weight_hilo(data, C0, 16, CNX_STEM_KH, true);      // BGR; the hi | lo halves of cnx_stem_kernel
+        const std::vector<float> w2 = stem_weight_hilo(data, C0, 16, CNX_STEM_KH, true);      // BGR; the hi | lo halves of patch_gather_kernel
         st = upload_matrix16(h->stem_w, w2.data(), C0, CNX_STEM_K, round_up(C0, 256), f16);
     } else if (key == "stem.0.bias") { EXPECT_NUMEL(C0); st = upload_f32(h->stem_b, data, C0); }
     else if (key == "stem.1.weight") { EXPECT_NUMEL(C0); st = upload_f32(h->stem_nw, data, C0); }

@@ -23,6 +23,7 @@
 #include "vit_internal.h"
 #include "model_host.h"
 #include "row_ln.h"
+#include "patch_rows.h"
 
 using namespace hipts;
 
@@ -58,37 +59,6 @@ struct hipts_eva {
 };
 
 namespace {
-
-// Patch matrix, hi | lo halves of the normalised pixel (K = 2 PK, PK = P*P*3 rounded up to 64, pad columns stay
-// zero).  Column (ky*P + kx)*3 + c holds memory channel c (RGB); the BGR flip of tagging.py:243 lives in the
-// weight permutation.  U8: ToTensor (/255) and Normalize ((x - .5) / .5) in float32 like the reference.
-template <bool U8, bool F16>
-__global__ __launch_bounds__(256) void eva_patchify_kernel(const void* __restrict__ img, bf16_t* __restrict__ a0, int batch, int S, int P,
-                                                           int grid, int PK) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t total = (int64_t)batch * grid * grid * P;
-    if (idx >= total) return;
-    const int ky = (int)(idx % P);
-    const int64_t tok = idx / P;
-    const int px = (int)(tok % grid), py = (int)((tok / grid) % grid);
-    const int64_t b = tok / ((int64_t)grid * grid);
-    bf16_t* dst = a0 + tok * (int64_t)(2 * PK) + ky * P * 3;
-    const int iy = py * P + ky;
-    for (int kx = 0; kx < P; ++kx) {
-        const int ix = px * P + kx;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float v;
-            if constexpr (U8) {
-                const float u = (float)reinterpret_cast<const uint8_t*>(img)[((b * S + iy) * S + ix) * 3 + c];
-                v = (u / 255.0f - 0.5f) / 0.5f;
-            } else {
-                v = reinterpret_cast<const float*>(img)[((b * 3 + (2 - c)) * S + iy) * (int64_t)S + ix];
-            }
-            split_hilo<F16>(v, dst[kx * 3 + c], dst[PK + kx * 3 + c]);
-        }
-    }
-}
 
 // x[b*TS + 0] = cls + pos[0]; x[b*TS + 1 + t] = tmp[b*np + t] (conv + bias + pos[1 + t], from the GEMM epilogue);
 // x[b*TS + T .. TS) = 0.   One thread per float4.
@@ -134,61 +104,6 @@ __global__ __launch_bounds__(256) void eva_colsum_kernel(const float* __restrict
         acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
     }
     reinterpret_cast<float4*>(part + ((int64_t)b * POOL_SPLITS + split) * D)[tid] = acc;
-}
-
-// pooled2[b] = hi | lo of fc_norm(mean over the patch tokens of x[b]) from the POOL_SPLITS partial row sums.  One
-// 1024-thread workgroup per image; x = part, np = POOL_SPLITS rows, TS = POOL_SPLITS, first row 0, count = patch tokens.
-template <bool F16>
-__global__ __launch_bounds__(1024) void eva_pool_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ bta,
-                                                        bf16_t* __restrict__ out, int np, int TS, int D, float eps, int count) {
-    __shared__ float part[4][1024];
-    __shared__ float red[4];
-    const int b = blockIdx.x, tid = threadIdx.x & 255, rg = threadIdx.x >> 8;
-    const float* xb = x + (int64_t)b * TS * D;
-    float m[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int r = rg; r < np; r += 4)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = tid + 256 * u;
-            if (c < D) m[u] += xb[(int64_t)r * D + c];
-        }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) part[rg][tid + 256 * u] = m[u];
-    __syncthreads();
-    float s = 0.f;
-    if (rg == 0) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int c = tid + 256 * u;
-            m[u] = ((part[0][c] + part[1][c]) + (part[2][c] + part[3][c])) / (float)count;
-            if (c < D) s += m[u];
-        }
-        s = wave_sum(s);
-        if ((tid & 63) == 0) red[tid >> 6] = s;
-    }
-    __syncthreads();
-    const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)D;
-    __syncthreads();
-    if (rg == 0) {
-        float ss = 0.f;
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (tid + 256 * u < D) ss += (m[u] - mean) * (m[u] - mean);
-        ss = wave_sum(ss);
-        if ((tid & 63) == 0) red[tid >> 6] = ss;
-    }
-    __syncthreads();
-    if (rg != 0) return;
-    const float rstd = 1.0f / sqrtf((red[0] + red[1] + red[2] + red[3]) / (float)D + eps);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int c = tid + 256 * u;
-        if (c < D) {
-            const float f = (m[u] - mean) * rstd * g[c] + bta[c];
-            split_hilo<F16>(f, out[(int64_t)b * 2 * D + c], out[(int64_t)b * 2 * D + D + c]);
-        }
-    }
 }
 
 // rows x cols float block -> 16-bit operand bits at row offset `row0` of a [*, ld] matrix that was allocated zeroed
@@ -240,17 +155,13 @@ int eva_run_images(hipts_eva* h, const void* in_dev, bool is_u8, int i0, int bat
     {
         const int64_t total = (int64_t)batch * np * P;
         const int blocks = ceil_div(total, 256);
-        if (is_u8) {
-            if (f16) eva_patchify_kernel<true, true><<<blocks, 256, 0, s>>>(in_dev, a0_p, batch, S, P, h->grid, h->PK);
-            else eva_patchify_kernel<true, false><<<blocks, 256, 0, s>>>(in_dev, a0_p, batch, S, P, h->grid, h->PK);
-        } else {
-            if (f16) eva_patchify_kernel<false, true><<<blocks, 256, 0, s>>>(in_dev, a0_p, batch, S, P, h->grid, h->PK);
-            else eva_patchify_kernel<false, false><<<blocks, 256, 0, s>>>(in_dev, a0_p, batch, S, P, h->grid, h->PK);
-        }
-        HIPTS_LAUNCH_CHECK();
-        g = GemmArgs{};
-        g.f16 = f16;
-        g.shared_chip = shared_chip;
+        // patch matrix, hi | lo halves of the normalised pixel (K = 2 PK, PK = P*P*3 rounded up to 64; the pad columns stay zero as
+        // allocated).  uint8: ToTensor and Normalize in float32 like the reference; float32: already BGR, the flip of tagging.py:243
+        // lives in the weight permutation
+        const PixelU8Affine from_u8{(const uint8_t*)in_dev};
+        const PixelF32Planes<true> from_f32{(const float*)in_dev};
+        HIPTS_LAUNCH_U8_F16(is_u8, f16, patch_gather_kernel, blocks, 256, 0, s, from_u8, from_f32, WindowPatch{P, h->PK}, a0_p, total, S, h->grid);
+        g = gemm_args(f16, shared_chip);
         g.A = a0_p; g.W = h->patch_w.as<bf16_t>(); g.M = batch * np; g.N = D; g.K = 2 * h->PK;
         g.bias = h->patch_b.as<float>(); g.out_f32 = tmp_p; g.pos = h->pos.as<float>() + D; g.tokens = np; g.qscale = 1.0f;
         HIPTS_TRY(launch_gemm(EPI_PATCH, g, s));
@@ -271,9 +182,7 @@ int eva_run_images(hipts_eva* h, const void* in_dev, bool is_u8, int i0, int bat
         EvaLayer& L = h->layers[li];
         const bool ln1_folded = fold && li > 0;
         if (!ln1_folded) HIPTS_TRY(launch_layernorm(li == 0 ? x0 : x, L.ln1_g.as<float>(), L.ln1_b.as<float>(), xn, M, D, c.ln_eps, f16, s));
-        g = GemmArgs{};
-        g.f16 = f16;
-        g.shared_chip = shared_chip;
+        g = gemm_args(f16, shared_chip);
         g.A = xn; g.W = L.qkv_w.as<bf16_t>(); g.M = M; g.N = 3 * D; g.K = D; g.bias = L.qkv_b.as<float>();
         g.out_bf16 = q_p; g.out2_bf16 = k_p; g.out3_bf16 = v_p;       // one launch: q and k rotated, v as it is, all [image][head][token][64]
         g.tokens = TS; g.tokens_pad = Tp; g.heads = H; g.dim = D;
@@ -282,9 +191,7 @@ int eva_run_images(hipts_eva* h, const void* in_dev, bool is_u8, int i0, int bat
         if (ln1_folded) folded(g, L.qkv_u.as<float>(), L.qkv_c.as<float>());
         HIPTS_TRY(launch_gemm(EPI_QK_ROPE, g, s));
         HIPTS_TRY(launch_attention2(q_p, k_p, v_p, att_p, batch, H, T, Tp, f16, s, TS, 0, h->split_att ? 1 : 0, split_lo_scale(f16)));
-        g = GemmArgs{};
-        g.f16 = f16;
-        g.shared_chip = shared_chip;
+        g = gemm_args(f16, shared_chip);
         g.A = att_p; g.W = L.proj_w.as<bf16_t>(); g.M = M; g.N = D; g.K = att_k; g.bias = L.proj_b.as<float>(); g.out_f32 = x;
         g.x_blocked = xb ? 1 : 0;
         g.sk_ws = h->sk_ws.as<char>() + (size_t)sub * GEMM_SK_WS_BYTES; g.sk_ws_bytes = GEMM_SK_WS_BYTES;      // split-K when the launch under-fills the chip
@@ -295,9 +202,7 @@ int eva_run_images(hipts_eva* h, const void* in_dev, bool is_u8, int i0, int bat
             HIPTS_TRY(launch_gemm(EPI_RESID, g, s));
             HIPTS_TRY(launch_layernorm(x, L.ln2_g.as<float>(), L.ln2_b.as<float>(), xn, M, D, c.ln_eps, f16, s));
         }
-        g = GemmArgs{};
-        g.f16 = f16;
-        g.shared_chip = shared_chip;
+        g = gemm_args(f16, shared_chip);
         // fc1_g and fc1_x in one launch (rows interleaved per 32 hidden units); silu(gate) * value in the epilogue
         g.A = xn; g.W = L.gx_w.as<bf16_t>(); g.M = M; g.N = 2 * h->HK; g.K = D; g.bias = L.gx_b.as<float>();
         g.out_bf16 = g1_p; g.ld_out = h->HK;
@@ -307,9 +212,7 @@ int eva_run_images(hipts_eva* h, const void* in_dev, bool is_u8, int i0, int bat
         HIPTS_TRY(launch_gemm(EPI_SWIGLU, g, s));
         // (round 3) no rowstat kernel between the two GEMMs: the SwiGLU epilogue leaves ONE partial pair per (256-column tile, row) -- the four
         // waves of a row meet in LDS -- and fc2's workgroups finish the 22 pairs of their tile's rows into an LDS table before their epilogue
-        g = GemmArgs{};
-        g.f16 = f16;
-        g.shared_chip = shared_chip;
+        g = gemm_args(f16, shared_chip);
         g.A = g1_p; g.W = L.fc2_w.as<bf16_t>(); g.M = M; g.N = D; g.K = h->HK; g.bias = L.fc2_c.as<float>(); g.out_f32 = x;
         g.x_blocked = xb ? 1 : 0;
         g.sk_ws = h->sk_ws.as<char>() + (size_t)sub * GEMM_SK_WS_BYTES; g.sk_ws_bytes = GEMM_SK_WS_BYTES;
@@ -331,10 +234,10 @@ int eva_run_images(hipts_eva* h, const void* in_dev, bool is_u8, int i0, int bat
     }
     float* part_p = h->pool_part.as<float>() + (size_t)i0 * POOL_SPLITS * D;
     eva_colsum_kernel<<<dim3(POOL_SPLITS, batch), 256, 0, s>>>(xb ? x_rm : x, part_p, np, TS, D);
-    HIPTS_LAUNCH_F16(f16, eva_pool_kernel, batch, 1024, 0, s, part_p, h->fcn_g.as<float>(), h->fcn_b.as<float>(), pooled2_p, POOL_SPLITS, POOL_SPLITS, D, c.ln_eps, np);
-    g = GemmArgs{};
-    g.f16 = f16;
-    g.shared_chip = shared_chip;
+    // pooled2 = hi | lo of fc_norm(mean over the patch tokens): the POOL_SPLITS partial rows summed, divided by the np tokens they cover
+    HIPTS_LAUNCH_F16(f16, pool_ln_kernel, batch, 1024, 0, s, part_p, h->fcn_g.as<float>(), h->fcn_b.as<float>(), PooledHiLo{pooled2_p}, POOL_SPLITS, D,
+                     c.ln_eps, 0, np);
+    g = gemm_args(f16, shared_chip);
     g.A = pooled2_p; g.W = h->head_w.as<bf16_t>(); g.M = batch; g.N = c.num_classes; g.K = 2 * D;
     g.sk_ws = h->sk_ws.as<char>() + (size_t)sub * GEMM_SK_WS_BYTES; g.sk_ws_bytes = GEMM_SK_WS_BYTES;      // split-K: 43 tiles on 256 CUs
     g.bias = h->head_b.as<float>(); g.out_f32 = lg; g.out2_f32 = pr;
@@ -491,7 +394,7 @@ int hipts_eva_set_tensor(hipts_eva_t* h, const char* key_c, const float* data, i
     std::string t;
     if (key == "patch_embed.proj.weight") {
         EXPECT_NUMEL((int64_t)D * 3 * P * P);
-        const std::vector<float> w2 = stem_weight_hilo(data, D, P * P, h->PK, true);      // BGR flip; the hi | lo halves of eva_patchify_kernel
+        const std::vector<float> w2 = stem_weight_hilo(data, D, P * P, h->PK, true);      // BGR flip; the hi | lo halves of patch_gather_kernel
         st = put_rows16(h->patch_w, w2.data(), D, 2 * h->PK, 0, 2 * h->PK, f16);
     } else if (key == "patch_embed.proj.bias") { EXPECT_NUMEL(D); st = upload_f32(h->patch_b, data, D); }
     else if (key == "cls_token") { EXPECT_NUMEL(D); st = upload_f32(h->cls, data, D); }

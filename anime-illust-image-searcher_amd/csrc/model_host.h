@@ -94,6 +94,29 @@ inline bool parse_indexed(const std::string& s, const char* prefix, int* index, 
         HIPTS_LAUNCH_CHECK();                                                                  \
     } while (0)
 
+// kernel<F16>(from_u8 or from_f32, ...) on the input type and the operand type, for a kernel whose first argument is the policy that
+// reads the images (patch_rows.h).  Four instantiations in the order the sources always had them: uint8 input with half, then bf16
+// operands, then float32 input with half, then bf16
+#define HIPTS_LAUNCH_U8_F16(is_u8, f16, kernel, grid, block, lds, stream, from_u8, from_f32, ...)    \
+    do {                                                                                       \
+        if (is_u8) {                                                                           \
+            if (f16) kernel<true><<<grid, block, lds, stream>>>(from_u8, __VA_ARGS__);         \
+            else kernel<false><<<grid, block, lds, stream>>>(from_u8, __VA_ARGS__);            \
+        } else {                                                                               \
+            if (f16) kernel<true><<<grid, block, lds, stream>>>(from_f32, __VA_ARGS__);        \
+            else kernel<false><<<grid, block, lds, stream>>>(from_f32, __VA_ARGS__);           \
+        }                                                                                      \
+        HIPTS_LAUNCH_CHECK();                                                                  \
+    } while (0)
+
+// a GEMM launch's arguments with the two fields every launch of a forward sets alike
+inline GemmArgs gemm_args(bool f16, bool shared_chip) {
+    GemmArgs g{};
+    g.f16 = f16;
+    g.shared_chip = shared_chip;
+    return g;
+}
+
 // Internal streams and events of the sub-batch split.  Nothing is created before the first split forward: a handle that only sees
 // small batches opens no stream of its own (a process has few hardware queues).  Destroyed with the handle, whose destroy function
 // has synchronised the device before.

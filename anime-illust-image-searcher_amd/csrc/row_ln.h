@@ -1,6 +1,6 @@
 // row_ln.h -- the "one wave per row" LayerNorm of the five forwards (vit.hip, eva.hip and ccip.hip through launch_layernorm; ccip.hip,
-// convnext.hip, swinv2.hip directly), the wave reduction and row statistics it is built from, and the hi | lo operand split.  Device
-// code only.  Everything lives in an anonymous namespace, so each including object gets its own copy under the same symbol names.
+// convnext.hip, swinv2.hip directly), the wave reduction and row statistics it is built from, the hi | lo operand split, and the pooled
+// LayerNorm head (pool_ln_kernel, at the end).  Device code only.  Everything lives in an anonymous namespace, so each including object gets its own copy under the same symbol names.
 //
 // Batch invariance and the parity bounds of the models rest on every LayerNorm rounding alike: there is ONE body, row_ln_kernel, and
 // what differs between its uses is a compile-time policy -- where the row comes from, which affine is applied, where the result goes.
@@ -250,6 +250,78 @@ __global__ __launch_bounds__(256) void row_ln_kernel(Src src, Affine affine, Sin
             if constexpr (std::is_same<Sink, BackToSource>::value) src.template store<F16>(c, o);
             else sink.template store<F16>(c, o);
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The pooled LayerNorm head of ccip.hip, convnext.hip and eva.hip (one workgroup per image), and where a pooled feature goes (also
+// swinv2.hip's token mean): store<F16>(image b, width C, column c, value).  F16 is the operand type of the 16-bit sink; the float32
+// one ignores it and is launched as <false>.
+// ---------------------------------------------------------------------------------------------
+struct PooledF32 {                      // float32 rows
+    float* out;
+    template <bool F16>
+    __device__ void store(int64_t b, int C, int c, float f) const { out[b * C + c] = f; }
+};
+
+struct PooledHiLo {                     // hi | lo halves, the A operand of a head GEMM with K = 2 C against [W | W]: [b][c] = hi, [b][C + c] = lo
+    bf16_t* out;
+    template <bool F16>
+    __device__ void store(int64_t b, int C, int c, float f) const { split_hilo<F16>(f, out[b * 2 * C + c], out[b * 2 * C + C + c]); }
+};
+
+// Head: sink[b][:] = LN((sum over the T rows of x[b]) / count)  (with bias): count = T for the mean over an image's tokens, or the
+// tokens behind T partial row sums (eva.hip).  One 1024-thread workgroup per image:
+// four row groups x 256 channel threads sum a quarter of the rows each (the loop is load-latency bound,
+// so more rows in flight is what matters), partial sums meet in LDS, the first 256 threads normalise.
+template <bool F16, class Sink>
+__global__ __launch_bounds__(1024) void pool_ln_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ bta,
+                                                       Sink sink, int T, int C, float eps, int blk, int count) {
+    __shared__ float part[4][1024];
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x & 255, rg = threadIdx.x >> 8;
+    const float* xb = x + (int64_t)b * T * C;
+    float m[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int r = rg; r < T; r += 4)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = tid + 256 * u;
+            if (c < C) m[u] += blk ? xb[((((int64_t)(r >> 4) * (C >> 4)) + (c >> 4)) << 8) + (r & 15) * 16 + (c & 15)] : xb[(int64_t)r * C + c];
+        }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) part[rg][tid + 256 * u] = m[u];
+    __syncthreads();
+    // (every thread keeps walking to the barriers; only row group 0 does the arithmetic)
+    float s = 0.f;
+    if (rg == 0) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = tid + 256 * u;
+            m[u] = ((part[0][c] + part[1][c]) + (part[2][c] + part[3][c])) / (float)count;
+            if (c < C) s += m[u];
+        }
+        s = wave_sum(s);
+        if ((tid & 63) == 0) red[tid >> 6] = s;
+    }
+    __syncthreads();
+    const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)C;
+    __syncthreads();
+    if (rg == 0) {
+        float ss = 0.f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (tid + 256 * u < C) ss += (m[u] - mean) * (m[u] - mean);
+        ss = wave_sum(ss);
+        if ((tid & 63) == 0) red[tid >> 6] = ss;
+    }
+    __syncthreads();
+    if (rg != 0) return;
+    const float rstd = 1.0f / sqrtf((red[0] + red[1] + red[2] + red[3]) / (float)C + eps);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int c = tid + 256 * u;
+        if (c < C) sink.template store<F16>(b, C, c, (m[u] - mean) * rstd * g[c] + bta[c]);
     }
 }
 

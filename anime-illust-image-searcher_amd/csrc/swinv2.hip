@@ -10,7 +10,7 @@
 //
 // Data layout as in the ConvNeXt forward: token-major NHWC, the residual stream x float32 [B*H*W][C], its hi | lo 16-bit halves xh2
 // [B*H*W][2 C] the A operand of q | k | v and fc1.  Every Linear is the shared persistent MFMA GEMM (gemm.hip):
-//   stem          convnet.h's cnx_stem_kernel (hi | lo patch gather) -> EPI_BIAS -> row_ln.h's row_ln_kernel (LayerNorm with bias in
+//   stem          patch_rows.h's patch_gather_kernel (hi | lo halves, Window4x4) -> EPI_BIAS -> row_ln.h's row_ln_kernel (LayerNorm with bias in
 //                 place, the ToF32And16 sink the ConvNeXt stem uses; its 16-bit copy xh is not read here) -> sw_split_x_kernel (xh2)
 //   merging       sw_merge_kernel (2 x 2 gather in timm's order as hi | lo halves of the fp32 stream) -> EPI_BIAS (K = 8 C, zero bias)
 //                 -> row_ln_kernel in place, as the stem
@@ -25,7 +25,7 @@
 //   fc1           EPI_GELU from xh2 (K = 2 C against [W | W]; gelu_tanh from the configuration, 0 = the erf form).  The hi | lo operands
 //                 of merging, q | k | v and fc1 are what brings a flat picture's logits within 1e-3 of float64: its tokens share every
 //                 rounding error, which the mean over tokens then cannot average out
-//   head          row_ln_kernel with the ToF32 sink (per-token LayerNorm, float32) -> sw_mean_kernel -> cnx_split_kernel (hi | lo) -> EPI_HEAD
+//   head          row_ln_kernel with the ToF32 sink (per-token LayerNorm, float32) -> sw_mean_kernel (hi | lo, the PooledHiLo sink) -> EPI_HEAD
 // The position-bias tables 16 sigmoid(cpb_mlp(table)) depend on the weights only: computed on the host (double, stored float32) at the
 // first forward after the last cpb_mlp tensor was set, [heads][(2 w - 1)^2] per block.
 #include <algorithm>
@@ -67,7 +67,7 @@ struct hipts_swinv2 {
     TensorLedger ledger;
     bool cpb_ready = false;
     // workspace (sized for cfg.max_batch), carved per image with the stride of the largest stage
-    DevBuf img_in, a0, x, xh, xh2, qkv, ao, br, m1, col, feat, feat2, logits, probs;
+    DevBuf img_in, a0, x, xh, xh2, qkv, ao, br, m1, col, feat2, logits, probs;
     size_t px = 0, p3c = 0, phid = 0, pcol = 0;
     SubStreams<2> streams;
     double flops_per_image = 0.0;
@@ -107,13 +107,14 @@ __global__ __launch_bounds__(256) void sw_split_x_kernel(const float* __restrict
     split_hilo4<F16>(v, *reinterpret_cast<bf16x4*>(xh2 + row * 2 * D + c), *reinterpret_cast<bf16x4*>(xh2 + row * 2 * D + D + c));
 }
 
-// Mean over an image's T tokens, tokens summed in order (one workgroup per image).
-__global__ __launch_bounds__(256) void sw_mean_kernel(const float* __restrict__ y, float* __restrict__ f, int T, int C) {
+// Mean over an image's T tokens, tokens summed in order (one workgroup per image), into a sink of the pooled head (row_ln.h).
+template <bool F16, class Sink>
+__global__ __launch_bounds__(256) void sw_mean_kernel(const float* __restrict__ y, Sink sink, int T, int C) {
     const int64_t b = blockIdx.x;
     for (int c = threadIdx.x; c < C; c += 256) {
         float s = 0.f;
         for (int t = 0; t < T; ++t) s += y[(b * T + t) * C + c];
-        f[b * C + c] = s / (float)T;
+        sink.template store<F16>(b, C, c, s / (float)T);
     }
 }
 
@@ -174,27 +175,16 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
     bf16_t* m1 = h->m1.as<bf16_t>() + (size_t)i0 * h->phid;
     bf16_t* col = h->col.as<bf16_t>() + (size_t)i0 * h->pcol;
     bf16_t* a0 = h->a0.as<bf16_t>() + (size_t)i0 * h->st[0].T * CNX_STEM_K;
-    auto gemm_args = [&]() {
-        GemmArgs g{};
-        g.f16 = f16;
-        g.shared_chip = shared_chip;
-        return g;
-    };
 
     // ---- stem: conv 4x4 s4 (+bias) -> LayerNorm (weight, bias) = the residual stream of stage 0
     {
         const SwStage& S0 = h->st[0];
         const int64_t M = (int64_t)batch * S0.T;
         const int blocks = ceil_div(M * 4, 256);
-        if (is_u8) {
-            if (f16) cnx_stem_kernel<true, true><<<blocks, 256, 0, s>>>(in_dev, h->lut.as<float>(), a0, M * 4, S, S0.H);
-            else cnx_stem_kernel<true, false><<<blocks, 256, 0, s>>>(in_dev, h->lut.as<float>(), a0, M * 4, S, S0.H);
-        } else {
-            if (f16) cnx_stem_kernel<false, true><<<blocks, 256, 0, s>>>(in_dev, nullptr, a0, M * 4, S, S0.H);
-            else cnx_stem_kernel<false, false><<<blocks, 256, 0, s>>>(in_dev, nullptr, a0, M * 4, S, S0.H);
-        }
-        HIPTS_LAUNCH_CHECK();
-        GemmArgs g = gemm_args();
+        const PixelU8Table from_u8{(const uint8_t*)in_dev, h->lut.as<float>()};
+        const PixelF32Planes<true> from_f32{(const float*)in_dev};
+        HIPTS_LAUNCH_U8_F16(is_u8, f16, patch_gather_kernel, blocks, 256, 0, s, from_u8, from_f32, Window4x4{}, a0, M * 4, S, S0.H);
+        GemmArgs g = gemm_args(f16, shared_chip);
         g.A = a0; g.W = h->stem_w.as<bf16_t>(); g.M = (int)M; g.N = S0.C; g.K = CNX_STEM_K;
         g.bias = h->stem_b.as<float>(); g.out_f32 = x;
         HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
@@ -213,7 +203,7 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
             const SwStage& Pv = h->st[si - 1];
             const int64_t total4 = (int64_t)M * Pv.C;          // M rows of 4 Cprev, in float4
             HIPTS_LAUNCH_F16(f16, sw_merge_kernel, ceil_div(total4, 256), 256, 0, s, x, col, total4, Pv.H, Pv.C);
-            GemmArgs g = gemm_args();
+            GemmArgs g = gemm_args(f16, shared_chip);
             g.A = col; g.W = St.ds_w.as<bf16_t>(); g.M = M; g.N = C; g.K = 8 * Pv.C;
             g.bias = St.ds_b.as<float>(); g.out_f32 = x;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
@@ -224,20 +214,20 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
         }
         const AddToStreamHiLo to_stream{x, xh2, xh2 + C};       // x += LN(branch); xh2 = [hi | lo] of the new x
         for (SwBlock& B : St.blocks) {
-            GemmArgs g = gemm_args();
+            GemmArgs g = gemm_args(f16, shared_chip);
             g.A = xh2; g.W = B.qkv2.as<bf16_t>(); g.M = M; g.N = 3 * C; g.K = 2 * C; g.bias = B.qkv_b.as<float>(); g.out_f32 = qkv;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
             HIPTS_TRY(launch_swin_attention(qkv, B.ls.as<float>(), B.cpb.as<float>(), ao, batch, H, St.win, B.shift, St.heads, f16, s));
-            g = gemm_args();
+            g = gemm_args(f16, shared_chip);
             g.A = ao; g.W = B.proj.as<bf16_t>(); g.M = M; g.N = C; g.K = C; g.bias = B.proj_b.as<float>(); g.out_f32 = br;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
             const LnGammaBeta norm1{B.n1_w.as<float>(), B.n1_b.as<float>()};
             HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(M, 4), 256, 0, s, FromF32{br}, norm1, to_stream, (int64_t)M, C, c.ln_eps);
-            g = gemm_args();
+            g = gemm_args(f16, shared_chip);
             g.A = xh2; g.W = B.fc1.as<bf16_t>(); g.M = M; g.N = St.hid; g.K = 2 * C; g.bias = B.fc1_b.as<float>();
             g.out_bf16 = m1; g.gelu_tanh = c.gelu_tanh;
             HIPTS_TRY(launch_gemm(EPI_GELU, g, s));
-            g = gemm_args();
+            g = gemm_args(f16, shared_chip);
             g.A = m1; g.W = B.fc2.as<bf16_t>(); g.M = M; g.N = C; g.K = St.hid; g.bias = B.fc2_b.as<float>(); g.out_f32 = br;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
             const LnGammaBeta norm2{B.n2_w.as<float>(), B.n2_b.as<float>()};
@@ -248,15 +238,12 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
     // ---- head: LayerNorm per token -> mean over tokens -> hi | lo -> fc (+bias) with sigmoid
     const SwStage& L = h->st[3];
     const int64_t ML = (int64_t)batch * L.T;
-    float* feat = h->feat.as<float>() + (size_t)i0 * L.C;
     bf16_t* feat2 = h->feat2.as<bf16_t>() + (size_t)i0 * 2 * L.C;
     const LnGammaBeta head_norm{h->head_nw.as<float>(), h->head_nb.as<float>()};
     row_ln_kernel<false><<<ceil_div(ML, 4), 256, 0, s>>>(FromF32{x}, head_norm, ToF32{br}, ML, L.C, c.ln_eps);
     HIPTS_LAUNCH_CHECK();
-    sw_mean_kernel<<<batch, 256, 0, s>>>(br, feat, L.T, L.C);
-    HIPTS_LAUNCH_CHECK();
-    HIPTS_LAUNCH_F16(f16, cnx_split_kernel, ceil_div((int64_t)batch * L.C, 256), 256, 0, s, feat, feat2, batch, L.C);
-    GemmArgs g = gemm_args();
+    HIPTS_LAUNCH_F16(f16, sw_mean_kernel, batch, 256, 0, s, br, PooledHiLo{feat2}, L.T, L.C);
+    GemmArgs g = gemm_args(f16, shared_chip);
     g.A = feat2; g.W = h->head_w.as<bf16_t>(); g.M = batch; g.N = c.num_classes; g.K = 2 * L.C;
     g.bias = h->head_b.as<float>(); g.out_f32 = lg ? lg + (size_t)i0 * c.num_classes : nullptr;
     g.out2_f32 = pr ? pr + (size_t)i0 * c.num_classes : nullptr;
@@ -358,7 +345,7 @@ int hipts_swinv2_create(const hipts_swinv2_config_t* cfg, int device, hipts_swin
     if ((st = upload_f32(h->lut, lut.data(), lut.size())) || (st = h->a0.alloc((size_t)B * h->st[0].T * CNX_STEM_K * 2)) ||
         (st = h->x.alloc((size_t)B * h->px * 4)) || (st = h->xh.alloc((size_t)B * h->px * 2)) || (st = h->xh2.alloc((size_t)B * h->px * 4)) || (st = h->qkv.alloc((size_t)B * h->p3c * 4)) ||
         (st = h->ao.alloc((size_t)B * h->px * 2)) || (st = h->br.alloc((size_t)B * h->px * 4)) || (st = h->m1.alloc((size_t)B * h->phid * 2)) ||
-        (st = h->col.alloc((size_t)B * h->pcol * 2)) || (st = h->feat.alloc((size_t)B * C3 * 4)) || (st = h->feat2.alloc((size_t)B * 2 * C3 * 2)) ||
+        (st = h->col.alloc((size_t)B * h->pcol * 2)) || (st = h->feat2.alloc((size_t)B * 2 * C3 * 2)) ||
         (st = h->logits.alloc((size_t)B * cfg->num_classes * 4)) || (st = h->probs.alloc((size_t)B * cfg->num_classes * 4))) {
         delete h;
         return st;
@@ -411,7 +398,7 @@ int hipts_swinv2_set_tensor(hipts_swinv2_t* h, const char* key_c, const float* d
     std::string sub, t;
     if (key == "patch_embed.proj.weight") {
         EXPECT_NUMEL((int64_t)C0 * 48);
-        const std::vector<float> w2 = stem_weight_hilo(data, C0, 16, CNX_STEM_KH, true);      // BGR; the hi | lo halves of cnx_stem_kernel
+        const std::vector<float> w2 = stem_weight_hilo(data, C0, 16, CNX_STEM_KH, true);      // BGR; the hi | lo halves of patch_gather_kernel
         st = upload_matrix16(h->stem_w, w2.data(), C0, CNX_STEM_K, round_up(C0, 256), f16);
     } else if (key == "patch_embed.proj.bias") { EXPECT_NUMEL(C0); st = upload_f32(h->stem_b, data, C0); }
     else if (key == "patch_embed.norm.weight") { EXPECT_NUMEL(C0); st = upload_f32(h->stem_nw, data, C0); }

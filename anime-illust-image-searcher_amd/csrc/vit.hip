@@ -20,6 +20,7 @@
 #include "vit_internal.h"
 #include "model_host.h"
 #include "row_ln.h"
+#include "patch_rows.h"
 
 using namespace hipts;
 
@@ -83,48 +84,8 @@ struct hipts_vit {
 
 namespace {
 
-// ---------------------------------------------------------------------------------------------
-// patch matrix: A0[m][(ky*P + kx)*3 + c] = bf16(normalised pixel), c in memory (RGB) order; the
-// BGR flip of tagging.py:243 is folded into the weight permutation at upload time.
-// One thread per (token, ky): reads P*3 contiguous bytes, writes P*3 contiguous bf16.
-// ---------------------------------------------------------------------------------------------
-template <bool F16>
-__global__ __launch_bounds__(256) void patchify_u8_kernel(const uint8_t* __restrict__ img, bf16_t* __restrict__ a0, int batch,
-                                                          int size, int P, int grid) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t total = (int64_t)batch * grid * grid * P;
-    if (idx >= total) return;
-    const int ky = (int)(idx % P);
-    const int64_t tok = idx / P;
-    const int px = (int)(tok % grid), py = (int)((tok / grid) % grid), b = (int)(tok / ((int64_t)grid * grid));
-    const uint8_t* src = img + (((int64_t)b * size + (py * P + ky)) * size + px * P) * 3;
-    bf16_t* dst = a0 + tok * (int64_t)(P * P * 3) + ky * P * 3;
-    // The pixel is stored as the exact integer 0..255 (exact in bf16).  ToTensor + Normalize,
-    // x = (u/255 - .5)/.5 = u*(2/255) - 1, is affine, so it is applied to the fp32 accumulator in the
-    // GEMM epilogue: W.x = (2/255) W.u - rowsum(W).  Rounding x itself to bf16 would put the same
-    // 256 rounding errors on every token -- a systematic error that mean-pooling does not average out.
-    if (P == 16) {          // 48 contiguous bytes in, 96 contiguous bytes out: three 16-B loads, six 16-B stores
-        const uint4* s4 = reinterpret_cast<const uint4*>(src);
-        uint4* d4 = reinterpret_cast<uint4*>(dst);
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-            const uint4 in = s4[v];
-            const uint32_t w[4] = {in.x, in.y, in.z, in.w};
-            bf16x8 lo, hi;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                lo[e] = to_op<F16>((float)((w[e >> 2] >> (8 * (e & 3))) & 0xffu));
-                hi[e] = to_op<F16>((float)((w[2 + (e >> 2)] >> (8 * (e & 3))) & 0xffu));
-            }
-            d4[2 * v] = *reinterpret_cast<const uint4*>(&lo);
-            d4[2 * v + 1] = *reinterpret_cast<const uint4*>(&hi);
-        }
-        return;
-    }
-    for (int i = 0; i < P * 3; ++i) dst[i] = to_op<F16>((float)src[i]);
-}
-
-// The same for 16 x 16 patches with every global access coalesced (round 4): a workgroup takes up to 16 neighbouring tokens of one patch
+// The patch matrix of the uint8 entry, A0[m][(ky*P + kx)*3 + c] = 16bit(raw byte) (patch_rows.h: patchify_u8_kernel, one thread per
+// (token, ky)), for 16 x 16 patches with every global access coalesced (round 4): a workgroup takes up to 16 neighbouring tokens of one patch
 // row -- 16 image rows x (tokens * 48) contiguous bytes -- with linear 16-byte loads, converts, lays the values out token-major in LDS
 // ([token][ky][kx * 3 + c], 1536 B per token) and writes the tokens' rows, which are contiguous in the patch matrix, with linear 16-byte
 // stores.  (patchify_u8_kernel reads 48-byte pieces 1344 B apart per lane: 39 us per 32 images for 58 MB.)
@@ -161,28 +122,6 @@ __global__ __launch_bounds__(256) void patchify_u8_p16_kernel(const uint8_t* __r
     const int out_chunks = ntok * 96;                                   // 1536 B per token
     uint4* dst = reinterpret_cast<uint4*>(a0 + (((int64_t)b * grid + py) * grid + px0) * 768);
     for (int L = tid; L < out_chunks; L += 256) dst[L] = *reinterpret_cast<const uint4*>(image + L * 16);
-}
-
-// x: float32 [B][3][S][S] (BGR, already normalised).  Channel c of the patch matrix (memory/RGB
-// order) is model channel 2 - c.  Each value is split into bf16 hi + bf16 lo (row = [hi(K) | lo(K)],
-// multiplied against [W | W]) so the float32 input keeps ~16 significant bits.
-template <bool F16>
-__global__ __launch_bounds__(256) void patchify_f32_kernel(const float* __restrict__ x, bf16_t* __restrict__ a0, int batch,
-                                                           int size, int P, int grid) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t total = (int64_t)batch * grid * grid * P;
-    if (idx >= total) return;
-    const int ky = (int)(idx % P);
-    const int64_t tok = idx / P;
-    const int px = (int)(tok % grid), py = (int)((tok / grid) % grid), b = (int)(tok / ((int64_t)grid * grid));
-    const int K = P * P * 3;
-    bf16_t* dst = a0 + tok * (int64_t)(2 * K) + ky * P * 3;
-    for (int c = 0; c < 3; ++c) {
-        const float* src = x + (((int64_t)b * 3 + (2 - c)) * size + (py * P + ky)) * size + px * P;
-        for (int kx = 0; kx < P; ++kx) {
-            split_hilo<F16>(src[kx], dst[kx * 3 + c], dst[K + kx * 3 + c]);
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -574,22 +513,17 @@ int vit_run_images(hipts_vit* h, const void* in_dev, bool is_u8, int i0, int nb,
         if (is_u8 && P == 16 && (S * 3) % 16 == 0) {
             const int xgroups = (h->grid + 15) / 16;
             const int pblocks = nb * h->grid * xgroups;
-            if (f16) patchify_u8_p16_kernel<true><<<pblocks, 256, 0, s>>>((const uint8_t*)in_p, a0, S, h->grid, xgroups);
-            else patchify_u8_p16_kernel<false><<<pblocks, 256, 0, s>>>((const uint8_t*)in_p, a0, S, h->grid, xgroups);
+            HIPTS_LAUNCH_F16(f16, patchify_u8_p16_kernel, pblocks, 256, 0, s, (const uint8_t*)in_p, a0, S, h->grid, xgroups);
         } else if (is_u8) {
-            if (f16) patchify_u8_kernel<true><<<blocks, 256, 0, s>>>((const uint8_t*)in_p, a0, nb, S, P, h->grid);
-            else patchify_u8_kernel<false><<<blocks, 256, 0, s>>>((const uint8_t*)in_p, a0, nb, S, P, h->grid);
-        } else {
-            if (f16) patchify_f32_kernel<true><<<blocks, 256, 0, s>>>((const float*)in_p, a0, nb, S, P, h->grid);
-            else patchify_f32_kernel<false><<<blocks, 256, 0, s>>>((const float*)in_p, a0, nb, S, P, h->grid);
+            HIPTS_LAUNCH_F16(f16, patchify_u8_kernel, blocks, 256, 0, s, (const uint8_t*)in_p, a0, nb, S, P, h->grid);
+        } else {      // hi | lo halves of the float32 input (BGR: plane 2 - c), a row [hi(K) | lo(K)] against [W | W]
+            HIPTS_LAUNCH_F16(f16, patch_gather_kernel, blocks, 256, 0, s, PixelF32Planes<true>{(const float*)in_p}, WindowPatch{P, h->patch_k}, a0,
+                             total, S, h->grid);
         }
-        HIPTS_LAUNCH_CHECK();
     }
     GemmArgs g;
     // patch embedding: x = A0 W^T + b + pos
-    g = GemmArgs{};
-    g.f16 = f16;
-    g.shared_chip = shared_chip;
+    g = gemm_args(f16, shared_chip);
     g.A = a0; g.M = M; g.N = D; g.out_f32 = x; g.pos = h->pos.as<float>(); g.tokens = T;
     if (is_u8) {   // exact integer pixels; affine normalisation folded into the epilogue
         g.W = h->patch_w.as<bf16_t>(); g.K = h->patch_k; g.bias = h->patch_b_u8.as<float>(); g.qscale = 2.0f / 255.0f;
@@ -632,9 +566,7 @@ int vit_run_images(hipts_vit* h, const void* in_dev, bool is_u8, int i0, int nb,
     };
     // x += A W^T + b; with next_gamma also xn = 16bit(gamma * x) and the row statistics of x for the consumer of that norm
     auto residual = [&](const bf16_t* A, const bf16_t* W, const float* bias, int K, const float* next_gamma, double flops, double bytes) -> int {
-        GemmArgs r{};
-        r.f16 = f16;
-        r.shared_chip = shared_chip;
+        GemmArgs r = gemm_args(f16, shared_chip);
         r.A = A; r.W = W; r.M = M; r.N = D; r.K = K; r.bias = bias; r.out_f32 = x;
         r.sk_ws = h->sk_ws.as<char>() + (size_t)sub * GEMM_SK_WS_BYTES; r.sk_ws_bytes = GEMM_SK_WS_BYTES;      // this stream's split-K workspace
         r.x_blocked = xb ? 1 : 0;
@@ -656,9 +588,7 @@ int vit_run_images(hipts_vit* h, const void* in_dev, bool is_u8, int i0, int nb,
         // q, k, v in ONE launch over the fused qkv weight (N = 3 D; round 3): all three leave in the [image][head][token][64] layout, V in
         // its natural orientation -- the attention kernel reads it transposed out of LDS (attn2.hip), so no transposing epilogue, one
         // launch and one pass over the activations less per layer.  q pre-scaled for the base-2 softmax.
-        g = GemmArgs{};
-        g.f16 = f16;
-        g.shared_chip = shared_chip;
+        g = gemm_args(f16, shared_chip);
         g.A = xn; g.W = L.qkv_w.as<bf16_t>(); g.M = M; g.N = 3 * D; g.K = D;
         g.bias = L.qkv_b.as<float>(); g.out_bf16 = q; g.out2_bf16 = k; g.out3_bf16 = v;
         if (ln1_folded) folded(g, L.qkv_u.as<float>(), L.qkv_c.as<float>());
@@ -684,9 +614,7 @@ int vit_run_images(hipts_vit* h, const void* in_dev, bool is_u8, int i0, int nb,
                            dM * att_k * 2 + dM * dD * 8));
         stagger(3);
         if (!fold) HIPTS_TRY(layernorm(L.ln2_g.as<float>(), L.ln2_b.as<float>()));
-        g = GemmArgs{};
-        g.f16 = f16;
-        g.shared_chip = shared_chip;
+        g = gemm_args(f16, shared_chip);
         g.A = xn; g.W = L.fc1_w.as<bf16_t>(); g.M = M; g.N = c.mlp_dim; g.K = D;
         g.bias = L.fc1_b.as<float>(); g.out_bf16 = hmid; g.gelu_tanh = c.gelu_tanh;
         if (fold) folded(g, L.fc1_u.as<float>(), L.fc1_c.as<float>());
@@ -706,18 +634,11 @@ int vit_run_images(hipts_vit* h, const void* in_dev, bool is_u8, int i0, int nb,
         ProfScope ps(h, s, PC_POOL, 0.0, dM * dD * 4);
         pool_partial_kernel<<<dim3(h->pool_splits, nb), 256, 0, s>>>(xb ? x_rm : x, pool_part, T, D, c.ln_eps, c.pool_then_norm ? 0 : 1, h->pool_splits);
         HIPTS_LAUNCH_CHECK();
-        if (f16)
-            pool_finalize_kernel<true><<<nb, 256, 0, s>>>(pool_part, h->norm_g.as<float>(), h->norm_b.as<float>(), pooled2, T, D, c.ln_eps,
-                                                          c.pool_then_norm ? 1 : 0, h->pool_splits);
-        else
-            pool_finalize_kernel<false><<<nb, 256, 0, s>>>(pool_part, h->norm_g.as<float>(), h->norm_b.as<float>(), pooled2, T, D, c.ln_eps,
-                                                           c.pool_then_norm ? 1 : 0, h->pool_splits);
-        HIPTS_LAUNCH_CHECK();
+        HIPTS_LAUNCH_F16(f16, pool_finalize_kernel, nb, 256, 0, s, pool_part, h->norm_g.as<float>(), h->norm_b.as<float>(), pooled2, T, D, c.ln_eps,
+                         c.pool_then_norm ? 1 : 0, h->pool_splits);
     }
     // head (+ sigmoid, tagging.py:176)
-    g = GemmArgs{};
-    g.f16 = f16;
-    g.shared_chip = shared_chip;
+    g = gemm_args(f16, shared_chip);
     g.A = pooled2; g.W = h->head_w.as<bf16_t>(); g.M = nb; g.N = c.num_classes; g.K = 2 * D;
     g.sk_ws = h->sk_ws.as<char>() + (size_t)sub * GEMM_SK_WS_BYTES; g.sk_ws_bytes = GEMM_SK_WS_BYTES;      // split-K: 43 tiles on 256 CUs
     g.bias = h->head_b.as<float>(); g.out_f32 = lg ? lg + (size_t)i0 * c.num_classes : nullptr;

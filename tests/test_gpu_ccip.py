@@ -59,6 +59,26 @@ def test_ccip_tiny_matches_oracle(f16):
     np.testing.assert_array_equal(enc.forward_u8(imgs12)[:8], enc.forward_u8(imgs12[:8]))
 
 
+@pytest.mark.parametrize("f16", [0, 1])
+def test_ccip_tiny_float32_entry(f16):
+    """The float32 NCHW entry (hipts_ccip_forward_f32: the one-thread-per-kernel-row gather with the 7 x 7 stride 4 pad 2 window and the
+    unflipped float32 planes) on its own: a 64-pixel image gives a 16 x 16 stem grid, and the window crosses all four borders.  The
+    normalised pixels the oracle's preprocess produces are the values the uint8 entry reads from its table, so the two entries build the
+    same patch matrix and their features are equal bit for bit (measured: max difference exactly 0 in both operand modes)."""
+    from hiptagsearch import synth
+    from hiptagsearch.cfeatures import CCIPEncoder
+    cfg = dict(synth.CCIP_TINY, operand_f16=f16)
+    w = synth.ccip_weights(cfg, seed=3)
+    imgs = synth.images_u8(3, cfg["image_size"], seed=51)
+    want, x = _oracle(cfg, w, imgs)
+    enc = CCIPEncoder(cfg, w, max_batch=4)
+    got = enc(x)
+    _check(got, want, f16)
+    got_u8 = enc.forward_u8(imgs)
+    print("CCIP (operand_f16=%d) float32 entry against forward_u8: max |df| = %.3e" % (f16, np.abs(got - got_u8).max()))
+    np.testing.assert_array_equal(got, got_u8)
+
+
 def test_ccip_without_res_scale_and_missing_tensor():
     from hiptagsearch import synth, _lib
     from hiptagsearch.cfeatures import CCIPEncoder

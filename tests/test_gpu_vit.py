@@ -50,6 +50,23 @@ def test_vit_tiny_matches_oracle(variant):
 
 
 @pytest.mark.parametrize("operands", ["half", "bf16"])
+def test_vit_tiny_patch8_both_entries(operands):
+    """Patch 8 (64 tokens, K = 192): the uint8 entry takes the generic byte gather (every other test has patch 16 and its LDS-tiled
+    kernel), the float32 entry the hi | lo gather with a run-time patch size."""
+    from hiptagsearch import synth
+    from hiptagsearch.tagger import ViTTagger
+    cfg = dict(synth.VIT_TINY, patch=8, operand_f16=1 if operands == "half" else 0)
+    w = synth.vit_weights(cfg, seed=11)
+    imgs = synth.images_u8(3, cfg["image_size"], seed=12)
+    want, x = _oracle_logits(cfg, w, imgs)
+    model = ViTTagger(cfg, w, max_batch=4)
+    for name, (logits, _) in (("forward_u8", model.forward_u8(imgs)), ("forward", model.forward(x))):
+        err = np.abs(logits - want).max()
+        print("ViT tiny patch 8, %s operands, %s: max |logit error| = %.3e" % (operands, name, err))
+        assert err <= LOGIT_TOL, (name, err)
+
+
+@pytest.mark.parametrize("operands", ["half", "bf16"])
 def test_vit_b16_448_matches_oracle(operands):
     """config[1] geometry (ViT-B/16 @448, 784 tokens, 10861 classes), 3 noise images (oracle is CPU); both operand types."""
     from hiptagsearch import synth
