@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.h"
+#include "rank_util.h"
 
 using namespace hipts;
 
@@ -41,15 +42,6 @@ namespace {
 constexpr int CR_FILTER_THREADS = 256;
 constexpr int CR_SMALL = 2048;           // up to this many survivors: one workgroup, bitonic sort in LDS
 constexpr int CR_TILE = 1024;            // survivors per workgroup of a radix pass (one per thread)
-
-// order-preserving u32 image of a float and back (as in query.hip)
-__device__ __forceinline__ uint32_t f32_order_key(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float f32_from_key(uint32_t k) {
-    return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k);
-}
 
 // ---------------------------------------------------------------------------------------------
 // 1. filter
@@ -105,33 +97,6 @@ __global__ __launch_bounds__(CR_FILTER_THREADS) void crerank_filter_kernel(const
     }
 }
 
-// block-wide exclusive scan of one value per thread (1024 threads); the total in *total
-__device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t x, uint32_t* scratch /*[17]*/, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(incl, o);
-        if (lane >= o) incl += y;
-    }
-    if (lane == 63) scratch[wave] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (int w = 0; w < 16; ++w) {
-            const uint32_t t = scratch[w];
-            scratch[w] = run;
-            run += t;
-        }
-        scratch[16] = run;
-    }
-    __syncthreads();
-    const uint32_t res = scratch[wave] + incl - x;
-    *total = scratch[16];
-    __syncthreads();
-    return res;
-}
-
 // ---------------------------------------------------------------------------------------------
 // 2. compaction: counts -> offsets (one workgroup), then the ordered scatter
 // ---------------------------------------------------------------------------------------------
@@ -142,7 +107,7 @@ __global__ __launch_bounds__(1024) void crerank_offsets_kernel(uint32_t* __restr
         const int b = b0 + threadIdx.x;
         const uint32_t c = b < nblocks ? bcount[b] : 0u;
         uint32_t total;
-        const uint32_t ex = block_excl_scan_u32(c, scratch, &total);
+        const uint32_t ex = block_excl_scan(c, scratch, &total);
         if (b < nblocks) bcount[b] = carry + ex;
         carry += total;
     }
@@ -164,7 +129,7 @@ __global__ __launch_bounds__(CR_FILTER_THREADS) void crerank_compact_kernel(cons
     const float diff = 1.0f - sim[r];
     const float score = 1.0f - diff;
     rows_out[pos] = (uint32_t)r;
-    keys_out[pos] = ~f32_order_key(score);                                        // ascending key = descending score
+    keys_out[pos] = ~float_order_key(score);                                        // ascending key = descending score
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -200,7 +165,7 @@ __global__ __launch_bounds__(1024) void crerank_sort_small_kernel(const uint32_t
     for (uint32_t i = tid; i < n; i += 1024) {
         const uint64_t c = ck[i];
         docs_out[i] = row_doc[(uint32_t)c];
-        scores_out[i] = (double)f32_from_key(~(uint32_t)(c >> 32));
+        scores_out[i] = (double)float_from_key(~(uint32_t)(c >> 32));
     }
 }
 
@@ -247,7 +212,7 @@ __global__ __launch_bounds__(1024) void crerank_radix_scan_kernel(const uint32_t
     uint32_t sum = 0;
     for (uint32_t i = i0; i < i1; ++i) sum += hist[(int64_t)(i / nb) * hist_ld + (i % nb)];
     uint32_t all;
-    uint32_t run = block_excl_scan_u32(sum, scratch, &all);
+    uint32_t run = block_excl_scan(sum, scratch, &all);
     for (uint32_t i = i0; i < i1; ++i) {
         uint32_t* p = &hist[(int64_t)(i / nb) * hist_ld + (i % nb)];
         const uint32_t c = *p;
@@ -293,7 +258,7 @@ __global__ __launch_bounds__(CR_TILE) void crerank_radix_scatter_kernel(const ui
     const uint32_t pos = base[d] + wc[wave][d] + rank;     // < n: the scanned histograms sum to n
     if (FINAL) {
         docs_out[pos] = row_doc[row];
-        scores_out[pos] = (double)f32_from_key(~key);
+        scores_out[pos] = (double)float_from_key(~key);
     } else {
         keys_out[pos] = key;
         rows_out[pos] = row;

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "common.h"
+#include "rank_util.h"
 #include "../../include/hip_tagsearch_debug.h"
 
 using namespace hipts;
@@ -75,6 +76,29 @@ constexpr double BM25_K1 = 1.5;    // webui.py:126
 constexpr double BM25_B = 0.75;    // webui.py:127
 constexpr double REQUIRE_MAGIC = 1000.0;   // webui.py:60
 
+// The BM25 arithmetic of webui.py:139-170, stated once (float64, one rounding per operation, the reference's operation order).
+// webui.py:144  k1 * (1 - b + b * (dl / avgdl))   [(1-b) folds to 0.25 exactly]
+__device__ __forceinline__ double bm25_length_norm(double dl, double avgdl) {
+    return BM25_K1 * ((1.0 - BM25_B) + BM25_B * (dl / avgdl));
+}
+// webui.py:144-146  idf * (tf * (k1 + 1) / (tf + norm))
+__device__ __forceinline__ double bm25_term_score(double idf, double tfd, double nrm) {
+    const double denom = tfd + nrm;                          // :144
+    const double numer = tfd * (BM25_K1 + 1.0);              // :145
+    return idf * (numer / denom);                            // :146
+}
+// webui.py:154-170, one (document, query term) step of the document-major form: weight w, the term's tf in the document (0 = absent), its score sc
+__device__ __forceinline__ void bm25_accumulate(double w, int32_t tfv, double sc, double& s, bool& masked) {
+    if (w < 0.0) {                                           // :154-160 exclude
+        if (tfv > 0) masked = true;
+    } else if (w > REQUIRE_MAGIC) {                          // :161-168 required
+        s += (w - REQUIRE_MAGIC) * sc;
+        if (tfv == 0) masked = true;
+    } else {                                                 // :169-170
+        s += w * sc;
+    }
+}
+
 // One thread per (document, query).  Document-major CSR: the ~20 (term, tf) pairs of a document
 // are contiguous, consecutive threads own consecutive documents, so a wave sweeps one contiguous
 // span of the postings arrays.
@@ -88,9 +112,8 @@ __global__ __launch_bounds__(256) void bm25_score_kernel(const int64_t* __restri
     if (d >= D) return;
     const int qb = q_ptr[q], qe = q_ptr[q + 1];
     const int64_t b = ptr[d], e = ptr[d + 1];
-    // webui.py:144  k1 * (1 - b + b * (dl / avgdl))   [(1-b) folds to 0.25 exactly]
     const double dlv = (double)dl[d];
-    const double nrm = BM25_K1 * ((1.0 - BM25_B) + BM25_B * (dlv / avgdl));
+    const double nrm = bm25_length_norm(dlv, avgdl);
     double s = 0.0;
     bool masked = false;
     for (int j = qb; j < qe; ++j) {
@@ -100,18 +123,7 @@ __global__ __launch_bounds__(256) void bm25_score_kernel(const int64_t* __restri
         for (int64_t i = b; i < e; ++i)
             if (term[i] == t) tfv = tf[i];
         const double idf_t = (t >= 0 && t < V) ? idf[t] : 0.0;   // bm25_idf.get(term_id, 0)   :140
-        const double tfd = (double)tfv;
-        const double denom = tfd + nrm;                          // :144
-        const double numer = tfd * (BM25_K1 + 1.0);              // :145
-        const double sc = idf_t * (numer / denom);               // :146
-        if (w < 0.0) {                                           // :154-160 exclude
-            if (tfv > 0) masked = true;
-        } else if (w > REQUIRE_MAGIC) {                          // :161-168 required
-            s += (w - REQUIRE_MAGIC) * sc;
-            if (tfv == 0) masked = true;
-        } else {                                                 // :169-170
-            s += w * sc;
-        }
+        bm25_accumulate(w, tfv, bm25_term_score(idf_t, (double)tfv, nrm), s, masked);
     }
     out[(int64_t)q * D + d] = masked ? -INFINITY : s;
 }
@@ -128,13 +140,18 @@ __device__ unsigned long long g_bm25_stamps[8];
 #else
 #define BM25_STAMP(i) do { } while (0)
 #endif
-__global__ __launch_bounds__(1024) void bm25_postings_kernel(const int64_t* __restrict__ tptr, const int32_t* __restrict__ tdoc,
-                                                             const int32_t* __restrict__ ttf, const int32_t* __restrict__ dl,
-                                                             const double* __restrict__ idf, int32_t V, double avgdl, int64_t D,
-                                                             const int32_t* __restrict__ q_terms, const double* __restrict__ q_weights,
-                                                             const int32_t* __restrict__ q_ptr, double* __restrict__ out,
-                                                             uint8_t* __restrict__ mark_all, double* __restrict__ max_out) {
-    const int q = blockIdx.x, tid = threadIdx.x;
+// The walk itself, for the documents [lo, hi) of query q's row, by a workgroup of NT threads; term_range(t, b, e) gives the part of term
+// t's posting list that lies in that range.  Returns this thread's maximum of the finished scores it read back (-inf when nothing
+// asks for it: want_max false and no masking).  ROWS8: lo and hi are known to be multiples of 8 -- the 8-documents-per-step arms only;
+// otherwise the row decides, and the scalar arms exist too.  STAMPS: the BM25_STAMP points of the measurement-only build.
+template <int NT, bool ROWS8, bool STAMPS, typename TermRange>
+__device__ __forceinline__ double bm25_postings_walk(int q, int64_t lo, int64_t hi, TermRange term_range, const int32_t* __restrict__ tdoc,
+                                                     const int32_t* __restrict__ ttf, const int32_t* __restrict__ dl,
+                                                     const double* __restrict__ idf, int32_t V, double avgdl, int64_t D,
+                                                     const int32_t* __restrict__ q_terms, const double* __restrict__ q_weights,
+                                                     const int32_t* __restrict__ q_ptr, double* __restrict__ out,
+                                                     uint8_t* __restrict__ mark_all, bool want_max) {
+    const int tid = threadIdx.x;
     const int qb = q_ptr[q], qe = q_ptr[q + 1];
     double* __restrict__ scores = out + (int64_t)q * D;
     uint8_t* __restrict__ mark = mark_all + (int64_t)q * D;
@@ -145,7 +162,7 @@ __global__ __launch_bounds__(1024) void bm25_postings_kernel(const int64_t* __re
         if (w > REQUIRE_MAGIC) ++n_required;
         if (w > REQUIRE_MAGIC || w < 0.0) masking = true;
     }
-    BM25_STAMP(0);
+    if constexpr (STAMPS) BM25_STAMP(0);
     // the query's term metadata (posting range, idf) is requested before the row is cleared: per term the dependent chain is then
     // posting -> {document length, score} instead of term -> range -> posting -> ... (~2 us per term of a workgroup's 60-135 us)
     constexpr int TPRE = 8;
@@ -156,28 +173,30 @@ __global__ __launch_bounds__(1024) void bm25_postings_kernel(const int64_t* __re
         const int j = qb + u;
         const int32_t t = j < qe ? q_terms[j] : -1;
         const bool ok = t >= 0 && t < V;
-        t_b[u] = ok ? tptr[t] : 0;
-        t_e[u] = ok ? tptr[t + 1] : 0;
+        t_b[u] = 0;
+        t_e[u] = 0;
+        if (ok) term_range(t, t_b[u], t_e[u]);
         t_idf[u] = ok ? idf[t] : 0.0;
     }
     // 8 documents per thread and step where the row allows it (64 B of scores, 8 B of marks per thread: the byte-wide mark accesses
     // made the masked rows' last pass 65-72 us against 15-29 us for unmasked ones -- tools/bm25_stamps.py)
-    const bool vec8 = (D & 7) == 0;
+    const bool vec8 = ROWS8 || ((lo | hi) & 7) == 0;
+    const int64_t p0 = lo >> 1, p1 = hi >> 1;     // the range in pairs of documents (vec8)
     if (vec8) {
         // lane-contiguous 16-byte stores (1 KB per wave instruction; 64 B per lane at a 64 B stride wrote every line in four pieces: 59 us)
         const double2 z2 = make_double2(0.0, 0.0);
-        for (int64_t g = tid; g < (D >> 1); g += 1024) reinterpret_cast<double2*>(scores)[g] = z2;
+        for (int64_t g = p0 + tid; g < p1; g += NT) reinterpret_cast<double2*>(scores)[g] = z2;
         if (masking)
-            for (int64_t g = tid; g < (D >> 3); g += 1024) reinterpret_cast<uint64_t*>(mark)[g] = 0ull;
+            for (int64_t g = (lo >> 3) + tid; g < (hi >> 3); g += NT) reinterpret_cast<uint64_t*>(mark)[g] = 0ull;
     } else {
 #pragma unroll 8
-        for (int64_t d = tid; d < D; d += 1024) {
+        for (int64_t d = lo + tid; d < hi; d += NT) {
             scores[d] = 0.0;
             if (masking) mark[d] = 0;
         }
     }
     __syncthreads();
-    BM25_STAMP(1);
+    if constexpr (STAMPS) BM25_STAMP(1);
     for (int j = qb; j < qe; ++j) {
         const int32_t t = q_terms[j];
         const double w = q_weights[j];
@@ -191,169 +210,12 @@ __global__ __launch_bounds__(1024) void bm25_postings_kernel(const int64_t* __re
                 for (int x = 1; x < TPRE; ++x)
                     if (u == x) { idf_t = t_idf[x]; b = t_b[x]; e = t_e[x]; }
             } else {
-                idf_t = idf[t]; b = tptr[t]; e = tptr[t + 1];
+                idf_t = idf[t];
+                term_range(t, b, e);
             }
             // Eight postings per thread in flight: the documents of one term are distinct, but the compiler cannot know that a
             // load of scores[d'] may pass the store to scores[d], so an unrolled loop still ran its read-modify-writes one after
             // the other (~6 us per 1024 x 4 postings); here the gathers of a batch are all issued before the first store.
-            constexpr int PU = 8;
-            const bool req = w > REQUIRE_MAGIC;
-            const double ww = req ? (w - REQUIRE_MAGIC) : w;
-            for (int64_t i0 = b + tid; i0 < e; i0 += (int64_t)PU * 1024) {
-                int32_t dd[PU];
-                double tfd[PU];
-#pragma unroll
-                for (int u = 0; u < PU; ++u) {
-                    const int64_t i = i0 + (int64_t)u * 1024;
-                    dd[u] = i < e ? tdoc[i] : -1;
-                    tfd[u] = i < e ? (double)ttf[i] : 0.0;
-                }
-                if (w < 0.0) {
-#pragma unroll
-                    for (int u = 0; u < PU; ++u)
-                        if (dd[u] >= 0) mark[dd[u]] |= 0x80;
-                } else {
-                    double dlv[PU], sv[PU];
-                    uint8_t mk[PU];
-#pragma unroll
-                    for (int u = 0; u < PU; ++u) {
-                        dlv[u] = dd[u] >= 0 ? (double)dl[dd[u]] : 0.0;
-                        sv[u] = dd[u] >= 0 ? scores[dd[u]] : 0.0;
-                        mk[u] = (req && dd[u] >= 0) ? mark[dd[u]] : (uint8_t)0;
-                    }
-#pragma unroll
-                    for (int u = 0; u < PU; ++u) {
-                        if (dd[u] < 0) continue;
-                        const double nrm = BM25_K1 * ((1.0 - BM25_B) + BM25_B * (dlv[u] / avgdl));
-                        const double sc = idf_t * ((tfd[u] * (BM25_K1 + 1.0)) / (tfd[u] + nrm));
-                        scores[dd[u]] = sv[u] + ww * sc;
-                        if (req) mark[dd[u]] = (uint8_t)(mk[u] + 1);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    BM25_STAMP(2);
-    double mx = -INFINITY;
-    if (masking && vec8) {
-        // two documents per lane and access (16 B of scores, 2 B of marks), four accesses in flight; every wave instruction covers a contiguous KB
-        const int64_t pairs = D >> 1;
-        for (int64_t g0 = tid; g0 < pairs; g0 += 4 * 1024) {
-            double2 v[4];
-            uint32_t m2[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t g = g0 + u * 1024;
-                v[u] = g < pairs ? reinterpret_cast<const double2*>(scores)[g] : make_double2(-INFINITY, -INFINITY);
-                m2[u] = g < pairs ? reinterpret_cast<const uint16_t*>(mark)[g] : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t g = g0 + u * 1024;
-                if (g >= pairs) continue;
-                const uint32_t ma = m2[u] & 0xffu, mb_ = m2[u] >> 8;
-                const bool ka = (ma & 0x80u) || (int)(ma & 0x7fu) != n_required, kb = (mb_ & 0x80u) || (int)(mb_ & 0x7fu) != n_required;
-                if (ka) v[u].x = -INFINITY;
-                if (kb) v[u].y = -INFINITY;
-                if (ka || kb) reinterpret_cast<double2*>(scores)[g] = v[u];
-                mx = fmax(mx, fmax(v[u].x, v[u].y));
-            }
-        }
-    } else if (masking) {
-#pragma unroll 8
-        for (int64_t d = tid; d < D; d += 1024) {
-            const uint8_t m = mark[d];
-            double v = scores[d];
-            if ((m & 0x80) || (m & 0x7f) != n_required) scores[d] = v = -INFINITY;
-            mx = fmax(mx, v);
-        }
-    } else if (max_out && vec8) {
-        const int64_t pairs = D >> 1;
-#pragma unroll 4
-        for (int64_t g = tid; g < pairs; g += 1024) {
-            const double2 a0 = reinterpret_cast<const double2*>(scores)[g];
-            mx = fmax(mx, fmax(a0.x, a0.y));
-        }
-    } else if (max_out) {
-#pragma unroll 8
-        for (int64_t d = tid; d < D; d += 1024) mx = fmax(mx, scores[d]);
-    }
-    BM25_STAMP(3);
-    if (max_out) {      // row maximum for the normalisation of webui.py:379-380, fused here
-        __shared__ double part[16];
-        for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-        if ((tid & 63) == 0) part[tid >> 6] = mx;
-        __syncthreads();
-        if (tid == 0) {
-            double m = part[0];
-            for (int w = 1; w < 16; ++w) m = fmax(m, part[w]);
-            max_out[q] = m;
-        }
-    }
-}
-
-// The same walk with the document range cut into slices (round 4).  One workgroup per query is one workgroup per CU for a batch of 256:
-// 16 waves that clear, scatter into and re-read an 800 KB row at ~15 GB/s -- the kernel took 166 us for 620 MB, most of it latency.  A
-// document's float64 additions only have to keep the QUERY'S TERM ORDER, and documents are independent, so a workgroup may take any
-// document range: grid (query, part), each workgroup the postings of its range -- found through a table of every term's posting offsets
-// at BM25_SLICES fixed document boundaries, built with the index -- and a partial row maximum; four 512-thread workgroups share a CU.
-// Same instructions per document as bm25_postings_kernel: the same bits.
-constexpr int BM25_SLICES = 8;
-__global__ __launch_bounds__(512) void bm25_postings_sliced_kernel(const int64_t* __restrict__ tslice, const int32_t* __restrict__ tdoc,
-                                                                   const int32_t* __restrict__ ttf, const int32_t* __restrict__ dl,
-                                                                   const double* __restrict__ idf, int32_t V, double avgdl, int64_t D, int64_t slice_docs,
-                                                                   int per_part, const int32_t* __restrict__ q_terms,
-                                                                   const double* __restrict__ q_weights, const int32_t* __restrict__ q_ptr,
-                                                                   double* __restrict__ out, uint8_t* __restrict__ mark_all, double* __restrict__ max_part) {
-    constexpr int NT = 512;
-    const int q = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
-    const int s0 = part * per_part, s1 = s0 + per_part;                       // fixed slices [s0, s1)
-    const int64_t lo = (int64_t)s0 * slice_docs, hi = s1 == BM25_SLICES ? D : (int64_t)s1 * slice_docs;      // lo, hi multiples of 8 (D % 8 == 0)
-    const int qb = q_ptr[q], qe = q_ptr[q + 1];
-    double* __restrict__ scores = out + (int64_t)q * D;
-    uint8_t* __restrict__ mark = mark_all + (int64_t)q * D;
-    int n_required = 0;
-    bool masking = false;
-    for (int j = qb; j < qe; ++j) {
-        const double w = q_weights[j];
-        if (w > REQUIRE_MAGIC) ++n_required;
-        if (w > REQUIRE_MAGIC || w < 0.0) masking = true;
-    }
-    constexpr int TPRE = 8;
-    int64_t t_b[TPRE], t_e[TPRE];
-    double t_idf[TPRE];
-#pragma unroll
-    for (int u = 0; u < TPRE; ++u) {
-        const int j = qb + u;
-        const int32_t t = j < qe ? q_terms[j] : -1;
-        const bool ok = t >= 0 && t < V;
-        t_b[u] = ok ? tslice[(int64_t)t * (BM25_SLICES + 1) + s0] : 0;
-        t_e[u] = ok ? tslice[(int64_t)t * (BM25_SLICES + 1) + s1] : 0;
-        t_idf[u] = ok ? idf[t] : 0.0;
-    }
-    {
-        const double2 z2 = make_double2(0.0, 0.0);
-        for (int64_t g = (lo >> 1) + tid; g < (hi >> 1); g += NT) reinterpret_cast<double2*>(scores)[g] = z2;
-        if (masking)
-            for (int64_t g = (lo >> 3) + tid; g < (hi >> 3); g += NT) reinterpret_cast<uint64_t*>(mark)[g] = 0ull;
-    }
-    __syncthreads();
-    for (int j = qb; j < qe; ++j) {
-        const int32_t t = q_terms[j];
-        const double w = q_weights[j];
-        if (t >= 0 && t < V) {
-            double idf_t;
-            int64_t b, e;
-            const int u = j - qb;
-            if (u < TPRE) {                       // uniform
-                idf_t = t_idf[0]; b = t_b[0]; e = t_e[0];
-#pragma unroll
-                for (int x = 1; x < TPRE; ++x)
-                    if (u == x) { idf_t = t_idf[x]; b = t_b[x]; e = t_e[x]; }
-            } else {
-                idf_t = idf[t]; b = tslice[(int64_t)t * (BM25_SLICES + 1) + s0]; e = tslice[(int64_t)t * (BM25_SLICES + 1) + s1];
-            }
             constexpr int PU = 8;
             const bool req = w > REQUIRE_MAGIC;
             const double ww = req ? (w - REQUIRE_MAGIC) : w;
@@ -366,11 +228,11 @@ __global__ __launch_bounds__(512) void bm25_postings_sliced_kernel(const int64_t
                     dd[u2] = i < e ? tdoc[i] : -1;
                     tfd[u2] = i < e ? (double)ttf[i] : 0.0;
                 }
-                if (w < 0.0) {
+                if (w < 0.0) {                    // webui.py:154-160 exclude
 #pragma unroll
                     for (int u2 = 0; u2 < PU; ++u2)
                         if (dd[u2] >= 0) mark[dd[u2]] |= 0x80;
-                } else {
+                } else {                          // :161-170: a required term adds (w - REQUIRE_MAGIC) * score and counts its presence
                     double dlv[PU], sv[PU];
                     uint8_t mk[PU];
 #pragma unroll
@@ -382,8 +244,7 @@ __global__ __launch_bounds__(512) void bm25_postings_sliced_kernel(const int64_t
 #pragma unroll
                     for (int u2 = 0; u2 < PU; ++u2) {
                         if (dd[u2] < 0) continue;
-                        const double nrm = BM25_K1 * ((1.0 - BM25_B) + BM25_B * (dlv[u2] / avgdl));
-                        const double sc = idf_t * ((tfd[u2] * (BM25_K1 + 1.0)) / (tfd[u2] + nrm));
+                        const double sc = bm25_term_score(idf_t, tfd[u2], bm25_length_norm(dlv[u2], avgdl));
                         scores[dd[u2]] = sv[u2] + ww * sc;
                         if (req) mark[dd[u2]] = (uint8_t)(mk[u2] + 1);
                     }
@@ -392,9 +253,10 @@ __global__ __launch_bounds__(512) void bm25_postings_sliced_kernel(const int64_t
         }
         __syncthreads();
     }
+    if constexpr (STAMPS) BM25_STAMP(2);
     double mx = -INFINITY;
-    const int64_t p0 = lo >> 1, p1 = hi >> 1;
-    if (masking) {
+    if (masking && vec8) {
+        // two documents per lane and access (16 B of scores, 2 B of marks), four accesses in flight; every wave instruction covers a contiguous KB
         for (int64_t g0 = p0 + tid; g0 < p1; g0 += 4 * NT) {
             double2 v[4];
             uint32_t m2[4];
@@ -416,23 +278,72 @@ __global__ __launch_bounds__(512) void bm25_postings_sliced_kernel(const int64_t
                 mx = fmax(mx, fmax(v[u].x, v[u].y));
             }
         }
-    } else if (max_part) {
+    } else if (masking) {
+#pragma unroll 8
+        for (int64_t d = lo + tid; d < hi; d += NT) {
+            const uint8_t m = mark[d];
+            double v = scores[d];
+            if ((m & 0x80) || (m & 0x7f) != n_required) scores[d] = v = -INFINITY;
+            mx = fmax(mx, v);
+        }
+    } else if (want_max && vec8) {
 #pragma unroll 4
         for (int64_t g = p0 + tid; g < p1; g += NT) {
             const double2 a0 = reinterpret_cast<const double2*>(scores)[g];
             mx = fmax(mx, fmax(a0.x, a0.y));
         }
+    } else if (want_max) {
+#pragma unroll 8
+        for (int64_t d = lo + tid; d < hi; d += NT) mx = fmax(mx, scores[d]);
     }
+    if constexpr (STAMPS) BM25_STAMP(3);
+    return mx;
+}
+
+// One workgroup per query, the whole row; max_out (optional): the row maximum for the normalisation of webui.py:379-380, fused here.
+__global__ __launch_bounds__(1024) void bm25_postings_kernel(const int64_t* __restrict__ tptr, const int32_t* __restrict__ tdoc,
+                                                             const int32_t* __restrict__ ttf, const int32_t* __restrict__ dl,
+                                                             const double* __restrict__ idf, int32_t V, double avgdl, int64_t D,
+                                                             const int32_t* __restrict__ q_terms, const double* __restrict__ q_weights,
+                                                             const int32_t* __restrict__ q_ptr, double* __restrict__ out,
+                                                             uint8_t* __restrict__ mark_all, double* __restrict__ max_out) {
+    const int q = blockIdx.x;
+    auto term_range = [=](int32_t t, int64_t& b, int64_t& e) {
+        b = tptr[t];
+        e = tptr[t + 1];
+    };
+    const double mx = bm25_postings_walk<1024, false, true>(q, 0, D, term_range, tdoc, ttf, dl, idf, V, avgdl, D, q_terms, q_weights, q_ptr,
+                                                            out, mark_all, max_out != nullptr);
+    if (max_out) {
+        const double m = block_max<1024>(mx);
+        if (threadIdx.x == 0) max_out[q] = m;
+    }
+}
+
+// The same walk with the document range cut into slices (round 4).  One workgroup per query is one workgroup per CU for a batch of 256:
+// 16 waves that clear, scatter into and re-read an 800 KB row at ~15 GB/s -- the kernel took 166 us for 620 MB, most of it latency.  A
+// document's float64 additions only have to keep the QUERY'S TERM ORDER, and documents are independent, so a workgroup may take any
+// document range: grid (query, part), each workgroup the postings of its range -- found through a table of every term's posting offsets
+// at BM25_SLICES fixed document boundaries, built with the index -- and a partial row maximum; four 512-thread workgroups share a CU.
+constexpr int BM25_SLICES = 8;
+__global__ __launch_bounds__(512) void bm25_postings_sliced_kernel(const int64_t* __restrict__ tslice, const int32_t* __restrict__ tdoc,
+                                                                   const int32_t* __restrict__ ttf, const int32_t* __restrict__ dl,
+                                                                   const double* __restrict__ idf, int32_t V, double avgdl, int64_t D, int64_t slice_docs,
+                                                                   int per_part, const int32_t* __restrict__ q_terms,
+                                                                   const double* __restrict__ q_weights, const int32_t* __restrict__ q_ptr,
+                                                                   double* __restrict__ out, uint8_t* __restrict__ mark_all, double* __restrict__ max_part) {
+    const int q = blockIdx.x, part = blockIdx.y;
+    const int s0 = part * per_part, s1 = s0 + per_part;                       // fixed slices [s0, s1)
+    const int64_t lo = (int64_t)s0 * slice_docs, hi = s1 == BM25_SLICES ? D : (int64_t)s1 * slice_docs;      // lo, hi multiples of 8 (D % 8 == 0)
+    auto term_range = [=](int32_t t, int64_t& b, int64_t& e) {
+        b = tslice[(int64_t)t * (BM25_SLICES + 1) + s0];
+        e = tslice[(int64_t)t * (BM25_SLICES + 1) + s1];
+    };
+    const double mx = bm25_postings_walk<512, true, false>(q, lo, hi, term_range, tdoc, ttf, dl, idf, V, avgdl, D, q_terms, q_weights, q_ptr,
+                                                           out, mark_all, max_part != nullptr);
     if (max_part) {
-        __shared__ double part_s[NT / 64];
-        for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-        if ((tid & 63) == 0) part_s[tid >> 6] = mx;
-        __syncthreads();
-        if (tid == 0) {
-            double m = part_s[0];
-            for (int w = 1; w < NT / 64; ++w) m = fmax(m, part_s[w]);
-            max_part[(int64_t)q * gridDim.y + part] = m;
-        }
+        const double m = block_max<512>(mx);
+        if (threadIdx.x == 0) max_part[(int64_t)q * gridDim.y + part] = m;
     }
 }
 __global__ void bm25_max_reduce_kernel(const double* __restrict__ parts, int nparts, double* __restrict__ max_out, int nq) {
@@ -451,28 +362,20 @@ __global__ __launch_bounds__(1024) void rowmax_kernel(const T* __restrict__ v, i
     const T* row = v + (int64_t)blockIdx.x * n;
     T m = -INFINITY;
     for (int64_t i = threadIdx.x; i < n; i += 1024) m = fmax(m, row[i]);
-    for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o));
-    __shared__ T part[16];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        T x = threadIdx.x < 16 ? part[threadIdx.x] : (T)-INFINITY;
-        for (int o = 8; o >= 1; o >>= 1) x = fmax(x, __shfl_xor(x, o));
-        if (threadIdx.x == 0) out[blockIdx.x] = x;
-    }
-}
-
-// order-preserving u32 image of a float (for atomicMax); 0 is below every real value
-__device__ __forceinline__ uint32_t float_order_key(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float float_from_key(uint32_t k) {
-    return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k);
+    m = block_max<1024>(m);
+    if (threadIdx.x == 0) out[blockIdx.x] = m;
 }
 
 // webui.py:377-383 (and :208 with norm flags off):
 //   out = wa * (a / max_a) + (double)((float)wb * (b / max_b))
+// The one statement of it: the batched combine, the fused top-k and the one-query kernels all call this.  A maximum <= 0 (or absent:
+// pass 0) means "do not divide".
+__device__ __forceinline__ double combine_score(double A, float B, double max_a, float max_b, double wa, float wb) {
+    if (max_a > 0.0) A = A / max_a;               // webui.py:379-380
+    if (max_b > 0.0f) B = B / max_b;              // webui.py:377-378
+    const float wB = wb * B;                      // python float * float32 array stays float32
+    return wa * A + (double)wB;                   // webui.py:383
+}
 __global__ __launch_bounds__(256) void combine_kernel(const double* __restrict__ a, const float* __restrict__ b, int64_t n,
                                                       double wa, float wb, const double* __restrict__ max_a,
                                                       const float* __restrict__ max_b, const uint32_t* __restrict__ max_b_keys,
@@ -480,18 +383,9 @@ __global__ __launch_bounds__(256) void combine_kernel(const double* __restrict__
     const int q = blockIdx.y;
     const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (d >= n) return;
-    double A = a[(int64_t)q * n + d];
-    float B = b[(int64_t)q * n + d];
-    if (max_a) {
-        const double m = max_a[q];
-        if (m > 0.0) A = A / m;
-    }
-    if (max_b || max_b_keys) {
-        const float m = max_b ? max_b[q] : float_from_key(max_b_keys[q]);
-        if (m > 0.0f) B = B / m;
-    }
-    const float wB = wb * B;                      // python float * float32 array stays float32
-    out[(int64_t)q * n + d] = wa * A + (double)wB;
+    const double ma = max_a ? max_a[q] : 0.0;
+    const float mb = max_b ? max_b[q] : (max_b_keys ? float_from_key(max_b_keys[q]) : 0.0f);
+    out[(int64_t)q * n + d] = combine_score(a[(int64_t)q * n + d], b[(int64_t)q * n + d], ma, mb, wa, wb);
 }
 
 // =============================================================================================
@@ -777,33 +671,6 @@ __device__ __forceinline__ double key_value(uint64_t k) {
     return __longlong_as_double((long long)u);
 }
 
-// block-wide exclusive scan of one int per thread (1024 threads); returns exclusive prefix, total in *total
-__device__ __forceinline__ int block_excl_scan(int x, int* scratch /*[17]*/, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int y = __shfl_up(incl, o);
-        if (lane >= o) incl += y;
-    }
-    if (lane == 63) scratch[wave] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int w = 0; w < 16; ++w) {
-            int t = scratch[w];
-            scratch[w] = run;
-            run += t;
-        }
-        scratch[16] = run;
-    }
-    __syncthreads();
-    const int res = scratch[wave] + incl - x;
-    *total = scratch[16];
-    __syncthreads();
-    return res;
-}
-
 // Monotone (non-decreasing) 12-bit digit of a score, uniform in VALUE over [-2, 2): the fast path of the
 // top-k histograms on it.  Everything below -2 (and NaN) is digit 0, everything from 2 up is 4095.
 __device__ __forceinline__ uint32_t value_digit(double x) {
@@ -845,7 +712,7 @@ __device__ unsigned long long g_topk_stamps[16];
 #endif
 
 // The score rows as the two addends of webui.py:377-383 instead of their sum: with `a` set the kernel computes
-// wa * (a / max_a) + (double)(wb * (b / max_b)) -- combine_kernel's expression, operation for operation -- wherever it reads a score,
+// wa * (a / max_a) + (double)(wb * (b / max_b)) (combine_score) wherever it reads a score,
 // and the batched search neither writes nor re-reads the combined rows (round 3: 20 B per score of traffic less, one launch less).
 struct TopkFused {
     const double* a = nullptr;       // [nq][n] BM25 scores
@@ -882,26 +749,12 @@ __global__ __launch_bounds__(1024) void topk_kernel(const double* __restrict__ v
     if (fused) {
         if (fz.max_b_parts) {        // the maximum over the product kernel's workgroups (exact: the same value rowmax_kernel finds in the stored row)
             const float* pp = fz.max_b_parts + (int64_t)(blockIdx.x >> 8) * (256 * 256) + (blockIdx.x & 255);
-            float v = tid < fz.parts ? pp[(int64_t)tid * 256] : -INFINITY;
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-            __shared__ float pmax[16];
-            if ((tid & 63) == 0) pmax[tid >> 6] = v;
-            __syncthreads();
-            v = pmax[0];
-#pragma unroll
-            for (int w = 1; w < 16; ++w) v = fmaxf(v, pmax[w]);
-            f_mb = v;
+            f_mb = block_max<1024>(tid < fz.parts ? pp[(int64_t)tid * 256] : -INFINITY);
         } else {
             f_mb = fz.max_b[blockIdx.x];
         }
     }
-    auto comb = [&](double A, float B) -> double {       // combine_kernel, operation for operation (the file is built with -ffp-contract=off)
-        if (f_ma > 0.0) A = A / f_ma;
-        if (f_mb > 0.0f) B = B / f_mb;
-        const float wB = fz.wb * B;
-        return fz.wa * A + (double)wB;
-    };
+    auto comb = [&](double A, float B) -> double { return combine_score(A, B, f_ma, f_mb, fz.wa, fz.wb); };
     auto val = [&](int64_t i) -> double { return fused ? comb(fa[i], fb[i]) : v[i]; };
     auto val2 = [&](int64_t i) -> double2 {              // scores i, i + 1 (i even, rows 16-byte aligned: `wide`)
         if (fused) {
@@ -1640,21 +1493,12 @@ __global__ __launch_bounds__(S1_THREADS) void search1_score_kernel(const Search1
         }
         step_a(3);
         __builtin_amdgcn_sched_barrier(0);
-        const double nrm = BM25_K1 * ((1.0 - BM25_B) + BM25_B * (dlv / avgdl));
+        const double nrm = bm25_length_norm(dlv, avgdl);
         for (int j = 0; j < Q.nt; ++j) {
             const double w = Q.weights[j];
             const int32_t tfv = stf[j][tid];
             const double idf_t = sidf[j];
-            const double tfd = (double)tfv;
-            const double sc = idf_t * ((tfd * (BM25_K1 + 1.0)) / (tfd + nrm));
-            if (w < 0.0) {
-                if (tfv > 0) masked = true;
-            } else if (w > REQUIRE_MAGIC) {
-                s += (w - REQUIRE_MAGIC) * sc;
-                if (tfv == 0) masked = true;
-            } else {
-                s += w * sc;
-            }
+            bm25_accumulate(w, tfv, bm25_term_score(idf_t, (double)tfv, nrm), s, masked);
         }
         if (masked) s = -INFINITY;
         // ---- the rest of the index stream
@@ -1705,22 +1549,13 @@ __global__ __launch_bounds__(S1_THREADS) void search1_score_kernel(const Search1
                 if (ti == Q.terms[j]) stf[j][tid] = tf[i];
         }
     }
-    const double nrm = BM25_K1 * ((1.0 - BM25_B) + BM25_B * (dlv / avgdl));
+    const double nrm = bm25_length_norm(dlv, avgdl);
     for (int j = 0; j < Q.nt; ++j) {
         const int32_t t = Q.terms[j];
         const double w = Q.weights[j];
         const int32_t tfv = stf[j][tid];
         const double idf_t = (t >= 0 && t < V) ? idf[t] : 0.0;
-        const double tfd = (double)tfv;
-        const double sc = idf_t * ((tfd * (BM25_K1 + 1.0)) / (tfd + nrm));
-        if (w < 0.0) {
-            if (tfv > 0) masked = true;
-        } else if (w > REQUIRE_MAGIC) {
-            s += (w - REQUIRE_MAGIC) * sc;
-            if (tfv == 0) masked = true;
-        } else {
-            s += w * sc;
-        }
+        bm25_accumulate(w, tfv, bm25_term_score(idf_t, (double)tfv, nrm), s, masked);
     }
     if (masked) s = -INFINITY;
     // ---- the index stream
@@ -1864,12 +1699,7 @@ __global__ __launch_bounds__(256) void search1_combine_kernel(const double* __re
     for (int c = 0; c < gw; ++c) {
         const int64_t d = (group * gw + c) * 64 + lane;
         if (d < D) {
-            double A = bm[d];
-            float B = sim[d];
-            if (ma > 0.0) A = A / ma;                    // webui.py:379-380
-            if (mb > 0.0f) B = B / mb;                   // webui.py:377-378
-            const float wB = wb * B;
-            const double f = wa * A + (double)wB;        // webui.py:383
+            const double f = combine_score(bm[d], sim[d], ma, mb, wa, wb);
             final_out[d] = f;
             m = fmax(m, f);
         }
@@ -1881,60 +1711,68 @@ __global__ __launch_bounds__(256) void search1_combine_kernel(const double* __re
 }
 
 constexpr int S1_COLLECT_THREADS = 1024;
-__global__ __launch_bounds__(S1_COLLECT_THREADS) void search1_collect_kernel(const double* __restrict__ final_in, int64_t D, int k,
-                                                                             const unsigned long long* __restrict__ wmax, int groups,
-                                                                             uint32_t* __restrict__ bcnt, uint32_t* __restrict__ bflag,
-                                                                             unsigned long long* __restrict__ bkey, uint32_t* __restrict__ bid, int bcap) {
-    __shared__ uint32_t hist[4096];
-    __shared__ int scan[17];
-    __shared__ int sh_dmin;
-    __shared__ uint32_t sh_n, sh_other;
-    const int tid = threadIdx.x, lane = tid & 63;
-    // threshold digit: the digit of the k-th largest group maximum (every workgroup finds it itself: 8 B x G from L2)
-    for (int i = tid; i < 4096; i += S1_COLLECT_THREADS) hist[i] = 0;
+struct S1HandOn {                // LDS of one workgroup of search1_collect_kernel / search1_finish_kernel
+    uint32_t hist[4096];
+    int scan[17];
+    int dmin;
+    uint32_t n, other;
+};
+
+// Threshold digit = the digit of the k-th largest of `groups` values; group_digit(g) is value_digit of group g's value.  Every
+// workgroup finds it itself (the values come from L2).  Digit 0 is everything below -2: combined scores are >= -1 unless a required /
+// excluded term made them -inf, so with fewer than k groups above it the threshold is digit 1 -- every finite score is a candidate and
+// the ranking fills up with -inf ties.  Also clears the candidate counter and the flag s1_hand_on uses.
+template <typename F>
+__device__ __forceinline__ uint32_t s1_threshold_digit(S1HandOn& sh, int groups, int k, F group_digit) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 4096; i += S1_COLLECT_THREADS) sh.hist[i] = 0;
     if (tid == 0) {
-        sh_n = 0;
-        sh_other = 0;
+        sh.n = 0;
+        sh.other = 0;
     }
     __syncthreads();
     for (int g0 = 0; g0 < groups; g0 += S1_COLLECT_THREADS) {
         const int g = g0 + tid;
-        const uint32_t dg = g < groups ? value_digit(key_value(wmax[g])) : 0u;
-        hist_add(hist, dg, dg != 0u);
+        const uint32_t dg = g < groups ? group_digit(g) : 0u;
+        hist_add(sh.hist, dg, dg != 0u);
     }
     __syncthreads();
-    // Digit 0 is everything below -2: combined scores are >= -1 unless a required / excluded term made them -inf, so with fewer
-    // than k groups above it the threshold is digit 1 -- every finite score is a candidate and the ranking fills up with -inf ties.
+    // walk the bins from the top: thread t owns reversed bins 4t .. 4t + 3
     int own[4], ssum = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int bin = 4095 - (4 * tid + j);
-        own[j] = bin >= 1 ? (int)hist[bin] : 0;
+        own[j] = bin >= 1 ? (int)sh.hist[bin] : 0;
         ssum += own[j];
     }
     int total;
-    const int excl = block_excl_scan(ssum, scan, &total);
-    if (tid == 0) sh_dmin = 1;
+    const int excl = block_excl_scan(ssum, sh.scan, &total);
+    if (tid == 0) sh.dmin = 1;
     __syncthreads();
     if (excl < k && k <= excl + ssum) {
         int run = excl;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (run < k && k <= run + own[j]) sh_dmin = 4095 - (4 * tid + j);
+            if (run < k && k <= run + own[j]) sh.dmin = 4095 - (4 * tid + j);
             run += own[j];
         }
     }
     __syncthreads();
-    const uint32_t dmin = (uint32_t)sh_dmin;
-    const int64_t d = (int64_t)blockIdx.x * S1_COLLECT_THREADS + tid;
-    const double f = d < D ? final_in[d] : -INFINITY;
+    return (uint32_t)sh.dmin;
+}
+
+// Document d (score f) is a candidate if its digit is at or above the threshold: the candidates go to this workgroup's own slots (LDS
+// counter, one add per wave), their number and "a finite score stayed behind" to bcnt / bflag.
+__device__ __forceinline__ void s1_hand_on(S1HandOn& sh, double f, int64_t d, int64_t D, uint32_t dmin, uint32_t* __restrict__ bcnt,
+                                           uint32_t* __restrict__ bflag, unsigned long long* __restrict__ bkey, uint32_t* __restrict__ bid, int bcap) {
+    const int tid = threadIdx.x, lane = tid & 63;
     const bool take = d < D && value_digit(f) >= dmin;
-    if (d < D && !take && f != -INFINITY) sh_other = 1u;
+    if (d < D && !take && f != -INFINITY) sh.other = 1u;
     const uint64_t m = __ballot(take);
-    if (m != 0) {                                   // candidates go to this workgroup's own slots (LDS counter, one add per wave)
+    if (m != 0) {
         uint32_t base = 0;
         const int leader = __ffsll((unsigned long long)m) - 1;
-        if (lane == leader) base = atomicAdd(&sh_n, (uint32_t)__popcll(m));
+        if (lane == leader) base = atomicAdd(&sh.n, (uint32_t)__popcll(m));
         base = __shfl(base, leader);
         if (take) {
             const uint32_t slot = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
@@ -1946,9 +1784,21 @@ __global__ __launch_bounds__(S1_COLLECT_THREADS) void search1_collect_kernel(con
     }
     __syncthreads();
     if (tid == 0) {
-        bcnt[blockIdx.x] = sh_n;                    // may exceed the cap: the ranking kernel then takes the exact path
-        bflag[blockIdx.x] = sh_other;
+        bcnt[blockIdx.x] = sh.n;                    // may exceed the cap: the ranking kernel then takes the exact path
+        bflag[blockIdx.x] = sh.other;
     }
+}
+
+// The group values are the group maxima search1_combine_kernel stored; the scores are its combined scores.
+__global__ __launch_bounds__(S1_COLLECT_THREADS) void search1_collect_kernel(const double* __restrict__ final_in, int64_t D, int k,
+                                                                             const unsigned long long* __restrict__ wmax, int groups,
+                                                                             uint32_t* __restrict__ bcnt, uint32_t* __restrict__ bflag,
+                                                                             unsigned long long* __restrict__ bkey, uint32_t* __restrict__ bid, int bcap) {
+    __shared__ S1HandOn sh;
+    const uint32_t dmin = s1_threshold_digit(sh, groups, k, [&](int g) { return value_digit(key_value(wmax[g])); });
+    const int64_t d = (int64_t)blockIdx.x * S1_COLLECT_THREADS + threadIdx.x;
+    const double f = d < D ? final_in[d] : -INFINITY;
+    s1_hand_on(sh, f, d, D, dmin, bcnt, bflag, bkey, bid, bcap);
 }
 
 // search1_combine_kernel + search1_collect_kernel in ONE launch (round 4): the threshold no longer comes from the group maxima of the
@@ -1956,92 +1806,28 @@ __global__ __launch_bounds__(S1_COLLECT_THREADS) void search1_collect_kernel(con
 // WITNESS documents the score kernel left behind, two per wave: a workgroup combines the 2 G witnesses itself (G x 32 B from L2),
 // takes per wave the larger of its two, and uses the digit of the k-th largest of those G values -- still a lower bound of the k-th
 // largest combined score, because every value belongs to a real document and no two waves share one.  Then it combines its own 1024
-// documents (webui.py:377-383, combine_kernel's expression, operation for operation), stores them for the fallback paths and the
-// caller, and hands on the candidates as search1_collect_kernel does.  Used when a group is a whole wave (gl == 64, gw == 1: 160 k <=
-// D <= 262 k documents at k = 100); other sizes keep the two kernels.
+// documents (combine_score), stores them for the fallback paths and the caller, and hands on the candidates.  Used when a group is a
+// whole wave (gl == 64, gw == 1: 160 k <= D <= 262 k documents at k = 100); other sizes keep the two kernels.
 __global__ __launch_bounds__(S1_COLLECT_THREADS) void search1_finish_kernel(const double* __restrict__ bm, const float* __restrict__ sim, int64_t D, int k,
                                                                             double wa, float wb, double* __restrict__ final_out,
                                                                             const Search1State* __restrict__ st, const Search1Witness* __restrict__ wit,
                                                                             int groups, uint32_t* __restrict__ bcnt, uint32_t* __restrict__ bflag,
                                                                             unsigned long long* __restrict__ bkey, uint32_t* __restrict__ bid, int bcap) {
-    __shared__ uint32_t hist[4096];
-    __shared__ int scan[17];
-    __shared__ int sh_dmin;
-    __shared__ uint32_t sh_n, sh_other;
-    const int tid = threadIdx.x, lane = tid & 63;
+    __shared__ S1HandOn sh;
     double ma;
     float mb;
     search1_maxima(st, &ma, &mb);
-    auto comb = [&](double A, float B) -> double {       // search1_combine_kernel / combine_kernel, operation for operation
-        if (ma > 0.0) A = A / ma;
-        if (mb > 0.0f) B = B / mb;
-        const float wB = wb * B;
-        return wa * A + (double)wB;
-    };
-    for (int i = tid; i < 4096; i += S1_COLLECT_THREADS) hist[i] = 0;
-    if (tid == 0) {
-        sh_n = 0;
-        sh_other = 0;
-    }
-    __syncthreads();
-    for (int g0 = 0; g0 < groups; g0 += S1_COLLECT_THREADS) {
-        const int g = g0 + tid;
-        uint32_t dg = 0u;
-        if (g < groups) {
-            const Search1Witness w = wit[g];
-            dg = value_digit(fmax(comb(w.bm_a, w.sim_a), comb(w.bm_b, w.sim_b)));
-        }
-        hist_add(hist, dg, dg != 0u);
-    }
-    __syncthreads();
-    int own[4], ssum = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int bin = 4095 - (4 * tid + j);
-        own[j] = bin >= 1 ? (int)hist[bin] : 0;
-        ssum += own[j];
-    }
-    int total;
-    const int excl = block_excl_scan(ssum, scan, &total);
-    if (tid == 0) sh_dmin = 1;
-    __syncthreads();
-    if (excl < k && k <= excl + ssum) {
-        int run = excl;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (run < k && k <= run + own[j]) sh_dmin = 4095 - (4 * tid + j);
-            run += own[j];
-        }
-    }
-    __syncthreads();
-    const uint32_t dmin = (uint32_t)sh_dmin;
-    const int64_t d = (int64_t)blockIdx.x * S1_COLLECT_THREADS + tid;
+    const uint32_t dmin = s1_threshold_digit(sh, groups, k, [&](int g) {
+        const Search1Witness w = wit[g];
+        return value_digit(fmax(combine_score(w.bm_a, w.sim_a, ma, mb, wa, wb), combine_score(w.bm_b, w.sim_b, ma, mb, wa, wb)));
+    });
+    const int64_t d = (int64_t)blockIdx.x * S1_COLLECT_THREADS + threadIdx.x;
     double f = -INFINITY;
     if (d < D) {
-        f = comb(bm[d], sim[d]);
+        f = combine_score(bm[d], sim[d], ma, mb, wa, wb);
         final_out[d] = f;
     }
-    const bool take = d < D && value_digit(f) >= dmin;
-    if (d < D && !take && f != -INFINITY) sh_other = 1u;
-    const uint64_t m = __ballot(take);
-    if (m != 0) {
-        uint32_t base = 0;
-        const int leader = __ffsll((unsigned long long)m) - 1;
-        if (lane == leader) base = atomicAdd(&sh_n, (uint32_t)__popcll(m));
-        base = __shfl(base, leader);
-        if (take) {
-            const uint32_t slot = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-            if (slot < (uint32_t)bcap) {
-                bkey[(int64_t)blockIdx.x * bcap + slot] = order_key(f);
-                bid[(int64_t)blockIdx.x * bcap + slot] = (uint32_t)d;
-            }
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        bcnt[blockIdx.x] = sh_n;
-        bflag[blockIdx.x] = sh_other;
-    }
+    s1_hand_on(sh, f, d, D, dmin, bcnt, bflag, bkey, bid, bcap);
 }
 
 // Handle-less entry points (hipts_combine / hipts_topk) keep their small scratch here: one slot

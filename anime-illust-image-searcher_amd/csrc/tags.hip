@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "common.h"
+#include "rank_util.h"
 
 using namespace hipts;
 
@@ -29,16 +30,6 @@ struct hipts_tagsel {
 };
 
 namespace {
-
-__device__ __forceinline__ uint32_t order_key32(float x) {
-    if (x == 0.0f) x = 0.0f;
-    const uint32_t u = __float_as_uint(x);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key32_value(uint32_t k) {
-    const uint32_t u = (k >> 31) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(u);
-}
 
 // sorts keys[0..npad) descending
 __device__ void bitonic_desc(uint64_t* keys, int npad) {
@@ -66,7 +57,7 @@ __device__ void select_category(const float* __restrict__ probs, const int32_t* 
     const int tid = threadIdx.x, nthr = blockDim.x;
     for (int i = tid; i < npad; i += nthr) {
         uint64_t k = 0;
-        if (i < n) k = ((uint64_t)order_key32(probs[idx[i]]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)i);
+        if (i < n) k = ((uint64_t)float_order_key_canon(probs[idx[i]]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)i);
         keys[i] = k;
     }
     __syncthreads();
@@ -77,8 +68,8 @@ __device__ void select_category(const float* __restrict__ probs, const int32_t* 
         double best = -INFINITY;
         int besti = 0x7fffffff;
         for (int i = tid; i < n - 1; i += nthr) {
-            const double a = (double)key32_value((uint32_t)(keys[i] >> 32));
-            const double b = (double)key32_value((uint32_t)(keys[i + 1] >> 32));
+            const double a = (double)float_from_key((uint32_t)(keys[i] >> 32));
+            const double b = (double)float_from_key((uint32_t)(keys[i + 1] >> 32));
             const double dif = a - b;
             if (dif > best) {
                 best = dif;
@@ -106,8 +97,8 @@ __device__ void select_category(const float* __restrict__ probs, const int32_t* 
                     b = sh_d[w];
                     bi = sh_i[w];
                 }
-            const double a0 = (double)key32_value((uint32_t)(keys[bi] >> 32));
-            const double a1 = (double)key32_value((uint32_t)(keys[bi + 1] >> 32));
+            const double a0 = (double)float_from_key((uint32_t)(keys[bi] >> 32));
+            const double a1 = (double)float_from_key((uint32_t)(keys[bi + 1] >> 32));
             double t = (a0 + a1) / 2;                                                // :65
             if (floor015 && !(t > 0.15)) t = 0.15;                                   // :201 max(0.15, t)
             sh_d[16] = t;
@@ -121,7 +112,7 @@ __device__ void select_category(const float* __restrict__ probs, const int32_t* 
     // kept labels are a prefix of the sorted order: count entries with p > thresh
     int cnt = 0;
     for (int i = tid; i < n; i += nthr)
-        if ((double)key32_value((uint32_t)(keys[i] >> 32)) > thresh) ++cnt;
+        if ((double)float_from_key((uint32_t)(keys[i] >> 32)) > thresh) ++cnt;
     for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
     if ((tid & 63) == 0) sh_i[tid >> 6] = cnt;
     __syncthreads();

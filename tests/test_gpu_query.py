@@ -2,6 +2,8 @@
 Bit-exact for float64 BM25, float32 index products (k-ordered fma chain) and ranking."""
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -81,6 +83,65 @@ def test_bm25_libm_idf_within_one_ulp(corpus20k):
     b = BM25Index(ptr, terms, V, numpy_idf=True).export()["idf"]
     nz = b != 0
     assert np.max(np.abs(a[nz] - b[nz]) / b[nz]) <= 2.3e-16      # tolerance: 1 ulp of float64
+
+
+# Every BM25 kernel and arm against the oracle.  The switches that choose a kernel are read once per process, hence the children: each
+# loads this file and runs the same check under one setting.
+_ARM_CHILD = r"""
+import importlib.util, sys
+for p in %(paths)r:
+    sys.path.insert(0, p)
+spec = importlib.util.spec_from_file_location("query_arms", %(file)r)
+m = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(m)
+m.%(call)s
+"""
+
+
+def _run_in_child(call, setting):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    name, value = setting.split("=")
+    code = _ARM_CHILD % {"paths": [os.path.join(root, "anime-illust-image-searcher_amd"), root], "file": os.path.abspath(__file__), "call": call}
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, **{name: value}), timeout=300)
+    assert r.returncode == 0, (setting, r.stdout[-2000:], r.stderr[-2000:])
+
+
+def _check_bm25_kernels(sizes):
+    """V = 200, about 20 distinct tags per document; six queries in one call: plain, a required term that is present, a required term
+    nobody has, an excluded term, eleven terms (past the posting walk's eight prefetched ones, with an excluded and a required term
+    among the late ones), and the empty query."""
+    from hiptagsearch import synth
+    from hiptagsearch.bm25 import BM25Index
+    from oracle import bm25 as obm25
+    V = 200
+    qs = [{3: 1.0, 10: 1.0}, {4: 1001.0, 12: 1.0}, {7: 1.0, V + 5: 1001.0}, {1: -1.0, 8: 1.0},
+          dict(zip([15, 16, 17, 18, 19, 20, 21, 22, 23, 1, 0], [1.0, 1.0, 2.0, 1.0, 1.0, 3.0, 1.0, 1.0, 1.0, -1.0, 1002.0])), {}]
+    for D in sizes:
+        ptr, terms = synth.tag_corpus(D=D, V=V, seed=100 + D)
+        idx = BM25Index(ptr, terms, V)
+        corpus, idf, avgdl, _, dl = _oracle_index(ptr, terms, V)
+        optr, oterm, otf = obm25.to_csr(corpus)
+        idf_arr = np.zeros(V)
+        for t, v in idf.items():
+            idf_arr[t] = v
+        got = idx.score(qs)
+        for i, q in enumerate(qs):
+            want = obm25.bm25_score_csr(optr, oterm, otf, idf_arr, avgdl, dl, list(q.keys()), list(q.values()))
+            assert got[i].tobytes() == want.tobytes(), "D %d query %d: %r" % (D, i, q)
+        assert np.isinf(got[2]).all() and not got[5].any()      # nobody has the required term; no term at all
+        assert np.isfinite(got[1]).any() and np.isinf(got[1]).any() and np.isfinite(got[4]).any() and np.isinf(got[4]).any()
+
+
+@pytest.mark.parametrize("setting", [None, "HIPTS_BM25=scan", "HIPTS_BM25_PARTS=1", "HIPTS_BM25_PARTS=2"])
+def test_bm25_every_kernel_bit_exact(setting):
+    """The posting walk in all its forms, bit for bit against oracle.bm25.bm25_score_csr.  Default dispatch: D = 1003 (one workgroup per
+    query, a row that is no multiple of 8: the scalar clear / re-read arms), D = 1000 (the same kernel, 8 documents per step), D = 8192
+    (the smallest sliced index, slices of 1024 documents, one slice per workgroup).  Then D = 8192 in a child process each for the
+    document-major scan kernel, the unsliced kernel on a sliceable index, and four slices per workgroup."""
+    if setting is None:
+        _check_bm25_kernels([1003, 1000, 8192])
+    else:
+        _run_in_child("_check_bm25_kernels([8192])", setting)
 
 
 # --------------------------------------------------------------------------------- similarity
@@ -318,6 +379,66 @@ def test_search_one_query_many_in_a_row(corpus20k):
             _lib.call("hiptsdbg_search1_last", bm._h, ctypes.byref(c), ctypes.byref(fast))
             decided += fast.value
         assert 0 <= decided <= len(qs)
+
+
+def _check_one_query_arms():
+    """D = 8192 (the one-query path's floor), dim 300, V = 400.  Documents 0 .. 127 carry 60 distinct tags each: the first score
+    workgroup's span is 7680 term ids, more than the 6144 it can stage in LDS, so it walks its lists in memory; every other workgroup
+    stages.  k = 10: 128 groups of 64 documents >= 25, threshold and hand-on in search1_finish_kernel; k = 100: groups of 32,
+    search1_combine_kernel + search1_collect_kernel."""
+    import ctypes
+    from hiptagsearch import _lib, synth
+    from hiptagsearch.bm25 import BM25Index
+    from hiptagsearch.index import Similarity
+    from hiptagsearch.search import SearchEngine
+    from oracle import bm25 as obm25
+    from oracle import search as osearch
+    D, dim, V = 8192, 300, 400
+    ptr0, terms0 = synth.tag_corpus(D=D, V=V, seed=21)
+    rng = np.random.default_rng(22)
+    docs = [rng.choice(V, 60, replace=False).astype(np.int32) for _ in range(128)] + [terms0[ptr0[d]:ptr0[d + 1]] for d in range(128, D)]
+    ptr = np.zeros(D + 1, np.int64)
+    ptr[1:] = np.cumsum([len(x) for x in docs])
+    terms = np.concatenate(docs)
+    assert ptr[128] == 7680
+    rows = synth.index_vectors(D, dim, seed=23)
+    bm = BM25Index(ptr, terms, V)
+    index = Similarity("idx", None, dim, capacity=D)
+    index.add_matrix(rows)
+    eng = SearchEngine(None, index, {}, bm, [])
+    head = [int(docs[0][0]), int(docs[100][5]), int(docs[127][59])]                  # terms of documents 0 .. 127
+    qs = [{3: 1.0, 17: 1.0}, {5: 1001.0, 40: 1.0}, {2: -1.0, 9: 1.0, 30: 2.0}, {head[0]: 1.0, head[1]: 1002.0, head[2]: -1.0}]
+    qv = rng.standard_normal((len(qs), dim))
+    qv = (qv / np.linalg.norm(qv, axis=1, keepdims=True)).astype(np.float32)
+    corpus, idf, avgdl, _, dl = _oracle_index(ptr, terms, V)
+    optr, oterm, otf = obm25.to_csr(corpus)
+    idf_arr = np.zeros(V)
+    for t, v in idf.items():
+        idf_arr[t] = v
+    finals = [osearch.combine(obm25.bm25_score_csr(optr, oterm, otf, idf_arr, avgdl, dl, list(q.keys()), list(q.values())),
+                              osearch.similarity(rows, qv[i])) for i, q in enumerate(qs)]
+    _lib.call("hipts_query_profile_enable", bm._h, 1)
+    for k in (10, 100):
+        for i, q in enumerate(qs):
+            wi, wv = osearch.topk(finals[i], k)
+            gi, gv = eng.score_topk([q], qv[i:i + 1], k)
+            np.testing.assert_array_equal(gi[0], wi, err_msg="query %d k %d" % (i, k))
+            assert gv[0].tobytes() == wv.tobytes(), "query %d k %d scores" % (i, k)
+    ms, n, by = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
+    _lib.call("hipts_query_profile_read", bm._h, 5, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(by))
+    assert n.value == 2 * len(qs) and ms.value > 0 and by.value > D * dim * 4 * 2 * len(qs)       # the one-query path really ran
+    _lib.call("hipts_query_profile_enable", bm._h, 0)
+
+
+@pytest.mark.parametrize("setting", [None, "HIPTS_S1_PIPE=0"])
+def test_search_one_query_remaining_arms_match_oracle(setting):
+    """The arms of the one-query path that the 20 000-document tests do not reach -- the score kernel's unstaged BM25 walk, both
+    hand-on forms at the smallest index, and (in a child process, HIPTS_S1_PIPE=0) the score kernel's sequential instantiation --
+    against the oracle: bm25_score_csr -> combine -> topk, ids and score bytes."""
+    if setting is None:
+        _check_one_query_arms()
+    else:
+        _run_in_child("_check_one_query_arms()", setting)
 
 
 # --------------------------------------------------------------------------------- full query function
