@@ -139,6 +139,7 @@ _SIGNATURES = {
     "hipts_crerank_destroy": [c_void_p],
     "hipts_crerank_run": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "hipts_crerank_read": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p],
+    "hipts_rerank_finish": [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "hipts_query_profile_enable": [c_void_p, c_int],
     "hipts_query_profile_read": [c_void_p, c_int, POINTER(c_double), POINTER(c_int64), POINTER(c_double)],
     "hipts_query_profile_name": [c_int, c_char_p, c_size_t],

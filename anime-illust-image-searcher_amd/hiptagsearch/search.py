@@ -9,7 +9,8 @@ The reference keeps model, index, dictionary and the BM25 statistics in module g
 `load_model()` fills (webui.py:649-689); here they live in a SearchEngine, and the module-level
 functions of the same names operate on the engine installed with `set_engine()`.
 Scoring (BM25, index product, normalise, combine, top-k) runs in libhip_tagsearch.so; parsing,
-the 10-document pseudo-relevance bookkeeping and the gap filter are host logic.
+the 10-document pseudo-relevance bookkeeping and the gap filter are host logic on the one-query path; for a batch
+(find_similar_documents_batch) the bookkeeping after the second ranking and the gap filter are one kernel, hipts_rerank_finish.
 """
 import ctypes
 import itertools
@@ -31,6 +32,7 @@ RERANKED_SCORE_WEIGHT: float = 0.3     # webui.py:56
 DIFF_FILTER_THRESH = 1e-6              # webui.py:58
 REQUIRE_TAG_MAGIC_NUMBER = 1000        # webui.py:60
 TOPK_MAX = 1024                        # hipts_topk limit
+BATCH_MAX = 256                        # queries per device pass of find_similar_documents_batch: what hipts_search is tuned for
 
 
 def filter_searched_result(ranked: List[Tuple[int, float]]) -> List[Tuple[int, float]]:
@@ -61,7 +63,8 @@ class SearchEngine:
         self.compat_rerank = compat_rerank
         self.cindex = None                     # cfeatures.CharacterFeatureIndex for 'character oriented' mode
         self.crerank = None                    # cfeatures.DeviceReranker once enable_device_crerank() was called (default: the host loop)
-        self.stats = {"queries": 0, "full_rank_fallbacks": 0, "rank_continuations": 0}     # full_rank_fallbacks: always 0 since round 3
+        self.stats = {"queries": 0, "full_rank_fallbacks": 0, "rank_continuations": 0,       # full_rank_fallbacks: always 0 since round 3
+                      "batch_single_reruns": 0}
         self._search_fn = _lib.load().hipts_search
         self._w_bm25, self._w_sim = c_double(BM25_WEIGHT), c_double(DOC2VEC_WEIGHT)
         # webui.py:623-646: path -> {tag: True} and path -> doc id, built from the same index file
@@ -70,6 +73,12 @@ class SearchEngine:
 
     # ---- webui.py:82-117 ------------------------------------------------------------------------
     def normalize_and_apply_weight_doc2vec(self, new_doc: str) -> np.ndarray:
+        tag_and_weight, all_weight = self._parse_doc2vec_query(new_doc)
+        vecs = self.model.infer_vectors([[t] for t, _ in tag_and_weight])            # :106, batched
+        return self._weighted_query_vector(tag_and_weight, all_weight, vecs)
+
+    @staticmethod
+    def _parse_doc2vec_query(new_doc: str) -> Tuple[List[Tuple[str, int]], int]:
         tag_and_weight: List[Tuple[str, int]] = []
         all_weight = 0
         for tag in new_doc.split(" "):
@@ -80,7 +89,10 @@ class SearchEngine:
             all_weight += wi
         if all_weight == 0:
             all_weight = 1
-        vecs = self.model.infer_vectors([[t] for t, _ in tag_and_weight])            # :106, batched
+        return tag_and_weight, all_weight
+
+    def _weighted_query_vector(self, tag_and_weight: List[Tuple[str, int]], all_weight: int, vecs) -> np.ndarray:
+        """webui.py:104-117 on the inferred vectors of the query's tags (one per entry of tag_and_weight, in order)."""
         got = np.zeros(self.model.vector_size)
         for (tag, weight), v in zip(tag_and_weight, vecs):
             v = v / np.linalg.norm(v)                                                # :107
@@ -173,8 +185,11 @@ class SearchEngine:
 
     # ---- webui.py:345-390 -----------------------------------------------------------------------
     def find_similar_documents(self, new_doc: str, topn: int = 50) -> List[Tuple[int, float]]:
-        import torch
         self.stats["queries"] += 1
+        return self._find_one(new_doc, topn)
+
+    def _find_one(self, new_doc: str, topn: int) -> List[Tuple[int, float]]:
+        import torch
         vec = self.normalize_and_apply_weight_doc2vec(new_doc)                        # :349
         qw, required, exclude = self.parse_bm25_query(new_doc)                        # :354-371
         D = len(self.index)
@@ -184,6 +199,73 @@ class SearchEngine:
         if self.search_mode == "character oriented":                                  # :386-388
             return self._cfeatures_rerank(ids[0], vals[0], topn, required, exclude)
         return self._doc2vec_rerank(final_dev, ids[0], vals[0], topn)                 # :390
+
+    def find_similar_documents_batch(self, queries: Sequence[str], topn: int = 50) -> List[List[Tuple[int, float]]]:
+        """find_similar_documents for a batch of queries as a front end accumulates them: per query the same list, ids and float bits.
+        Every device stage runs once per chunk of BATCH_MAX queries (first-stage search, one inference of the distinct top-ten
+        documents, second index pass, combine, ranking, hipts_rerank_finish); the query vectors and the ten-document rerank queries
+        are built on the host with the single path's own arithmetic (numpy's reduction order and BLAS are part of those bits).
+        A query whose result the ranks past TOPK_MAX decide (status 1 of hipts_rerank_finish) is answered by the one-query path and
+        counted in stats["batch_single_reruns"]."""
+        queries = list(queries)
+        if not queries or topn < 1 or len(self.index) <= 10 or self.search_mode == "character oriented":
+            return [self.find_similar_documents(q, topn) for q in queries]
+        parsed = [(self._parse_doc2vec_query(q), self.parse_bm25_query(q)[0]) for q in queries]       # KeyError before any launch
+        out: List[List[Tuple[int, float]]] = []
+        for c0 in range(0, len(queries), BATCH_MAX):
+            out += self._find_chunk(queries[c0:c0 + BATCH_MAX], parsed[c0:c0 + BATCH_MAX], topn)
+        return out
+
+    def _find_chunk(self, queries: List[str], parsed, topn: int) -> List[List[Tuple[int, float]]]:
+        import torch
+        nq, D = len(queries), len(self.index)
+        self.stats["queries"] += nq
+        # 1. query vectors: the distinct tags of the chunk in one inference (webui.py:106)
+        tags = list(dict.fromkeys(t for (tw, _), _ in parsed for t, _ in tw))
+        tag_vec = dict(zip(tags, self.model.infer_vectors([[t] for t in tags])))
+        qvecs = np.stack([self._weighted_query_vector(tw, allw, [tag_vec[t] for t, _ in tw]) for (tw, allw), _ in parsed])
+        # 2. first stage (webui.py:352,374-383)
+        k = min(TOPK_MAX, D)
+        final_dev = torch.empty((nq, D), dtype=torch.float64, device="cuda:%d" % self.index.device)
+        ids, vals = self.score_topk([qw for _, qw in parsed], qvecs, k, final_out=final_dev)
+        # 3. rerank queries: the distinct top-ten documents in one inference (webui.py:198-203)
+        top10 = np.ascontiguousarray(ids[:, :10])
+        docs = list(dict.fromkeys(top10.ravel().tolist()))
+        doc_vec = dict(zip(docs, self.model.infer_vectors([self._doc_tags(d) for d in docs])))
+        rq = np.stack([self._rerank_query_of(np.stack([doc_vec[d] for d in top10[q].tolist()]), [float(v) for v in vals[q, :10]])
+                       for q in range(nq)]).astype(np.float32)
+        lists, status = self._rerank_finish_batch(final_dev, rq, top10, topn)
+        # 5. the ranks past TOPK_MAX decide: the one-query path continues the ranking
+        for q in np.flatnonzero(status).tolist():
+            self.stats["batch_single_reruns"] += 1
+            lists[q] = self._find_one(queries[q], topn)
+        return lists
+
+    def _rerank_finish_batch(self, final_dev, rerank_queries: np.ndarray, top10: np.ndarray, topn: int):
+        """Stage 4 of the batch: second index pass (webui.py:205), 0.7 / 0.3 combine (:208, written over final_dev), ranking and the
+        finishing kernel.  Returns (lists, status int32 [nq]); lists[q] is the result where status[q] == 0."""
+        import torch
+        nq, D = final_dev.shape
+        dev = final_dev.device
+        rs_dev = torch.empty((nq, D), dtype=torch.float32, device=dev)
+        self.index.query(rerank_queries, out=rs_dev)
+        _lib.call("hipts_combine", _lib.ptr(final_dev), _lib.ptr(rs_dev), nq, c_int64(D), c_double(ORIGINAL_SCORE_WEIGHT),
+                  c_double(RERANKED_SCORE_WEIGHT), 0, 0, _lib.ptr(final_dev), self.index.device, _lib.current_stream_ptr())
+        k = min(TOPK_MAX, D)
+        rids_dev = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        rvals_dev = torch.empty((nq, k), dtype=torch.float64, device=dev)
+        _lib.call("hipts_topk", _lib.ptr(final_dev), nq, c_int64(D), k, _lib.ptr(rids_dev), _lib.ptr(rvals_dev), _lib.DEVICE, self.index.device,
+                  _lib.current_stream_ptr())
+        cap = min(topn, 10 + k)
+        docs = np.empty((nq, cap), dtype=np.int32)
+        scores = np.empty((nq, cap), dtype=np.float64)
+        counts = np.empty(nq, dtype=np.int32)
+        status = np.empty(nq, dtype=np.int32)
+        _lib.call("hipts_rerank_finish", _lib.ptr(rids_dev), _lib.ptr(rvals_dev), nq, k, c_int64(D), _lib.ptr(np.ascontiguousarray(top10, dtype=np.int32)),
+                  topn, _lib.ptr(docs), _lib.ptr(scores), _lib.ptr(counts), _lib.ptr(status), self.index.device, _lib.current_stream_ptr())
+        lists = [list(zip(docs[q, :c].tolist(), scores[q, :c].tolist())) if st == 0 else None
+                 for q, (c, st) in enumerate(zip(counts.tolist(), status.tolist()))]
+        return lists, status
 
     # ---- webui.py:255-342 -----------------------------------------------------------------------
     def enable_device_crerank(self, enable: bool = True):
@@ -228,6 +310,9 @@ class SearchEngine:
 
     def _rerank_query(self, top10_ids: Sequence[int], top10_scores: Sequence[float]) -> np.ndarray:
         vecs = self.model.infer_vectors([self._doc_tags(int(d)) for d in top10_ids])  # :198-199
+        return self._rerank_query_of(vecs, top10_scores)
+
+    def _rerank_query_of(self, vecs: np.ndarray, top10_scores: Sequence[float]) -> np.ndarray:
         mean = np.average(vecs.astype(np.float64), axis=0, weights=np.asarray(top10_scores, dtype=np.float64))   # :200 (value column)
         if self.compat_rerank:
             # webui.py:200-203 divides the (index, value) pairs by the Frobenius norm of the whole
@@ -310,6 +395,13 @@ def find_similar_documents(new_doc: str, topn: int = 50) -> List[Tuple[int, floa
     if _engine is None:
         raise RuntimeError("no SearchEngine installed: call set_engine(load_engine()) first (webui.py:585 load_model)")
     return _engine.find_similar_documents(new_doc, topn)
+
+
+def find_similar_documents_batch(queries: Sequence[str], topn: int = 50) -> List[List[Tuple[int, float]]]:
+    """find_similar_documents for a batch of queries on the installed engine."""
+    if _engine is None:
+        raise RuntimeError("no SearchEngine installed: call set_engine(load_engine()) first (webui.py:585 load_model)")
+    return _engine.find_similar_documents_batch(queries, topn)
 
 
 def load_engine(device: int = 0, d2v_model: str = "doc2vec_model", compat_rerank: bool = False) -> SearchEngine:

@@ -524,6 +524,27 @@ int hipts_crerank_run(hipts_crerank_t* h, hipts_index_t* features, const float* 
                       const int32_t* exc_ids, int64_t* counts_out, void* stream);
 int hipts_crerank_read(hipts_crerank_t* h, int query, int64_t first, int64_t count, int32_t* docs_out, double* scores_out);
 
+/* ------------------------------------------------------------------------------------------
+ * Normal-mode rerank, finishing stage for a batch.   Replaces the host list code of
+ * webui.py:210-240 after the second ranking: division by the maximum, the top ten pinned at 1.0,
+ * removal of their duplicates, the gap filter (webui.py:63-80) and the cut to topn.
+ *
+ * ranked_ids int32 [nq][k] / ranked_vals float64 [nq][k]: hipts_topk (device outputs) of rf = 0.7 * final + 0.3 * rs over n
+ * documents, k <= min(1024, n), n > 10.  top10 int32 [nq][10] (host): the first stage's ten best ids, in rank order.
+ * Per query, with mx = ranked_vals[0]: every value becomes v / mx when mx > 0 (IEEE division); the list F is the ten pairs
+ * (top10[j], 1.0) followed by the ranked entries whose id is not among the ten; index i is a cut point when
+ * d = F[i].score - F[i + 1].score has d != 0 and d < 1e-6.  The prefix is exhausted when k == n or ranked_vals[k - 1] == -inf.
+ * The list ends at t: the second cut point when there are two; else the only one when there is one; else its length L when
+ * the prefix is exhausted and L - 1 when it is not.  Emitted are, in order, the entries (id, score) with index < t and
+ * score > 0, at most topn: docs_out int32 [nq][cap], scores_out float64 [nq][cap] with cap = min(topn, 10 + k), the number
+ * in counts_out int32 [nq]; rows are defined up to their count.  status_out int32 [nq]: 0 = this is the result of the full
+ * ranking (two cut points, or an exhausted prefix, or topn entries emitted -- they all lie below anything a continuation of
+ * the ranking could change); 1 = the ranks past k decide it, the caller continues the ranking (hipts_topk_after).
+ * All outputs are host arrays; one kernel launch for all nq queries, one synchronisation (the copy back). */
+int hipts_rerank_finish(const int32_t* ranked_ids, const double* ranked_vals, int nq, int k, int64_t n, const int32_t* top10,
+                        int topn, int32_t* docs_out, double* scores_out, int32_t* counts_out, int32_t* status_out, int device,
+                        void* stream);
+
 /* Per-kernel timing of the query path for roofline accounting (bench.py), as hipts_vit_profile_* above: while enabled, every
  * kernel hipts_search launches is bracketed by HIP events on the stream it is launched on.  read() resolves them (synchronises) and
  * returns, for one kernel category, the summed device time, the launches and the ALGORITHMIC bytes those launches stand for
