@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "gemm_plan.h"
 #include "vit_internal.h"
 #include "model_host.h"
 #include "convnet.h"
@@ -296,12 +297,11 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
         // beta).  40 of a forward's 45 row_ln_kernel launches (5.2 % of its kernel time, each a pass over the fp32 stream) go; a stage's
         // first norm1 (its rows come from the downsample GEMM) and the downsample norms (their consumer is the im2col) stay.  Only when the
         // stage's residual launches are not the two-workgroups-per-CU kernel's anyway (that loop has no statistics epilogue): more tiles
-        // than half the CUs.  HIPTS_CCIP_LN_FOLD=0: off (A/B).
+        // than gemm_dw_size() takes (half the CUs by default).  HIPTS_CCIP_LN_FOLD=0: off (A/B).
         static const bool fold_env = !(getenv("HIPTS_CCIP_LN_FOLD") && atoi(getenv("HIPTS_CCIP_LN_FOLD")) == 0);
-        const int cus_dev = current_device_cus(nullptr);
         const int sblocks = (C + 255) / 256;
         const bool fold23 = fold_env && !fuse_ln && si >= c.attn_from_stage && C % 256 == 0 && M % 256 == 0 && h->stat_part.p &&
-                            (long)((M + 255) / 256) * sblocks * 4 > (long)cus_dev * 2;
+                            !gemm_dw_size((long)((M + 255) / 256) * sblocks, current_device_cus(nullptr), gemm_knobs());
         float* stat_p = fold23 ? h->stat_part.as<float>() + 2 * (size_t)i0 * h->pstat : nullptr;
         bool xn_folded = false;         // xn holds gamma * x + stat_p the row sums (not the LayerNorm itself)
         auto folded = [&](GemmArgs& ga, const float* u) {

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 
@@ -126,6 +127,15 @@ struct PerDevice {
     bool done(int dev) const { return dev >= 0 && dev < 64 && ((mask >> dev) & 1); }
     void mark(int dev) { if (dev >= 0 && dev < 64) mask |= (uint64_t)1 << dev; }
 };
+// The idiom for the commonest case: raise the dynamic-LDS limit of the listed kernels to lds_bytes, once per device
+template <typename... Kernels>
+int allow_dynamic_lds(PerDevice& once, int dev, int lds_bytes, Kernels... kernels) {
+    std::lock_guard<std::mutex> lk(once.mu);
+    if (once.done(dev)) return HIPTS_OK;
+    for (const void* k : {(const void*)kernels...}) HIPTS_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    once.mark(dev);
+    return HIPTS_OK;
+}
 // Compute units of the CURRENT device (cached per device); 256 if the runtime does not say.
 int current_device_cus(int* dev_out = nullptr);
 

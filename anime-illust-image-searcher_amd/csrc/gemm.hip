@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "gemm_plan.h"
 #include "vit_internal.h"
 
 namespace hipts {
@@ -1056,9 +1057,9 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(const GemmArgs a, int t
     if (trace && tid == 0) a.stamps[blockIdx.x * 8 + 4] = wall_clock64();
 }
 
-// HIPTS_GEMM selects the main loop for A/B runs: "pp" (default) ping-pong with 16-MFMA segments;
-// "pp2" 32-MFMA segments (better at K >= 4096, slightly worse on the ViT's K = 768 shapes);
-// "s3" three-stage 256x128 tile, two workgroups per CU; "v1" simple two-barrier loop.
+static_assert(GEMM_PLAN_TILE == BM && GEMM_PLAN_TILE == BN && GEMM_PLAN_BK == BK && GEMM_PLAN_HALF_BN == DW_BN && GEMM_PLAN_HALF_BN == S3_BN &&
+              GEMM_PLAN_LDS == LDS_BYTES && GEMM_PLAN_LDS3 == DW_LDS && GEMM_PLAN_LDS3 == S3_LDS, "gemm_plan.h plans for other tiles than these kernels'");
+
 // Bit mask over epilogue numbers whose launches take the 4-wave loop of gemm4.hip where it is built (HIPTS_GEMM_Q4; hiptsdbg_set_gemm_q4
 // changes it at run time for A/B runs and the comparison tests)
 std::atomic<long long> g_q4_mask{-1};
@@ -1071,234 +1072,133 @@ unsigned gemm_q4_mask() {
     return (unsigned)v;
 }
 
-int gemm_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("HIPTS_GEMM");
-        v = (e && strcmp(e, "v1") == 0) ? 0 : (e && strcmp(e, "pp2") == 0) ? 3 : (e && strcmp(e, "s3") == 0) ? 2 : (e && strcmp(e, "dw") == 0) ? 4 : 1;
-    }
-    return v;
+int gemm_variant() { return gemm_knobs().variant; }
+
+int gemm_plan_status(const GemmPlan& p, GemmEpilogue epi) {
+    if (p.error == 1) return set_error(HIPTS_ERR_INVALID, "half-precision operands are only built for the pp and dw GEMM loops");
+    if (p.error == 2) return set_error(HIPTS_ERR_INVALID, "gemm: e4m3 operands are not built for epilogue %d", (int)epi);
+    return HIPTS_OK;
 }
 
+// validate (launch_gemm), plan (gemm_plan.h), launch: nothing is decided here.  The `if constexpr` guards name the epilogues an
+// instantiation is built for; the plan never asks for another.
 template <int EPI>
 int launch_t(const GemmArgs& a, hipStream_t s) {
     int dev = 0;
-    const int cus_dev = current_device_cus(&dev);
-    static PerDevice attr;
-    {
-      std::lock_guard<std::mutex> lk(attr.mu);
-      if (!attr.done(dev)) {
-        HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, 7, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, 7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, 6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_pp2_kernel<EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_s3_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, S3_LDS));
-        HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_dw_kernel<EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, DW_LDS));
-        HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_dw_kernel<EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, DW_LDS));
-        attr.mark(dev);
-      }
-    }
-    const int tiles_m = (a.M + BM - 1) / BM;
-    if (a.op8) {
-        // e4m3 operands: the persistent ping-pong loop with full tiles only
-        if constexpr (EPI == EPI_STAR || EPI == EPI_RESID || EPI == EPI_RESCALE || EPI == EPI_RESID_LN || EPI == EPI_QK || EPI == EPI_VT ||
-                      EPI == EPI_BIAS) {
-            static PerDevice attr8;
-            {
-                std::lock_guard<std::mutex> lk(attr8.mu);
-                if (!attr8.done(dev)) {
-                    HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, 8, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-                    attr8.mark(dev);
-                }
+    const int cus = current_device_cus(&dev);
+    const GemmPlan p = gemm_plan((GemmEpilogue)EPI, a, cus, gemm_knobs(), gemm_q4_mask());
+    HIPTS_TRY(gemm_plan_status(p, (GemmEpilogue)EPI));
+    GemmArgs ar = a;
+    ar.raster_gm = p.raster_gm; ar.raster_gn = p.raster_gn; ar.epi_prio = p.epi_prio; ar.epi_prefetch = p.epi_prefetch;
+    ar.sk_first = p.sk_first; ar.sk_slices = p.sk_slices;
+    const bool f16 = a.f16 != 0;
+    auto go = [&](void (*kernel)(const GemmArgs, int, int)) { kernel<<<p.grid, p.block, p.lds_bytes, s>>>(ar, p.tiles_m, p.tiles_n); };
+    switch (p.loop) {
+        case HIPTSDBG_GEMM_Q4: return launch_gemm_q4((GemmEpilogue)EPI, ar, p, dev, s);
+        case HIPTSDBG_GEMM_PP_E4M3:
+            if constexpr (EPI == EPI_STAR || EPI == EPI_RESID || EPI == EPI_RESCALE || EPI == EPI_RESID_LN || EPI == EPI_QK || EPI == EPI_VT ||
+                          EPI == EPI_BIAS) {
+                static PerDevice once;
+                HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_pp_kernel<EPI, 8, true, true>));
+                go(gemm_pp_kernel<EPI, 8, true, true>);
             }
-            const int cus8 = cus_dev;
-            const int tiles_n = (a.N + BN - 1) / BN;
-            const int ntile = tiles_m * tiles_n;
-            const int slots = cus8 >= 8 ? cus8 / 8 * 8 : cus8;
-            gemm_pp_kernel<EPI, 8, true, true><<<ntile > slots ? slots : ntile, 512, LDS_BYTES, s>>>(a, tiles_m, tiles_n);
-            HIPTS_LAUNCH_CHECK();
-            return HIPTS_OK;
-        } else {
-            return set_error(HIPTS_ERR_INVALID, "gemm: e4m3 operands are not built for epilogue %d", (int)EPI);
+            break;
+        case HIPTSDBG_GEMM_DW: {
+            static PerDevice once;
+            HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_dw_kernel<EPI, false>, gemm_dw_kernel<EPI, true>));
+            if (f16) go(gemm_dw_kernel<EPI, true>);
+            else go(gemm_dw_kernel<EPI, false>);
+            break;
         }
-    }
-    int variant = gemm_variant();
-    if (EPI == EPI_QK_ROPE || EPI == EPI_SWIGLU || EPI == EPI_RESID_XG || EPI == EPI_RESID_XGI) variant = 1;      // staged epilogue only (pp, or dw below)
-    if (EPI == EPI_RESID_LN) variant = 1;      // the row reduction across waves uses the persistent loop's LDS scratch stage
-    if (variant == 1 && EPI != EPI_HEAD && EPI != EPI_RESID_LN && (!getenv("HIPTS_GEMM") || EPI == EPI_QK_ROPE || EPI == EPI_SWIGLU || EPI == EPI_RESID_XG || EPI == EPI_RESID_XGI)) {
-        // A launch with fewer 256 x 256 tiles than CUs (the CAFormer's late stages: 11 520 tokens x 512 columns
-        // = 90 tiles) leaves most of the chip idle; the 256 x 128 two-per-CU kernel has 2 x the tiles and
-        // 2 x the slots (measured, CCIP B36 @384 batch 20: 9.3 -> 8.8 ms; no difference at batch 64).
-        const int cus0 = cus_dev;
-        static const bool auto_dw = !(getenv("HIPTS_GEMM_AUTO_DW") && atoi(getenv("HIPTS_GEMM_AUTO_DW")) == 0);      // A/B
-        // (round 3: only below 3/4 of the CUs -- EVA02-L's q|k|v at batch 10 is 252 tiles on 256 CUs and runs 1 % faster on the persistent kernel.
-        // Late round 4: only up to HALF the CUs, where every 256 x 128 tile gets a CU of its own; between a half and the whole chip the
-        // persistent kernel with 192-row tiles -- one round of 3/4 the length -- is faster: CCIP batch 64, whose stage-2 launches are 144
-        // tiles, 3244 -> 3412 images/s, batch 20 (90 tiles) stays on this kernel: 2586 against 2553.  HIPTS_GEMM_DW_LIMIT = n/4 of the CUs.)
-        static const int dw_limit4 = getenv("HIPTS_GEMM_DW_LIMIT") ? atoi(getenv("HIPTS_GEMM_DW_LIMIT")) : 2;
-        if (auto_dw && (long)tiles_m * ((a.N + BN - 1) / BN) * 4 <= (long)cus0 * dw_limit4 && a.M > BM && !((EPI == EPI_RESID_XG || EPI == EPI_RESID_XGI || EPI == EPI_SWIGLU) && a.stat_part)) variant = 4;
-    }
-    {   // A/B: HIPTS_GEMM_DW_MASK = bit mask over epilogue numbers whose launches take the two-workgroups-per-CU 256 x 128 kernel (its
-        // residents run out of phase, so one's epilogue overlaps the other's main loop; it pays only where the epilogue is long and K short)
-        static const unsigned dw_mask = getenv("HIPTS_GEMM_DW_MASK") ? (unsigned)strtoul(getenv("HIPTS_GEMM_DW_MASK"), nullptr, 0) : 0u;
-#ifdef HIPTS_X_DW_STAT      // timing probe only (the statistics come out wrong): lets the masked epilogues take the dw kernel even with stat_part
-        if (variant == 1 && ((dw_mask >> (int)EPI) & 1u) && a.M > BM) variant = 4;
-#else
-        if (variant == 1 && ((dw_mask >> (int)EPI) & 1u) && a.M > BM && !((EPI == EPI_RESID_XG || EPI == EPI_RESID_XGI) && a.stat_part)) variant = 4;
-#endif
-    }
-    HIPTS_REQUIRE(!a.f16 || variant == 1 || variant == 4, "half-precision operands are only built for the pp and dw GEMM loops");
-    if (variant == 4) {
-        const int tiles_n = (a.N + DW_BN - 1) / DW_BN;
-        if (a.f16) gemm_dw_kernel<EPI, true><<<tiles_m * tiles_n, 256, DW_LDS, s>>>(a, tiles_m, tiles_n);
-        else gemm_dw_kernel<EPI, false><<<tiles_m * tiles_n, 256, DW_LDS, s>>>(a, tiles_m, tiles_n);
-    } else if (variant == 2) {
-        const int tiles_n = (a.N + S3_BN - 1) / S3_BN;
-        gemm_s3_kernel<EPI><<<tiles_m * tiles_n, 256, S3_LDS, s>>>(a, tiles_m, tiles_n);
-    } else {
-        const int tiles_n = (a.N + BN - 1) / BN;
-        if (variant == 3) {
+        case HIPTSDBG_GEMM_S3: {
+            static PerDevice once;
+            HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_s3_kernel<EPI>));
+            go(gemm_s3_kernel<EPI>);
+            break;
+        }
+        case HIPTSDBG_GEMM_V1: {
+            static PerDevice once;
+            HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_kernel<EPI>));
+            go(gemm_kernel<EPI>);
+            break;
+        }
+        case HIPTSDBG_GEMM_PP2: {
+            static PerDevice once;
             if constexpr (EPI == EPI_GELU) {
-                if (a.stamps) {
-                    HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_pp2_kernel<EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-                    gemm_pp2_kernel<EPI, true><<<tiles_m * tiles_n, 512, LDS_BYTES, s>>>(a, tiles_m, tiles_n);
-                    HIPTS_LAUNCH_CHECK();
-                    return HIPTS_OK;
+                HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_pp2_kernel<EPI, false>, gemm_pp2_kernel<EPI, true>));
+                if (p.stamped) {
+                    go(gemm_pp2_kernel<EPI, true>);
+                    break;
                 }
+            } else {
+                HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_pp2_kernel<EPI, false>));
             }
-            gemm_pp2_kernel<EPI><<<tiles_m * tiles_n, 512, LDS_BYTES, s>>>(a, tiles_m, tiles_n);
+            go(gemm_pp2_kernel<EPI, false>);
+            break;
         }
-        else if (variant == 1) {
-            // 256-, 224- or 192-row tiles, whichever needs fewer (size-weighted) rounds over the CUs
-            const int cus = cus_dev;
-            static const int min_mr = !getenv("HIPTS_GEMM_BM") ? 6 : strcmp(getenv("HIPTS_GEMM_BM"), "256") == 0 ? 8 : strcmp(getenv("HIPTS_GEMM_BM"), "224") == 0 ? 7 : 6;
-            auto tiles_of = [&](int mr) { return (a.M + 32 * mr - 1) / (32 * mr); };
-            auto cost_of = [&](int mr) { return ((long)tiles_of(mr) * tiles_n + cus - 1) / cus * (32 * mr); };
-            // measured (r01): the switch pays when the predicted saving is large (N = 768: 2.625 vs 3 rounds,
-            // -4..6 %) and costs 3 % when it is marginal (N = 3072: 9.6 vs 10) -- smaller tiles re-read W more.
-            // ... and only when the launch has the chip to itself: with sub-batches on several streams the
-            // partial last round is filled by the other stream's kernel and full tiles win (4.50 -> 4.59 k img/s).
-            // 192 rows (round 3, half operands only): EVA02-L at the reference's batch of 10 -- 10 250 rows x 1024 columns are 164
-            // tiles of 256 rows on 256 CUs (one round, 64 % of the chip) but 216 tiles of 192 rows (one round of 3/4 the length).
-            int mr = 8;
-            // ... unless the whole launch is smaller than the chip (late round 4): then there is no last round for the other stream to fill,
-            // and shorter tiles end the launch sooner (HIPTS_GEMM_MR_SHARED=0: as before, 1: by cost for every shared launch)
-            static const int mr_shared = getenv("HIPTS_GEMM_MR_SHARED") ? atoi(getenv("HIPTS_GEMM_MR_SHARED")) : -1;
-            if (!a.shared_chip || mr_shared == 1 || (mr_shared != 0 && (long)tiles_of(8) * tiles_n < cus)) {
-                long best = cost_of(8) * 93;
-                for (int c = 7; c >= (a.f16 ? min_mr : (min_mr > 7 ? min_mr : 7)); --c)
-                    if (cost_of(c) * 100 < best) {
-                        best = cost_of(c) * 100;
-                        mr = c;
-                    }
-            }
-            if (EPI == EPI_HEAD && a.sk_ws && getenv("HIPTS_GEMM_SPLITK_HEAD") && atoi(getenv("HIPTS_GEMM_SPLITK_HEAD")) >= 2) mr = 8;       // the split-K instantiation is built for 256-row tiles
-            const int tiles_mr = tiles_of(mr);
-            // persistent grid: one workgroup per CU (a multiple of 8 so that a workgroup's tiles keep their XCD)
-            static const bool persist = !(getenv("HIPTS_GEMM_PERSIST") && strcmp(getenv("HIPTS_GEMM_PERSIST"), "0") == 0);
-            const int ntile = tiles_mr * tiles_n;
-            const int slots = cus >= 8 ? cus / 8 * 8 : cus;
-            const int grid = (persist && ntile > slots) ? slots : ntile;
-            static const int raster = getenv("HIPTS_GEMM_RASTER") ? atoi(getenv("HIPTS_GEMM_RASTER")) : 8;      // measured: 8 +0.4..0.8 % on the ViT forward, 4 / 16 +-0
-            static const int raster_gn = getenv("HIPTS_GEMM_RASTER_GN") ? atoi(getenv("HIPTS_GEMM_RASTER_GN")) : 6;      // measured (r03): fc1 fetches 251 -> 207 MB, q|k|v 194 -> 167 MB per launch, images/s +-0; 0 = off
-            GemmArgs ar = a;
-            static const int epi_prio = getenv("HIPTS_EPI_PRIO") ? atoi(getenv("HIPTS_EPI_PRIO")) : 0;
-            ar.epi_prio = epi_prio;
-            static const int epi_prefetch = getenv("HIPTS_EPI_PREFETCH") ? atoi(getenv("HIPTS_EPI_PREFETCH")) : 0;
-            ar.epi_prefetch = epi_prefetch;
-            ar.raster_gm = (raster > 0 && tiles_n >= 8) ? raster : 0;
-            ar.raster_gn = (raster_gn > 0 && tiles_n >= 8 && tiles_n > raster_gn) ? raster_gn : 0;
-            {   // the 4-wave, one-wave-per-SIMD loop (gemm4.hip) where it is built: HIPTS_GEMM_Q4 = bit mask over epilogue numbers (A/B)
-                const unsigned q4_mask = gemm_q4_mask();
-                if (mr == 8 && ((q4_mask >> (int)EPI) & 1u)) {
-                    bool handled = false;
-                    const int st = launch_gemm_q4((GemmEpilogue)EPI, ar, s, &handled);
-                    if (handled) return st;
-                }
-            }
-            static const bool resid_general = getenv("HIPTS_RESID_GENERAL") && atoi(getenv("HIPTS_RESID_GENERAL")) != 0;      // A/B: the predicated residual epilogue on interior tiles too
-            // Split-K tail (GemmArgs::sk_*), an EXPERIMENT that lost (round 4) and stays off: the residual GEMMs with a long K whose last round
-            // fills less than half of the chip -- EVA02-L's proj / fc2 at the reference's batch of 10 (84 tiles per sub-batch on 256 CUs), the
-            // ViT's fc2 per 32-image sub-batch (294 tiles: 38 in the second round) -- with S <= HIPTS_GEMM_SPLITK slices of at least
-            // HIPTS_GEMM_SPLITK_MINKT K-tiles.  Measured (tools/gpurun/r4_splitk.sh, one box): ViT-B/16 5093-5103 -> 4894-4898 images/s
-            // (S = 4; S = 2: 4982), EVA02-L batch 10 1044 -> 829-832 images/s (S = 3), batch 32 unchanged.  A 256 x 256 fp32 slab is 256 KB:
-            // 84 tiles x 3 slices write 64 MB through to memory and their last arrivers read it back, ~50 us per launch, more than the
-            // under-filled main loop costs (cdna_hip_programming.md says as much: combine in-launch only when the slabs of a tile are tens of
-            // KB).  It also gives up batch invariance -- a tile summed as S partial chains has other low bits than the same tile summed as one
-            // chain, and WHICH tiles are split depends on the launch's size (tests/test_gpu_vit.py::test_folded_layernorm_path..., the sharded
-            // CLIs' byte-equal output files) -- though run to run it is deterministic (slabs are added in slice order).  The tag head's launch
-            // (EPI_HEAD: one row panel of 43 column tiles whatever the batch) would keep the invariance; HIPTS_GEMM_SPLITK_HEAD=4 enables it.
+        default: {      // HIPTSDBG_GEMM_PP
             if constexpr (EPI == EPI_RESID || EPI == EPI_RESID_XG || EPI == EPI_RESID_XGI || EPI == EPI_RESID_ROWSTAT || EPI == EPI_HEAD) {
-                static const int sk_env = getenv("HIPTS_GEMM_SPLITK") ? atoi(getenv("HIPTS_GEMM_SPLITK")) : 0;
-                static const int sk_head = getenv("HIPTS_GEMM_SPLITK_HEAD") ? atoi(getenv("HIPTS_GEMM_SPLITK_HEAD")) : 0;
-                const int sk_max = EPI == EPI_HEAD ? (tiles_mr == 1 ? sk_head : 0) : sk_env;
-                static const int sk_minkt = getenv("HIPTS_GEMM_SPLITK_MINKT") ? atoi(getenv("HIPTS_GEMM_SPLITK_MINKT")) : 5;
-                const int nkt = a.K / BK;
-                const int rem = ntile % slots;      // tiles of the partial last round (the whole launch when it is smaller than the chip)
-                if (a.sk_ws && mr == 8 && sk_max >= 2 && rem > 0 && rem * 2 <= slots && rem <= 1024) {
-                    int sl = std::min(sk_max, std::min(slots / rem, nkt / (sk_minkt > 0 ? sk_minkt : 1)));
-                    while (sl >= 2 && 4096 + (size_t)rem * sl * ((size_t)BM * BN * 4) > a.sk_ws_bytes) --sl;
-                    if (sl >= 2) {
-                        static PerDevice attr_sk;
-                        {
-                            std::lock_guard<std::mutex> lk(attr_sk.mu);
-                            if (!attr_sk.done(dev)) {
-                                HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, 8, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-                                HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, 8, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-                                attr_sk.mark(dev);
-                            }
-                        }
-                        ar.sk_first = ntile - rem;
-                        ar.sk_slices = sl;
-                        const int items = ar.sk_first + rem * sl;
-                        const int grid_sk = (persist && items > slots) ? slots : items;
-                        if (a.f16) gemm_pp_kernel<EPI, 8, true, false, true><<<grid_sk, 512, LDS_BYTES, s>>>(ar, tiles_m, tiles_n);
-                        else gemm_pp_kernel<EPI, 8, false, false, true><<<grid_sk, 512, LDS_BYTES, s>>>(ar, tiles_m, tiles_n);
-                        HIPTS_LAUNCH_CHECK();
-                        return HIPTS_OK;
-                    }
+                if (p.sk_slices >= 2) {     // the split-K tail
+                    static PerDevice once;
+                    HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_pp_kernel<EPI, 8, false, false, true>, gemm_pp_kernel<EPI, 8, true, false, true>));
+                    if (f16) go(gemm_pp_kernel<EPI, 8, true, false, true>);
+                    else go(gemm_pp_kernel<EPI, 8, false, false, true>);
+                    break;
                 }
             }
             if constexpr (EPI == EPI_RESID_XG) {
-                // every tile inside the matrix: the instantiation without per-lane predication (HIPTS_RESID_GENERAL=1: the general one, A/B).
-                // (Not instantiated for RESID_XGI: its only user, EVA02, has 1025 tokens per image -- no launch of whole tiles -- and with the
-                // input fold's extra column vector the interior form compiled to 60 spilled registers.)
-                if (mr == 8 && a.M % 256 == 0 && a.N % 256 == 0 && a.N <= 1024 && !a.pos && !a.res_scale && a.out_bf16 && a.stat_part && !resid_general) {
-                    static PerDevice attr_int;
-                    {
-                        std::lock_guard<std::mutex> lk(attr_int.mu);
-                        if (!attr_int.done(dev)) {
-                            HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, 8, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-                            HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, 8, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-                            attr_int.mark(dev);
-                        }
-                    }
-                    if (a.f16) gemm_pp_kernel<EPI, 8, true, false, false, true><<<grid, 512, LDS_BYTES, s>>>(ar, tiles_m, tiles_n);
-                    else gemm_pp_kernel<EPI, 8, false, false, false, true><<<grid, 512, LDS_BYTES, s>>>(ar, tiles_m, tiles_n);
-                    HIPTS_LAUNCH_CHECK();
-                    return HIPTS_OK;
+                if (p.interior) {
+                    static PerDevice once;
+                    HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_pp_kernel<EPI, 8, false, false, false, true>, gemm_pp_kernel<EPI, 8, true, false, false, true>));
+                    if (f16) go(gemm_pp_kernel<EPI, 8, true, false, false, true>);
+                    else go(gemm_pp_kernel<EPI, 8, false, false, false, true>);
+                    break;
                 }
             }
-            if (a.f16) {
-                if (mr == 6) gemm_pp_kernel<EPI, 6, true><<<grid, 512, LDS_BYTES, s>>>(ar, tiles_mr, tiles_n);
-                else if (mr == 7) gemm_pp_kernel<EPI, 7, true><<<grid, 512, LDS_BYTES, s>>>(ar, tiles_mr, tiles_n);
-                else gemm_pp_kernel<EPI, 8, true><<<grid, 512, LDS_BYTES, s>>>(ar, tiles_m, tiles_n);
-            } else {
-                if (mr == 7) gemm_pp_kernel<EPI, 7, false><<<grid, 512, LDS_BYTES, s>>>(ar, tiles_mr, tiles_n);
-                else gemm_pp_kernel<EPI, 8, false><<<grid, 512, LDS_BYTES, s>>>(ar, tiles_m, tiles_n);
-            }
+            static PerDevice once;
+            HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_pp_kernel<EPI, 8, false>, gemm_pp_kernel<EPI, 7, false>, gemm_pp_kernel<EPI, 8, true>,
+                                        gemm_pp_kernel<EPI, 7, true>, gemm_pp_kernel<EPI, 6, true>));
+            if (f16 && p.mr == 6) go(gemm_pp_kernel<EPI, 6, true>);
+            else if (f16 && p.mr == 7) go(gemm_pp_kernel<EPI, 7, true>);
+            else if (f16) go(gemm_pp_kernel<EPI, 8, true>);
+            else if (p.mr == 7) go(gemm_pp_kernel<EPI, 7, false>);
+            else go(gemm_pp_kernel<EPI, 8, false>);
         }
-        else
-            gemm_kernel<EPI><<<tiles_m * tiles_n, 512, LDS_BYTES, s>>>(a, tiles_m, tiles_n);
     }
     HIPTS_LAUNCH_CHECK();
     return HIPTS_OK;
 }
 
 }  // namespace
+
+const GemmKnobs& gemm_knobs() {
+    static const GemmKnobs knobs = [] {
+        auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+        GemmKnobs k;
+        const char* e = getenv("HIPTS_GEMM");
+        k.variant_set = e != nullptr;
+        k.variant = (e && strcmp(e, "v1") == 0) ? HIPTSDBG_GEMM_V1 : (e && strcmp(e, "pp2") == 0) ? HIPTSDBG_GEMM_PP2 : (e && strcmp(e, "s3") == 0) ? HIPTSDBG_GEMM_S3
+                    : (e && strcmp(e, "dw") == 0) ? HIPTSDBG_GEMM_DW : HIPTSDBG_GEMM_PP;
+        k.auto_dw = num("HIPTS_GEMM_AUTO_DW", 1) != 0;
+        k.dw_limit4 = num("HIPTS_GEMM_DW_LIMIT", 2);
+        k.dw_mask = getenv("HIPTS_GEMM_DW_MASK") ? (unsigned)strtoul(getenv("HIPTS_GEMM_DW_MASK"), nullptr, 0) : 0u;
+        e = getenv("HIPTS_GEMM_BM");
+        k.min_mr = !e ? 6 : strcmp(e, "256") == 0 ? 8 : strcmp(e, "224") == 0 ? 7 : 6;
+        k.mr_shared = num("HIPTS_GEMM_MR_SHARED", -1);
+        e = getenv("HIPTS_GEMM_PERSIST");
+        k.persist = !(e && strcmp(e, "0") == 0);
+        k.raster = num("HIPTS_GEMM_RASTER", 8);
+        k.raster_gn = num("HIPTS_GEMM_RASTER_GN", 6);
+        k.epi_prio = num("HIPTS_EPI_PRIO", 0);
+        k.epi_prefetch = num("HIPTS_EPI_PREFETCH", 0);
+        k.resid_general = num("HIPTS_RESID_GENERAL", 0) != 0;
+        k.splitk = num("HIPTS_GEMM_SPLITK", 0);
+        k.splitk_head = num("HIPTS_GEMM_SPLITK_HEAD", 0);
+        k.splitk_minkt = num("HIPTS_GEMM_SPLITK_MINKT", 5);
+        return k;
+    }();
+    return knobs;
+}
 
 int launch_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
     if (a.op8) HIPTS_REQUIRE(a.K % 128 == 0 && a.K >= 128, "gemm: K=%d must be a positive multiple of 128 with e4m3 operands", a.K);
@@ -1384,4 +1284,25 @@ extern "C" int hiptsdbg_gelu(const float* x_host, int n, int tanh_form, float* y
     HIPTS_LAUNCH_CHECK();
     HIPTS_HIP(hipMemcpy(y_host, y.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return HIPTS_OK;
+}
+
+// Development/test aid (not part of the public ABI), host only: the launcher's plan for a launch described by numbers
+// (include/hip_tagsearch_debug.h); the pointers the rules only test for presence point at a dummy.
+extern "C" int hiptsdbg_gemm_plan(int epi, int M, int N, int K, int f16, int shared_chip, unsigned features, int ld_out, int dim, int cus,
+                                  unsigned q4_mask, hiptsdbg_gemm_plan_t* out) {
+    using namespace hipts;
+    HIPTS_REQUIRE(out && epi >= EPI_PATCH && epi <= EPI_RESID_LS && M >= 1 && N >= 1 && K >= 64 && K % 64 == 0 && cus >= 1, "hiptsdbg_gemm_plan: bad argument");
+    static float dummy[2];
+    GemmArgs g{};
+    g.M = M; g.N = N; g.K = K; g.f16 = f16; g.shared_chip = shared_chip; g.ld_out = ld_out; g.dim = dim;
+    if (features & 1) g.stat_part = dummy;
+    if (features & 2) { g.sk_ws = dummy; g.sk_ws_bytes = GEMM_SK_WS_BYTES; }
+    if (features & 4) g.pos = dummy;
+    if (features & 8) g.res_scale = dummy;
+    if (features & 16) { g.out_bf16 = reinterpret_cast<bf16_t*>(dummy); g.ln_gamma = dummy; }
+    if (features & 32) g.stat_in = dummy;
+    if (features & 64) g.op8 = 1;
+    if (features & 128) g.stamps = reinterpret_cast<unsigned long long*>(dummy);
+    *out = gemm_plan((GemmEpilogue)epi, g, cus, gemm_knobs(), q4_mask);
+    return gemm_plan_status(*out, (GemmEpilogue)epi);
 }

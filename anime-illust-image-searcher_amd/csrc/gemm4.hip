@@ -17,11 +17,12 @@
 //   * After the loop a wave hands its accumulators to the epilogues of gemm_epi.h as two 128 x 64 wave-parts (virtual wave_n = 2 wn + h).
 //
 // Built for the launches whose tiles all lie inside the matrix (M, N multiples of 256) with an even number of K-tiles: every GEMM of the
-// ViT-B/16 forward but the tag head.  Everything else stays on gemm_pp_kernel (launch_gemm_q4 says "not handled").
+// ViT-B/16 forward but the tag head.  Everything else stays on gemm_pp_kernel (gemm_plan.h lists the conditions).
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
+#include "gemm_plan.h"
 #include "vit_internal.h"
 
 namespace hipts {
@@ -388,27 +389,19 @@ __global__ __launch_bounds__(256, 1) void gemm_q4_kernel(const GemmArgs a, int t
 }
 
 template <int EPI, bool F16, bool INT>
-int launch_q4_t(const GemmArgs& a, hipStream_t s, int tiles_m, int tiles_n, int cus, int dev) {
-    static PerDevice attr;
-    {
-        std::lock_guard<std::mutex> lk(attr.mu);
-        if (!attr.done(dev)) {
-            HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_q4_kernel<EPI, F16, INT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-            if constexpr (F16 && (EPI == EPI_GELU || INT))
-                HIPTS_HIP(hipFuncSetAttribute((const void*)gemm_q4_kernel<EPI, F16, INT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-            attr.mark(dev);
-        }
-    }
-    const int ntile = tiles_m * tiles_n;
-    const int slots = cus >= 8 ? cus / 8 * 8 : cus;
+int launch_q4_t(const GemmArgs& a, const GemmPlan& p, int dev, hipStream_t s) {
+    static PerDevice once;
     if constexpr (F16 && (EPI == EPI_GELU || INT)) {
-        if (a.stamps) {      // measurement build: in-kernel cycle stamps of workgroup 8 (tools/gemm_bench.py)
-            gemm_q4_kernel<EPI, F16, INT, true><<<ntile > slots ? slots : ntile, 256, LDS_BYTES, s>>>(a, tiles_m, tiles_n);
+        HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_q4_kernel<EPI, F16, INT>, gemm_q4_kernel<EPI, F16, INT, true>));
+        if (p.stamped) {      // measurement build: in-kernel cycle stamps of workgroup 8 (tools/gemm_bench.py)
+            gemm_q4_kernel<EPI, F16, INT, true><<<p.grid, p.block, p.lds_bytes, s>>>(a, p.tiles_m, p.tiles_n);
             HIPTS_LAUNCH_CHECK();
             return HIPTS_OK;
         }
+    } else {
+        HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_q4_kernel<EPI, F16, INT>));
     }
-    gemm_q4_kernel<EPI, F16, INT><<<ntile > slots ? slots : ntile, 256, LDS_BYTES, s>>>(a, tiles_m, tiles_n);
+    gemm_q4_kernel<EPI, F16, INT><<<p.grid, p.block, p.lds_bytes, s>>>(a, p.tiles_m, p.tiles_n);
     HIPTS_LAUNCH_CHECK();
     return HIPTS_OK;
 }
@@ -418,40 +411,19 @@ int launch_q4_t(const GemmArgs& a, hipStream_t s, int tiles_m, int tiles_n, int 
 static std::atomic<long long> g_q4_launches{0};
 long long gemm_q4_launch_count() { return g_q4_launches.load(std::memory_order_relaxed); }
 
-// The 4-wave loop for the launches it is built for; *handled = false leaves the launch to gemm_pp_kernel.  `a` carries the launcher's
-// raster fields.
-int launch_gemm_q4(GemmEpilogue epi, const GemmArgs& a, hipStream_t s, bool* handled) {
-    *handled = false;
-    if (a.op8 || a.sk_slices > 1) return HIPTS_OK;
-    if (a.stamps && !(a.f16 && (epi == EPI_GELU || epi == EPI_RESID_XG))) return HIPTS_OK;
-    if (a.M % BM || a.N % BN || a.K % (2 * BK) || a.K < 2 * BK) return HIPTS_OK;
-    if (epi != EPI_GELU && epi != EPI_QK && epi != EPI_RESID_XG) return HIPTS_OK;
-    const int ld = a.ld_out ? a.ld_out : a.N;
-    if (epi == EPI_GELU && ld % 8) return HIPTS_OK;
-    if (epi == EPI_QK && a.dim % 64) return HIPTS_OK;
-    // per-lane source offsets are 32-bit: 256 rows of a tile
-    if ((size_t)256 * a.K * 2 >= ((size_t)1 << 31)) return HIPTS_OK;
-    int dev = 0;
-    const int cus = current_device_cus(&dev);
-    const int tiles_m = a.M / BM, tiles_n = a.N / BN;
-    *handled = true;
+// Launches what gemm_plan() decided (loop == HIPTSDBG_GEMM_Q4: it lists the launches this file is built for).  `a` carries the
+// launcher-set fields.
+int launch_gemm_q4(GemmEpilogue epi, const GemmArgs& a, const GemmPlan& p, int dev, hipStream_t s) {
     g_q4_launches.fetch_add(1, std::memory_order_relaxed);
     const bool f16 = a.f16 != 0;
     switch (epi) {
-        case EPI_GELU:
-            return f16 ? launch_q4_t<EPI_GELU, true, false>(a, s, tiles_m, tiles_n, cus, dev) : launch_q4_t<EPI_GELU, false, false>(a, s, tiles_m, tiles_n, cus, dev);
-        case EPI_QK:
-            return f16 ? launch_q4_t<EPI_QK, true, false>(a, s, tiles_m, tiles_n, cus, dev) : launch_q4_t<EPI_QK, false, false>(a, s, tiles_m, tiles_n, cus, dev);
-        case EPI_RESID_XG: {
-            const bool interior = a.N <= 1024 && !a.pos && !a.res_scale && a.out_bf16 && a.stat_part && !a.rowstat && !a.stat_in;
-            if (interior)
-                return f16 ? launch_q4_t<EPI_RESID_XG, true, true>(a, s, tiles_m, tiles_n, cus, dev) : launch_q4_t<EPI_RESID_XG, false, true>(a, s, tiles_m, tiles_n, cus, dev);
-            return f16 ? launch_q4_t<EPI_RESID_XG, true, false>(a, s, tiles_m, tiles_n, cus, dev) : launch_q4_t<EPI_RESID_XG, false, false>(a, s, tiles_m, tiles_n, cus, dev);
-        }
-        default: break;
+        case EPI_GELU: return f16 ? launch_q4_t<EPI_GELU, true, false>(a, p, dev, s) : launch_q4_t<EPI_GELU, false, false>(a, p, dev, s);
+        case EPI_QK: return f16 ? launch_q4_t<EPI_QK, true, false>(a, p, dev, s) : launch_q4_t<EPI_QK, false, false>(a, p, dev, s);
+        case EPI_RESID_XG:
+            if (p.interior) return f16 ? launch_q4_t<EPI_RESID_XG, true, true>(a, p, dev, s) : launch_q4_t<EPI_RESID_XG, false, true>(a, p, dev, s);
+            return f16 ? launch_q4_t<EPI_RESID_XG, true, false>(a, p, dev, s) : launch_q4_t<EPI_RESID_XG, false, false>(a, p, dev, s);
+        default: return set_error(HIPTS_ERR_INVALID, "gemm: the 4-wave loop is not built for epilogue %d", (int)epi);
     }
-    *handled = false;
-    return HIPTS_OK;
 }
 
 }  // namespace hipts

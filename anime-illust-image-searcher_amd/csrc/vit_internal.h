@@ -282,8 +282,7 @@ struct GemmArgs {
 
 int launch_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s);
 // gemm4.hip: the 4-wave (one wave per SIMD) main loop for launches of whole 256 x 256 tiles with an even number of K-tiles and the
-// GELU / QK / RESID_XG epilogues; *handled = false: not built for this launch, the caller goes on to gemm_pp_kernel
-int launch_gemm_q4(GemmEpilogue epi, const GemmArgs& a, hipStream_t s, bool* handled);
+// GELU / QK / RESID_XG epilogues (launch_gemm_q4, declared in gemm_plan.h, launches what gemm_plan() decided)
 constexpr unsigned GEMM_Q4_DEFAULT_MASK = 0u;      // epilogues whose eligible launches take gemm4.hip by default (HIPTS_GEMM_Q4 overrides)
 void set_gemm_q4_mask(unsigned mask);
 long long gemm_q4_launch_count();              // launches gemm4.hip has taken so far (tests: the comparison really compared)

@@ -62,6 +62,27 @@ int hiptsdbg_mlp_stamps(unsigned long long* host, int n);
  * lane L < 24 holds (Z[2L], Z[2L+1]), lane 32 + L holds (Z[2L+1], Z[2L+2]), the other lanes zero. */
 int hiptsdbg_mlp_weight_image(const float* w1, const float* w2, int C, uint16_t* out, long long out_halves);
 int hiptsdbg_dw_toeplitz(const float* w, int channels, uint32_t* out);
+/* How the GEMM launcher would run a launch (csrc/gemm_plan.h: gemm_plan() is the one place the launch policy lives and the launcher
+ * consumes exactly this).  Host only, no GPU call.  loop: the main loop; mr: rows of a tile / 32 (8 / 7 / 6); interior: the residual
+ * instantiation without per-lane predication; stamped: the instantiation with in-kernel cycle stamps; tiles_m x tiles_n tiles on
+ * `grid` workgroups of `block` threads with lds_bytes of dynamic LDS; tiles from sk_first on are cut into sk_slices K ranges
+ * (1: no split); the raster_* / epi_* fields as the kernel receives them. */
+enum { HIPTSDBG_GEMM_V1 = 0, HIPTSDBG_GEMM_PP = 1, HIPTSDBG_GEMM_S3 = 2, HIPTSDBG_GEMM_PP2 = 3, HIPTSDBG_GEMM_DW = 4,
+       HIPTSDBG_GEMM_Q4 = 5, HIPTSDBG_GEMM_PP_E4M3 = 6 };
+typedef struct hiptsdbg_gemm_plan_t {
+    int32_t loop, mr, interior, stamped;
+    int32_t tiles_m, tiles_n, grid, block, lds_bytes;
+    int32_t sk_first, sk_slices;
+    int32_t raster_gm, raster_gn, epi_prio, epi_prefetch;
+    int32_t error;      /* 0, or why the launch is refused: 1 half operands outside the pp / dw loops, 2 e4m3 operands not built for the epilogue */
+} hiptsdbg_gemm_plan_t;
+/* The plan of the launch [M,K] x [N,K]^T with epilogue `epi` (GemmEpilogue) on a device of `cus` compute units, under this process's
+ * HIPTS_GEMM* / HIPTS_EPI_* / HIPTS_RESID_GENERAL environment (read once) and the 4-wave mask q4_mask.  f16 / shared_chip / ld_out / dim
+ * as GemmArgs; `features`: which optional arguments are present -- 1 stat_part, 2 sk_ws (the standard workspace size), 4 pos,
+ * 8 res_scale, 16 the 16-bit copy (out_bf16 with ln_gamma), 32 stat_in (a folded input), 64 op8, 128 stamps.  A launch the launcher
+ * refuses returns its error (and out->error). */
+int hiptsdbg_gemm_plan(int epi, int M, int N, int K, int f16, int shared_chip, unsigned features, int ld_out, int dim, int cus,
+                       unsigned q4_mask, hiptsdbg_gemm_plan_t* out);
 /* out_host float32 [M][N] = A W^T for bf16 bit patterns a_bf16 [M][K], w_bf16 [N][K] (plain epilogue). */
 int hiptsdbg_gemm_run(int M, int N, int K, const uint16_t* a_bf16, const uint16_t* w_bf16, float* out_host);
 /* The e4m3 operand path: a_f32 / w_f32 are quantised by the library (per-tensor power-of-two weight scale returned in

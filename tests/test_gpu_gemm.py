@@ -52,8 +52,9 @@ def test_gemm_variants_match_float64(variant):
 
 def test_gemm_default_dispatch_persistent_and_underfilled():
     """No HIPTS_GEMM: the dispatch the product uses.  (70000, 768, 128) is 822 tiles on 256 persistent
-    workgroups (several tiles per workgroup, next-tile prefetch); (11520, 512, 512) has 90 tiles < CUs and
-    goes to the two-per-CU kernel; (300, 272, 128) stays a plain one-tile-per-workgroup launch."""
+    workgroups (several tiles per workgroup, next-tile prefetch); (11520, 512, 512) has 90 tiles, at most half the CUs,
+    and goes to the two-per-CU kernel, and so does (300, 272, 128) with its 6 tiles (tests/test_gemm_plan_host.py holds
+    the launcher to the path named for each shape)."""
     env = {k: v for k, v in os.environ.items() if k != "HIPTS_GEMM"}
     code = _CHILD % {"pkg": os.path.join(ROOT, "anime-illust-image-searcher_amd"),
                      "shapes": [(70000, 768, 128), (11520, 512, 512), (300, 272, 128), (50000, 208, 64),
@@ -66,11 +67,14 @@ def test_gemm_default_dispatch_persistent_and_underfilled():
 def test_gemm_half_operands_and_tile_heights():
     """IEEE-half operands (the product default) through the persistent loop at each tile height the launcher picks:
     (10250, 1024, 1024) = EVA02-L's proj at the reference batch of 10 -> 192-row tiles (216 tiles, one round);
-    (50176, 768, 768) -> 224 rows; (66000, 1024, 320) -> 256 rows; (1025, 1024, 1024) one ragged round of 192."""
+    (50176, 768, 768) and (66000, 1024, 320) -> 224 rows; (32768, 512, 128) -> 256 rows, the general instantiation; (1025, 1024, 1024)
+    is 20 tiles of 256 x 256, few enough for the two-per-CU kernel with half operands (tests/test_gemm_plan_host.py holds the launcher
+    to these)."""
     env = {k: v for k, v in os.environ.items() if k != "HIPTS_GEMM"}
     env["HIPTS_DBG_GEMM_F16"] = "1"
     code = _CHILD % {"pkg": os.path.join(ROOT, "anime-illust-image-searcher_amd"),
-                     "shapes": [(10250, 1024, 1024), (50176, 768, 768), (66000, 1024, 320), (1025, 1024, 1024), (10250, 1024, 2752)]}
+                     "shapes": [(10250, 1024, 1024), (50176, 768, 768), (66000, 1024, 320), (1025, 1024, 1024), (10250, 1024, 2752),
+                                (32768, 512, 128)]}
     code = code.replace("a = synth.round_to_bf16(rng.standard_normal((M, K)).astype(np.float32))",
                         "a = rng.standard_normal((M, K)).astype(np.float16).astype(np.float32)")
     code = code.replace("w = synth.round_to_bf16((rng.standard_normal((N, K)) * 0.05).astype(np.float32))",
