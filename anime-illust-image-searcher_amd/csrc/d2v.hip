@@ -16,6 +16,7 @@
 // HBM or MFMA.
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -108,77 +109,163 @@ __device__ __forceinline__ uint32_t bisect_left_wave(const uint32_t* __restrict_
     return lo;
 }
 
+// ---------------------------------------------------------------------------------------------
+// What every kernel below must compute alike, bit for bit with oracle/csrc/oracle.c, stated once.
+// ---------------------------------------------------------------------------------------------
+// Kernel arguments of the three walking kernels (the planned kernel keeps plain parameters, see there).  Pointers inside a struct are
+// not __restrict__: the helpers below take the rows they touch as __restrict__ parameters.
+struct Model {
+    float* syn;                     // syn1neg [V][dim]; the planned kernel is handed the lane-major copy; only training writes it
+    const uint32_t* cum_table;
+    const uint32_t* sample_int;     // nullptr: no sub-sampling
+    const float* exp_table;         // EXP_TABLE_SIZE floats, copied to LDS by every workgroup
+    int64_t V;
+    int dim, negative;
+    double exp_scale;
+};
+struct Docs {                       // inference: CSR of word ids, start vector and seed per document, the result
+    const int64_t* doc_ptr;
+    const int32_t* words;
+    int64_t ndocs;
+    const float* v0;
+    const uint64_t* seeds;
+    float* out;
+};
+struct Schedule {
+    int epochs;
+    float alpha0, min_alpha;
+};
+
+// word2vec_inner.pyx's 48-bit LCG.  A draw is the state's upper 32 bits; every draw advances the state once.
+__device__ __forceinline__ void lcg_next(uint64_t& state) { state = (state * 25214903917ULL + 11) & LCG_MOD; }
+__device__ __forceinline__ uint64_t lcg_draw(uint64_t& state) {
+    const uint64_t r = state >> 16;
+    lcg_next(state);
+    return r;
+}
+// the state a document starts epoch (or training pass) k with, wave-uniform
+__device__ __forceinline__ uint64_t epoch_lcg(uint64_t seed, uint64_t k) { return uniform64(splitmix64(seed + k) & LCG_MOD); }
+
+// infer_vector's alpha: alpha0 in the first epoch, then one double subtraction of (alpha0 - min_alpha) / max(epochs - 1, 1) per epoch
+struct InferAlpha {
+    double alpha, delta;
+    __device__ explicit InferAlpha(const Schedule& s)
+        : alpha((double)s.alpha0), delta(((double)s.alpha0 - (double)s.min_alpha) / (double)(s.epochs - 1 > 1 ? s.epochs - 1 : 1)) {}
+    __device__ float next() {
+        const float a = (float)alpha;
+        alpha -= delta;
+        return a;
+    }
+};
+
+// Sub-sampling: one draw per in-vocabulary word, the word stays unless its threshold is below the draw.  Callers guard with
+// `sample_int != nullptr`: without sub-sampling nothing is drawn.
+__device__ __forceinline__ bool subsample_keeps(uint32_t threshold, uint64_t& state) { return !((uint64_t)threshold < lcg_draw(state)); }
+
+// A vector in registers: the lane owns elements lane, lane + 64, ... of a row of `dim` floats, zero past the end.  (One address per
+// row, `row + lane`, and constant offsets from it.)
 template <int EPL>
-__global__ __launch_bounds__(256) void d2v_infer_kernel(const float* __restrict__ syn1neg, const uint32_t* __restrict__ cum_table,
-                                                        const uint32_t* __restrict__ sample_int, int64_t V, int dim,
-                                                        const int64_t* __restrict__ doc_ptr, const int32_t* __restrict__ words,
-                                                        int64_t ndocs, const float* __restrict__ v0,
-                                                        const uint64_t* __restrict__ seeds, int epochs, float alpha0,
-                                                        float min_alpha, int negative, double exp_scale,
-                                                        const float* __restrict__ exp_table_g, float* __restrict__ out) {
+__device__ __forceinline__ void load_vec(float (&x)[EPL], const float* __restrict__ row, int dim, int lane) {
+    row += lane;
+#pragma unroll
+    for (int c = 0; c < EPL; ++c) x[c] = (lane + 64 * c < dim) ? row[64 * c] : 0.0f;
+}
+template <int EPL>
+__device__ __forceinline__ void store_vec(float* __restrict__ row, const float (&x)[EPL], int dim, int lane) {
+    row += lane;
+#pragma unroll
+    for (int c = 0; c < EPL; ++c)
+        if (lane + 64 * c < dim) row[64 * c] = x[c];
+}
+template <int EPL>
+__device__ __forceinline__ void atomic_add_vec(float* __restrict__ row, const float (&x)[EPL], int dim, int lane) {
+    row += lane;
+#pragma unroll
+    for (int c = 0; c < EPL; ++c)
+        if (lane + 64 * c < dim) unsafeAtomicAdd(&row[64 * c], x[c]);
+}
+
+// (the caller's __syncthreads() follows; `threads` is the workgroup size, a constant wherever the launch fixes it)
+__device__ __forceinline__ void load_exp_table(float* lds, const float* __restrict__ table, int threads) {
+    for (int i = threadIdx.x; i < EXP_TABLE_SIZE; i += threads) lds[i] = table[i];
+}
+
+// g = (label - sigmoid(f)) * a through EXP_TABLE; false (and no step) outside (-MAX_EXP, MAX_EXP).  The index is word2vec_inner.pyx's:
+// float add, widened to double, times exp_scale, truncated.  (The planned kernel takes the window test and the index apart: it looks
+// the whole group of a word up before it branches.)
+__device__ __forceinline__ bool sigmoid_in_window(float f) { return !(f <= -(float)MAX_EXP || f >= (float)MAX_EXP); }
+__device__ __forceinline__ int sigmoid_index(float f, double exp_scale) { return (int)((double)(f + (float)MAX_EXP) * exp_scale); }
+__device__ __forceinline__ bool sigmoid_grad(float f, float label, float a, const float* exp_table, double exp_scale, float& g) {
+    if (!sigmoid_in_window(f)) return false;
+    g = (label - exp_table[sigmoid_index(f, exp_scale)]) * a;
+    return true;
+}
+
+// The (1 + negative) targets of one word w against the input vector `in` (the document vector; PV-DM: the context mean / sum): the word
+// itself with label 1, then `negative` draws from cum_table with label 0.  The draw order is the oracle's contract: one draw per negative
+// sample, advanced BEFORE the sample that hit the word itself is skipped.  work = sum of g * syn1neg[target] in target order.
+// Hidden: what happens to syn1neg[target] -- nothing (inference), += g * in by a plain store (sequential training; the row was just read,
+// so it is fmaf(g, in, row)) or by float atomics (parallel training: concurrent documents lose no update).
+enum class Hidden { none, store, atomic };
+
+template <int EPL, Hidden H>
+__device__ __forceinline__ void ns_word_step(const float (&in)[EPL], int32_t w, uint64_t& state, const Model& m, uint32_t cum_last, float a,
+                                             const float* exp_table, int lane, float (&work)[EPL]) {
+    float rw[EPL];
+#pragma unroll
+    for (int c = 0; c < EPL; ++c) work[c] = 0.0f;
+    for (int d = 0; d < m.negative + 1; ++d) {
+        uint32_t target = (uint32_t)w;
+        if (d > 0) {
+            const uint32_t x = (uint32_t)lcg_draw(state) % cum_last;
+            target = __builtin_amdgcn_readfirstlane(bisect_left_wave(m.cum_table, x, (uint32_t)m.V, lane));
+            if (target == (uint32_t)w) continue;
+        }
+        float* row = m.syn + (int64_t)target * m.dim;
+        load_vec<EPL>(rw, row, m.dim, lane);
+        float p = 0.0f;
+#pragma unroll
+        for (int c = 0; c < EPL; ++c) p = fmaf(in[c], rw[c], p);
+        float g;
+        if (!sigmoid_grad(wave_sum_butterfly(p), d == 0 ? 1.0f : 0.0f, a, exp_table, m.exp_scale, g)) continue;
+#pragma unroll
+        for (int c = 0; c < EPL; ++c) {
+            work[c] = fmaf(g, rw[c], work[c]);
+            if (H == Hidden::store) rw[c] = fmaf(g, in[c], rw[c]);
+            if (H == Hidden::atomic) rw[c] = g * in[c];
+        }
+        if (H == Hidden::store) store_vec<EPL>(row, rw, m.dim, lane);
+        if (H == Hidden::atomic) atomic_add_vec<EPL>(row, rw, m.dim, lane);
+    }
+}
+
+template <int EPL>
+__global__ __launch_bounds__(256) void d2v_infer_kernel(Model m, Docs docs, Schedule sched) {
     __shared__ float exp_table[EXP_TABLE_SIZE];
-    for (int i = threadIdx.x; i < EXP_TABLE_SIZE; i += 256) exp_table[i] = exp_table_g[i];
+    load_exp_table(exp_table, m.exp_table, 256);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int64_t doc = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (doc >= ndocs) return;                       // whole wave exits together
-    float v[EPL], work[EPL], rw[EPL];
-#pragma unroll
-    for (int c = 0; c < EPL; ++c) v[c] = (lane + 64 * c < dim) ? v0[doc * dim + lane + 64 * c] : 0.0f;
-    const int64_t wb = doc_ptr[doc], we = doc_ptr[doc + 1];
-    const uint64_t seed = seeds[doc];
-    const uint32_t cum_last = cum_table[V - 1];
-    double alpha = (double)alpha0;
-    const double alpha_delta = ((double)alpha0 - (double)min_alpha) / (double)(epochs - 1 > 1 ? epochs - 1 : 1);
-    for (int e = 0; e < epochs; ++e) {
-        uint64_t next_random = uniform64(splitmix64(seed + (uint64_t)e) & LCG_MOD);
-        const float a = (float)alpha;
+    if (doc >= docs.ndocs) return;                  // whole wave exits together
+    float v[EPL], work[EPL];
+    load_vec<EPL>(v, docs.v0 + doc * m.dim, m.dim, lane);
+    const int64_t wb = docs.doc_ptr[doc], we = docs.doc_ptr[doc + 1];
+    const uint64_t seed = docs.seeds[doc];
+    const uint32_t cum_last = m.cum_table[m.V - 1];
+    InferAlpha alpha(sched);
+    for (int e = 0; e < sched.epochs; ++e) {
+        uint64_t next_random = epoch_lcg(seed, (uint64_t)e);
+        const float a = alpha.next();
         for (int64_t i = wb; i < we; ++i) {
-            const int32_t w = __builtin_amdgcn_readfirstlane(words[i]);
-            if (w < 0 || w >= V) continue;
-            if (sample_int) {
-                const uint64_t r = next_random >> 16;
-                next_random = (next_random * 25214903917ULL + 11) & LCG_MOD;
-                if ((uint64_t)sample_int[w] < r) continue;
-            }
-#pragma unroll
-            for (int c = 0; c < EPL; ++c) work[c] = 0.0f;
-            for (int d = 0; d < negative + 1; ++d) {
-                uint32_t target;
-                float label;
-                if (d == 0) {
-                    target = (uint32_t)w;
-                    label = 1.0f;
-                } else {
-                    const uint32_t x = (uint32_t)(next_random >> 16) % cum_last;
-                    target = __builtin_amdgcn_readfirstlane(bisect_left_wave(cum_table, x, (uint32_t)V, lane));
-                    next_random = (next_random * 25214903917ULL + 11) & LCG_MOD;
-                    if (target == (uint32_t)w) continue;
-                    label = 0.0f;
-                }
-                const float* __restrict__ row = syn1neg + (int64_t)target * dim;
-                float p = 0.0f;
-#pragma unroll
-                for (int c = 0; c < EPL; ++c) {
-                    rw[c] = (lane + 64 * c < dim) ? row[lane + 64 * c] : 0.0f;
-                    p = fmaf(v[c], rw[c], p);
-                }
-                p = wave_sum_butterfly(p);
-                float f = p;
-                if (f <= -(float)MAX_EXP || f >= (float)MAX_EXP) continue;
-                f = exp_table[(int)((double)(f + (float)MAX_EXP) * exp_scale)];
-                const float g = (label - f) * a;
-#pragma unroll
-                for (int c = 0; c < EPL; ++c) work[c] = fmaf(g, rw[c], work[c]);
-            }
+            const int32_t w = __builtin_amdgcn_readfirstlane(docs.words[i]);
+            if (w < 0 || w >= m.V) continue;
+            if (m.sample_int && !subsample_keeps(m.sample_int[w], next_random)) continue;
+            ns_word_step<EPL, Hidden::none>(v, w, next_random, m, cum_last, a, exp_table, lane, work);
 #pragma unroll
             for (int c = 0; c < EPL; ++c) v[c] = v[c] + work[c];
         }
-        alpha -= alpha_delta;
     }
-#pragma unroll
-    for (int c = 0; c < EPL; ++c)
-        if (lane + 64 * c < dim) out[doc * dim + lane + 64 * c] = v[c];
+    store_vec<EPL>(docs.out + doc * m.dim, v, m.dim, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -193,50 +280,38 @@ __global__ __launch_bounds__(256) void d2v_infer_kernel(const float* __restrict_
 constexpr int DM_CAP = 512;        // kept words of one document (host-checked against the raw length)
 
 template <int EPL>
-__global__ __launch_bounds__(256) void d2v_infer_dm_kernel(const float* __restrict__ syn1neg, const float* __restrict__ wv,
-                                                           const uint32_t* __restrict__ cum_table, const uint32_t* __restrict__ sample_int,
-                                                           int64_t V, int dim, const int64_t* __restrict__ doc_ptr,
-                                                           const int32_t* __restrict__ words, int64_t ndocs, const float* __restrict__ v0,
-                                                           const uint64_t* __restrict__ seeds, int epochs, float alpha0, float min_alpha,
-                                                           int negative, double exp_scale, const float* __restrict__ exp_table_g, int window,
-                                                           int dm_mean, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void d2v_infer_dm_kernel(Model m, const float* __restrict__ wv, Docs docs, Schedule sched, int window, int dm_mean) {
     __shared__ float exp_table[EXP_TABLE_SIZE];
     __shared__ int32_t s_kept[4][DM_CAP];
     __shared__ int32_t s_red[4][DM_CAP];
-    for (int i = threadIdx.x; i < EXP_TABLE_SIZE; i += 256) exp_table[i] = exp_table_g[i];
+    load_exp_table(exp_table, m.exp_table, 256);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t doc = (int64_t)blockIdx.x * 4 + wid;
-    if (doc >= ndocs) return;                       // whole wave exits together
+    if (doc >= docs.ndocs) return;                  // whole wave exits together
     int32_t* kept = s_kept[wid];
     int32_t* red = s_red[wid];
     float v[EPL], work[EPL], rw[EPL], l1[EPL];
-#pragma unroll
-    for (int c = 0; c < EPL; ++c) v[c] = (lane + 64 * c < dim) ? v0[doc * dim + lane + 64 * c] : 0.0f;
-    const int64_t wb = doc_ptr[doc], we = doc_ptr[doc + 1];
-    const uint64_t seed = seeds[doc];
-    const uint32_t cum_last = cum_table[V - 1];
-    double alpha = (double)alpha0;
-    const double alpha_delta = ((double)alpha0 - (double)min_alpha) / (double)(epochs - 1 > 1 ? epochs - 1 : 1);
-    for (int e = 0; e < epochs; ++e) {
-        uint64_t next_random = uniform64(splitmix64(seed + (uint64_t)e) & LCG_MOD);
-        const float a = (float)alpha;
+    load_vec<EPL>(v, docs.v0 + doc * m.dim, m.dim, lane);
+    const int64_t wb = docs.doc_ptr[doc], we = docs.doc_ptr[doc + 1];
+    const uint64_t seed = docs.seeds[doc];
+    const uint32_t cum_last = m.cum_table[m.V - 1];
+    InferAlpha alpha(sched);
+    for (int e = 0; e < sched.epochs; ++e) {
+        uint64_t next_random = epoch_lcg(seed, (uint64_t)e);
+        const float a = alpha.next();
         int n = 0;
         for (int64_t i = wb; i < we; ++i) {
-            const int32_t w = __builtin_amdgcn_readfirstlane(words[i]);
-            if (w < 0 || w >= V) continue;
-            if (sample_int) {
-                const uint64_t r = next_random >> 16;
-                next_random = (next_random * 25214903917ULL + 11) & LCG_MOD;
-                if ((uint64_t)sample_int[w] < r) continue;
-            }
+            const int32_t w = __builtin_amdgcn_readfirstlane(docs.words[i]);
+            if (w < 0 || w >= m.V) continue;
+            if (m.sample_int && !subsample_keeps(m.sample_int[w], next_random)) continue;
             if (lane == 0) kept[n] = w;
             ++n;
         }
         for (int i = 0; i < n; ++i) {
-            if (lane == 0) red[i] = (int32_t)((uint32_t)(next_random >> 16) % (uint32_t)window);
-            next_random = (next_random * 25214903917ULL + 11) & LCG_MOD;
+            const uint32_t b = (uint32_t)lcg_draw(next_random) % (uint32_t)window;
+            if (lane == 0) red[i] = (int32_t)b;
         }
         // lane 0's LDS writes are read by every lane of this wave below: LDS operations of one wave execute in order, the fence
         // only keeps the compiler from moving them
@@ -251,13 +326,13 @@ __global__ __launch_bounds__(256) void d2v_infer_dm_kernel(const float* __restri
 #pragma unroll
             for (int c = 0; c < EPL; ++c) l1[c] = 0.0f;
             float count = 0.0f;
-            for (int m = j; m < k; ++m) {
-                if (m == i) continue;
+            for (int mm = j; mm < k; ++mm) {
+                if (mm == i) continue;
                 count += 1.0f;
-                const int32_t wm = __builtin_amdgcn_readfirstlane(kept[m]);
-                const float* __restrict__ row = wv + (int64_t)wm * dim;
+                const int32_t wm = __builtin_amdgcn_readfirstlane(kept[mm]);
+                load_vec<EPL>(rw, wv + (int64_t)wm * m.dim, m.dim, lane);
 #pragma unroll
-                for (int c = 0; c < EPL; ++c) l1[c] = l1[c] + ((lane + 64 * c < dim) ? row[lane + 64 * c] : 0.0f);
+                for (int c = 0; c < EPL; ++c) l1[c] = l1[c] + rw[c];
             }
             count += 1.0f;                                  // the document tag
 #pragma unroll
@@ -267,37 +342,8 @@ __global__ __launch_bounds__(256) void d2v_infer_dm_kernel(const float* __restri
 #pragma unroll
                 for (int c = 0; c < EPL; ++c) l1[c] = l1[c] * inv_count;
             }
-#pragma unroll
-            for (int c = 0; c < EPL; ++c) work[c] = 0.0f;
             const int32_t w = __builtin_amdgcn_readfirstlane(kept[i]);
-            for (int d = 0; d < negative + 1; ++d) {
-                uint32_t target;
-                float label;
-                if (d == 0) {
-                    target = (uint32_t)w;
-                    label = 1.0f;
-                } else {
-                    const uint32_t x = (uint32_t)(next_random >> 16) % cum_last;
-                    target = __builtin_amdgcn_readfirstlane(bisect_left_wave(cum_table, x, (uint32_t)V, lane));
-                    next_random = (next_random * 25214903917ULL + 11) & LCG_MOD;
-                    if (target == (uint32_t)w) continue;
-                    label = 0.0f;
-                }
-                const float* __restrict__ row = syn1neg + (int64_t)target * dim;
-                float p = 0.0f;
-#pragma unroll
-                for (int c = 0; c < EPL; ++c) {
-                    rw[c] = (lane + 64 * c < dim) ? row[lane + 64 * c] : 0.0f;
-                    p = fmaf(l1[c], rw[c], p);
-                }
-                p = wave_sum_butterfly(p);
-                float f = p;
-                if (f <= -(float)MAX_EXP || f >= (float)MAX_EXP) continue;
-                f = exp_table[(int)((double)(f + (float)MAX_EXP) * exp_scale)];
-                const float g = (label - f) * a;
-#pragma unroll
-                for (int c = 0; c < EPL; ++c) work[c] = fmaf(g, rw[c], work[c]);
-            }
+            ns_word_step<EPL, Hidden::none>(l1, w, next_random, m, cum_last, a, exp_table, lane, work);
             if (!dm_mean) {
 #pragma unroll
                 for (int c = 0; c < EPL; ++c) work[c] = work[c] * inv_count;
@@ -308,11 +354,8 @@ __global__ __launch_bounds__(256) void d2v_infer_dm_kernel(const float* __restri
         // the next epoch's list writes must not overtake this epoch's list reads (same wave, in order; compiler fence only)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        alpha -= alpha_delta;
     }
-#pragma unroll
-    for (int c = 0; c < EPL; ++c)
-        if (lane + 64 * c < dim) out[doc * dim + lane + 64 * c] = v[c];
+    store_vec<EPL>(docs.out + doc * m.dim, v, m.dim, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -389,13 +432,17 @@ __global__ __launch_bounds__(256) void d2v_infer_plan_kernel(const float* __rest
                                                              int64_t ndocs, const float* __restrict__ v0, const uint64_t* __restrict__ seeds,
                                                              int epochs, float alpha0, float min_alpha, int negative, double exp_scale,
                                                              const float* __restrict__ exp_table_g, float* __restrict__ out) {
+    // This kernel is held to its measured instruction stream.  Plain parameters, not Model / Docs / Schedule: with the structs it (and
+    // only it) needed 4-6 VGPRs more and lost a wave of occupancy at 2 elements per lane.  Its start-vector load, result store and alpha
+    // schedule are written out instead of load_vec / store_vec / InferAlpha: with those the prologue was four instructions longer and a
+    // 100-epoch document took 4 % longer (LABNOTES).  syn1neg is the LANE-MAJOR copy (d2v_lane_major_kernel).
     __shared__ float exp_table[EXP_TABLE_SIZE];
     __shared__ uint32_t coarse[PLAN_COARSE];
     __shared__ uint32_t plan_raw[4][PLAN_CAP], plan_own[4][PLAN_CAP], plan[4][PLAN_CAP];
     __shared__ int32_t cw[4][PLAN_WORDS];
     __shared__ uint32_t csi[4][PLAN_WORDS];
     const uint32_t stride = (uint32_t)((V + PLAN_COARSE - 1) / PLAN_COARSE);
-    for (int i = threadIdx.x; i < EXP_TABLE_SIZE; i += 256) exp_table[i] = exp_table_g[i];
+    load_exp_table(exp_table, exp_table_g, 256);
     for (uint32_t c = threadIdx.x; c * stride < (uint32_t)V; c += 256) {
         const uint32_t last = (c + 1) * stride < (uint32_t)V ? (c + 1) * stride : (uint32_t)V;
         coarse[c] = cum_table[last - 1];
@@ -404,7 +451,7 @@ __global__ __launch_bounds__(256) void d2v_infer_plan_kernel(const float* __rest
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t doc = (int64_t)blockIdx.x * 4 + wv;
     if (doc >= ndocs) return;                       // whole wave exits together (no barrier below)
-    float v[EPL], work[EPL];
+    float v[EPL];
 #pragma unroll
     for (int c = 0; c < EPL; ++c) v[c] = (lane + 64 * c < dim) ? v0[doc * dim + lane + 64 * c] : 0.0f;
     const int64_t wb = doc_ptr[doc], we = doc_ptr[doc + 1];
@@ -415,7 +462,6 @@ __global__ __launch_bounds__(256) void d2v_infer_plan_kernel(const float* __rest
     uint32_t* praw = plan_raw[wv];
     uint32_t* pown = plan_own[wv];
     uint32_t* pl = plan[wv];
-    // (syn1neg here is the LANE-MAJOR copy, d2v_lane_major_kernel: dwordx4 blocks, then the tail block)
     constexpr int N4 = EPL >> 2, TW = (EPL & 3) == 3 ? 4 : (EPL & 3), ROWF = 64 * (4 * N4 + TW);
     auto load_row = [&](uint32_t e, float (&rw)[EPL]) {
         const float* __restrict__ row = syn1neg + (int64_t)(e & ~PLAN_POS) * ROWF;
@@ -435,7 +481,7 @@ __global__ __launch_bounds__(256) void d2v_infer_plan_kernel(const float* __rest
         }
     };
     for (int e = 0; e < epochs; ++e) {
-        uint64_t next_random = uniform64(splitmix64(seed + (uint64_t)e) & LCG_MOD);
+        uint64_t next_random = epoch_lcg(seed, (uint64_t)e);
         const float a = (float)alpha;
         for (int64_t c0 = wb; c0 < we; c0 += PLAN_WORDS) {
             const int nc = (int)(we - c0 < PLAN_WORDS ? we - c0 : PLAN_WORDS);
@@ -451,21 +497,17 @@ __global__ __launch_bounds__(256) void d2v_infer_plan_kernel(const float* __rest
             for (int i = 0; i < nc; ++i) {
                 const int32_t w = __builtin_amdgcn_readfirstlane(cw[wv][i]);
                 if (w < 0 || w >= V) continue;
-                if (sample_int) {
-                    const uint64_t r = next_random >> 16;
-                    next_random = (next_random * 25214903917ULL + 11) & LCG_MOD;
-                    if ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(csi[wv][i]) < r) continue;      // (the builtin returns int: no sign extension)
-                }
+                if (sample_int && !subsample_keeps((uint32_t)__builtin_amdgcn_readfirstlane(csi[wv][i]), next_random)) continue;
                 if (lane == 0) {
                     praw[n] = (uint32_t)w;
                     pown[n] = 0xffffffffu;          // marks a positive target (a raw draw may have any of its 32 bits set)
                 }
                 for (int d = 1; d <= negative; ++d) {
+                    const uint32_t r = (uint32_t)lcg_draw(next_random);
                     if (lane == 0) {
-                        praw[n + d] = (uint32_t)(next_random >> 16);
+                        praw[n + d] = r;
                         pown[n + d] = (uint32_t)w;
                     }
-                    next_random = (next_random * 25214903917ULL + 11) & LCG_MOD;
                 }
                 n += 1 + negative;
             }
@@ -525,9 +567,8 @@ __global__ __launch_bounds__(256) void d2v_infer_plan_kernel(const float* __rest
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
                     const float f = g < gs ? wave_sum_butterfly(p[g]) : 0.0f;
-                    ok[g] = g < gs && !(f <= -(float)MAX_EXP || f >= (float)MAX_EXP);
-                    const int idx = ok[g] ? (int)((double)(f + (float)MAX_EXP) * exp_scale) : 0;
-                    tv[g] = exp_table[idx];
+                    ok[g] = g < gs && sigmoid_in_window(f);
+                    tv[g] = exp_table[ok[g] ? sigmoid_index(f, exp_scale) : 0];
                 }
                 float wk[EPL];
 #pragma unroll
@@ -590,104 +631,112 @@ __global__ __launch_bounds__(256) void d2v_infer_plan_kernel(const float* __rest
 //                        stores lose nearly every update -- measured: neighbour purity at chance).  Not reproducible run to
 //                        run; its quality is judged downstream (tests/test_gpu_d2v_train.py).
 // ---------------------------------------------------------------------------------------------
-template <int EPL, bool ATOMIC>
-__device__ __forceinline__ void train_document(float* __restrict__ syn1neg, const uint32_t* __restrict__ cum_table,
-                                               const uint32_t* __restrict__ sample_int, int64_t V, int dim, const int32_t* __restrict__ words,
-                                               int64_t wb, int64_t we, float* __restrict__ vrow, uint64_t lcg0, float a, int negative,
-                                               double exp_scale, const float* exp_table, uint32_t cum_last, int lane) {
-    float v[EPL], work[EPL], rw[EPL];
-#pragma unroll
-    for (int c = 0; c < EPL; ++c) v[c] = (lane + 64 * c < dim) ? vrow[lane + 64 * c] : 0.0f;
-    uint64_t next_random = uniform64(lcg0);
+template <int EPL, Hidden H>
+__device__ __forceinline__ void train_document(const Model& m, const int32_t* __restrict__ words, int64_t wb, int64_t we, float* __restrict__ vrow,
+                                               uint64_t next_random, float a, const float* exp_table, uint32_t cum_last, int lane) {
+    float v[EPL], work[EPL];
+    load_vec<EPL>(v, vrow, m.dim, lane);
     for (int64_t i = wb; i < we; ++i) {
         const int32_t w = __builtin_amdgcn_readfirstlane(words[i]);
-        if (w < 0 || w >= V) continue;
-        if (sample_int) {
-            const uint64_t r = next_random >> 16;
-            next_random = (next_random * 25214903917ULL + 11) & LCG_MOD;
-            if ((uint64_t)sample_int[w] < r) continue;
-        }
-#pragma unroll
-        for (int c = 0; c < EPL; ++c) work[c] = 0.0f;
-        for (int d = 0; d < negative + 1; ++d) {
-            uint32_t target;
-            float label;
-            if (d == 0) {
-                target = (uint32_t)w;
-                label = 1.0f;
-            } else {
-                const uint32_t x = (uint32_t)(next_random >> 16) % cum_last;
-                target = __builtin_amdgcn_readfirstlane(bisect_left_wave(cum_table, x, (uint32_t)V, lane));
-                next_random = (next_random * 25214903917ULL + 11) & LCG_MOD;
-                if (target == (uint32_t)w) continue;
-                label = 0.0f;
-            }
-            float* __restrict__ row = syn1neg + (int64_t)target * dim;
-            float p = 0.0f;
-#pragma unroll
-            for (int c = 0; c < EPL; ++c) {
-                rw[c] = (lane + 64 * c < dim) ? row[lane + 64 * c] : 0.0f;
-                p = fmaf(v[c], rw[c], p);
-            }
-            p = wave_sum_butterfly(p);
-            float f = p;
-            if (f <= -(float)MAX_EXP || f >= (float)MAX_EXP) continue;
-            f = exp_table[(int)((double)(f + (float)MAX_EXP) * exp_scale)];
-            const float g = (label - f) * a;
-#pragma unroll
-            for (int c = 0; c < EPL; ++c) {
-                work[c] = fmaf(g, rw[c], work[c]);                                   // work += g * syn1neg[target]
-                if (lane + 64 * c < dim) {                                           // syn1neg[target] += g * doc   (learn_hidden)
-                    if (ATOMIC) unsafeAtomicAdd(&row[lane + 64 * c], g * v[c]);      // concurrent documents: no update is lost
-                    else row[lane + 64 * c] = fmaf(g, v[c], rw[c]);
-                }
-            }
-        }
+        if (w < 0 || w >= m.V) continue;
+        if (m.sample_int && !subsample_keeps(m.sample_int[w], next_random)) continue;
+        ns_word_step<EPL, H>(v, w, next_random, m, cum_last, a, exp_table, lane, work);
 #pragma unroll
         for (int c = 0; c < EPL; ++c) v[c] = v[c] + work[c];
     }
-#pragma unroll
-    for (int c = 0; c < EPL; ++c)
-        if (lane + 64 * c < dim) vrow[lane + 64 * c] = v[c];
+    store_vec<EPL>(vrow, v, m.dim, lane);
 }
 
-__device__ __forceinline__ float job_alpha(int epoch, int64_t job_first, int64_t ndocs, int epochs, float alpha0, float min_alpha) {
-    const double progress = ((double)epoch + (double)job_first / (double)ndocs) / (double)epochs;
-    double al = (double)alpha0 - ((double)alpha0 - (double)min_alpha) * progress;
-    if (al < (double)min_alpha) al = (double)min_alpha;
+__device__ __forceinline__ float job_alpha(int epoch, int64_t job_first, int64_t ndocs, const Schedule& s) {
+    const double progress = ((double)epoch + (double)job_first / (double)ndocs) / (double)s.epochs;
+    double al = (double)s.alpha0 - ((double)s.alpha0 - (double)s.min_alpha) * progress;
+    if (al < (double)s.min_alpha) al = (double)s.min_alpha;
     return (float)al;
 }
 
 // mode 1: grid over documents [doc0, doc1) of ONE epoch.  mode 0: one wavefront (grid 1, 64 threads), epochs [epoch0, epoch1).
 template <int EPL, bool SEQUENTIAL>
-__global__ __launch_bounds__(256) void d2v_train_kernel(float* __restrict__ syn1neg, float* __restrict__ doc_vectors,
-                                                        const uint32_t* __restrict__ cum_table, const uint32_t* __restrict__ sample_int,
-                                                        int64_t V, int dim, const int64_t* __restrict__ doc_ptr, const int32_t* __restrict__ words,
-                                                        const int64_t* __restrict__ job_first, int64_t ndocs, int epoch0, int epoch1, int epochs,
-                                                        float alpha0, float min_alpha, int negative, double exp_scale, uint64_t seed,
-                                                        const float* __restrict__ exp_table_g, int64_t doc0, int64_t doc1) {
+__global__ __launch_bounds__(256) void d2v_train_kernel(Model m, Schedule sched, const int64_t* __restrict__ doc_ptr, const int32_t* __restrict__ words,
+                                                        const int64_t* __restrict__ job_first, int64_t ndocs, float* __restrict__ doc_vectors,
+                                                        uint64_t seed, int epoch0, int epoch1, int64_t doc0, int64_t doc1) {
     __shared__ float exp_table[EXP_TABLE_SIZE];
-    for (int i = threadIdx.x; i < EXP_TABLE_SIZE; i += blockDim.x) exp_table[i] = exp_table_g[i];
+    load_exp_table(exp_table, m.exp_table, blockDim.x);      // 64 threads sequential, 256 parallel
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const uint32_t cum_last = cum_table[V - 1];
+    const uint32_t cum_last = m.cum_table[m.V - 1];
     if (SEQUENTIAL) {
         if (blockIdx.x != 0 || threadIdx.x >= 64) return;
         for (int e = epoch0; e < epoch1; ++e)
-            for (int64_t doc = 0; doc < ndocs; ++doc) {
-                const float a = job_alpha(e, job_first[doc], ndocs, epochs, alpha0, min_alpha);
-                const uint64_t lcg0 = splitmix64(seed + (uint64_t)e * (uint64_t)ndocs + (uint64_t)doc) & LCG_MOD;
-                train_document<EPL, false>(syn1neg, cum_table, sample_int, V, dim, words, doc_ptr[doc], doc_ptr[doc + 1], doc_vectors + doc * dim, lcg0,
-                                           a, negative, exp_scale, exp_table, cum_last, lane);
-            }
+            for (int64_t doc = 0; doc < ndocs; ++doc)
+                train_document<EPL, Hidden::store>(m, words, doc_ptr[doc], doc_ptr[doc + 1], doc_vectors + doc * m.dim,
+                                                   epoch_lcg(seed, (uint64_t)e * (uint64_t)ndocs + (uint64_t)doc),
+                                                   job_alpha(e, job_first[doc], ndocs, sched), exp_table, cum_last, lane);
     } else {
         const int64_t doc = doc0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
         if (doc >= doc1) return;
-        const float a = job_alpha(epoch0, job_first[doc], ndocs, epochs, alpha0, min_alpha);
-        const uint64_t lcg0 = splitmix64(seed + (uint64_t)epoch0 * (uint64_t)ndocs + (uint64_t)doc) & LCG_MOD;
-        train_document<EPL, true>(syn1neg, cum_table, sample_int, V, dim, words, doc_ptr[doc], doc_ptr[doc + 1], doc_vectors + doc * dim, lcg0, a,
-                                  negative, exp_scale, exp_table, cum_last, lane);
+        train_document<EPL, Hidden::atomic>(m, words, doc_ptr[doc], doc_ptr[doc + 1], doc_vectors + doc * m.dim,
+                                            epoch_lcg(seed, (uint64_t)epoch0 * (uint64_t)ndocs + (uint64_t)doc),
+                                            job_alpha(epoch0, job_first[doc], ndocs, sched), exp_table, cum_last, lane);
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Host side
+// ---------------------------------------------------------------------------------------------
+// word2vec_inner.pyx: EXP_TABLE[i] = exp((i / 1000 * 2 - 1) * 6); EXP_TABLE[i] /= (EXP_TABLE[i] + 1)   (REAL_t)
+void exp_table_host(float (&table)[EXP_TABLE_SIZE]) {
+    for (int i = 0; i < EXP_TABLE_SIZE; ++i) {
+        const float e = (float)exp((i / (float)EXP_TABLE_SIZE * 2 - 1) * MAX_EXP);
+        table[i] = (float)(e / (e + 1));
+    }
+}
+
+// The kernels are instantiated for 1 .. 8 elements per lane (dim <= 512): f(std::integral_constant<int, EPL>).
+template <typename F>
+void dispatch_epl(int epl, F f) {
+    switch (epl) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        default: return f(std::integral_constant<int, 8>{});
+    }
+}
+
+Model model_of(const hipts_d2v* h, const DevBuf& syn) {
+    return Model{syn.as<float>(), h->cum_table.as<uint32_t>(), h->has_sample ? h->sample_int.as<uint32_t>() : nullptr,
+                 h->exp_table.as<float>(), h->V, h->dim, h->negative, h->exp_scale};
+}
+
+// Inference input into the handle's staging buffers (enqueued on s); the result goes to `out` itself when that is device memory.
+int stage_documents(hipts_d2v* h, const int64_t* doc_ptr, const int32_t* words, int64_t ndocs, const float* v0, const uint64_t* seeds,
+                    float* out, int out_memspace, hipStream_t s, Docs* docs) {
+    const int64_t nw = doc_ptr[ndocs];
+    HIPTS_TRY(h->ws_ptr.reserve((size_t)(ndocs + 1) * 8));
+    HIPTS_TRY(h->ws_words.reserve((size_t)(nw ? nw : 1) * 4));
+    HIPTS_TRY(h->ws_v0.reserve((size_t)ndocs * h->dim * 4));
+    HIPTS_TRY(h->ws_seeds.reserve((size_t)ndocs * 8));
+    HIPTS_HIP(hipMemcpyAsync(h->ws_ptr.p, doc_ptr, (size_t)(ndocs + 1) * 8, hipMemcpyHostToDevice, s));
+    if (nw) HIPTS_HIP(hipMemcpyAsync(h->ws_words.p, words, (size_t)nw * 4, hipMemcpyHostToDevice, s));
+    HIPTS_HIP(hipMemcpyAsync(h->ws_v0.p, v0, (size_t)ndocs * h->dim * 4, hipMemcpyHostToDevice, s));
+    HIPTS_HIP(hipMemcpyAsync(h->ws_seeds.p, seeds, (size_t)ndocs * 8, hipMemcpyHostToDevice, s));
+    float* out_dev = out;
+    if (out_memspace != HIPTS_DEVICE) {
+        HIPTS_TRY(h->ws_out.reserve((size_t)ndocs * h->dim * 4));
+        out_dev = h->ws_out.as<float>();
+    }
+    *docs = Docs{h->ws_ptr.as<int64_t>(), h->ws_words.as<int32_t>(), ndocs, h->ws_v0.as<float>(), h->ws_seeds.as<uint64_t>(), out_dev};
+    return HIPTS_OK;
+}
+
+int finish_documents(hipts_d2v* h, const Docs& docs, float* out, int out_memspace, hipStream_t s) {
+    HIPTS_LAUNCH_CHECK();
+    if (out_memspace != HIPTS_DEVICE) HIPTS_HIP(hipMemcpyAsync(out, docs.out, (size_t)docs.ndocs * h->dim * 4, hipMemcpyDeviceToHost, s));
+    HIPTS_HIP(hipStreamSynchronize(s));   // staging buffers are reused by the next call
+    return HIPTS_OK;
 }
 
 }  // namespace
@@ -708,12 +757,8 @@ int hipts_d2v_create(const float* syn1neg, const uint32_t* cum_table, const uint
     h->negative = negative;
     h->exp_scale = exp_scale;
     h->has_sample = sample_int != nullptr;
-    // word2vec_inner.pyx: EXP_TABLE[i] = exp((i / 1000 * 2 - 1) * 6); EXP_TABLE[i] /= (EXP_TABLE[i] + 1)   (REAL_t)
     float table[EXP_TABLE_SIZE];
-    for (int i = 0; i < EXP_TABLE_SIZE; ++i) {
-        const float e = (float)exp((i / (float)EXP_TABLE_SIZE * 2 - 1) * MAX_EXP);
-        table[i] = (float)(e / (e + 1));
-    }
+    exp_table_host(table);
     int st;
     if ((st = h->syn1neg.alloc((size_t)vocab * dim * 4)) || (st = h->cum_table.alloc((size_t)vocab * 4)) ||
         (st = h->exp_table.alloc(sizeof(table))) || (st = upload(h->syn1neg.p, syn1neg, (size_t)vocab * dim * 4)) ||
@@ -754,53 +799,20 @@ int hipts_d2v_infer(hipts_d2v_t* h, const int64_t* doc_ptr, const int32_t* words
     hipStream_t s = (hipStream_t)stream;
     const int64_t nw = doc_ptr[ndocs];
     HIPTS_REQUIRE(doc_ptr[0] == 0 && nw >= 0 && (words || nw == 0), "hipts_d2v_infer: bad CSR");
-    HIPTS_TRY(h->ws_ptr.reserve((size_t)(ndocs + 1) * 8));
-    HIPTS_TRY(h->ws_words.reserve((size_t)nw * 4));
-    HIPTS_TRY(h->ws_v0.reserve((size_t)ndocs * h->dim * 4));
-    HIPTS_TRY(h->ws_seeds.reserve((size_t)ndocs * 8));
-    HIPTS_HIP(hipMemcpyAsync(h->ws_ptr.p, doc_ptr, (size_t)(ndocs + 1) * 8, hipMemcpyHostToDevice, s));
-    if (nw) HIPTS_HIP(hipMemcpyAsync(h->ws_words.p, words, (size_t)nw * 4, hipMemcpyHostToDevice, s));
-    HIPTS_HIP(hipMemcpyAsync(h->ws_v0.p, v0, (size_t)ndocs * h->dim * 4, hipMemcpyHostToDevice, s));
-    HIPTS_HIP(hipMemcpyAsync(h->ws_seeds.p, seeds, (size_t)ndocs * 8, hipMemcpyHostToDevice, s));
-    float* out_dev = out;
-    if (out_memspace != HIPTS_DEVICE) {
-        HIPTS_TRY(h->ws_out.reserve((size_t)ndocs * h->dim * 4));
-        out_dev = h->ws_out.as<float>();
-    }
+    Docs docs;
+    HIPTS_TRY(stage_documents(h, doc_ptr, words, ndocs, v0, seeds, out, out_memspace, s, &docs));
     const int grid = ceil_div(ndocs, 4);
-    const int epl = (h->dim + 63) / 64;
     static const bool planned_ok = !(getenv("HIPTS_D2V_PLAN") && strcmp(getenv("HIPTS_D2V_PLAN"), "0") == 0);      // A/B switch
     const bool planned = planned_ok && h->negative <= PLAN_MAX_NEG;
-#define D2V_LAUNCH(E)                                                                                                   \
-    if (planned)                                                                                                         \
-        d2v_infer_plan_kernel<E><<<grid, 256, 0, s>>>(h->syn_lane.as<float>(), h->cum_table.as<uint32_t>(),                \
-                                             h->has_sample ? h->sample_int.as<uint32_t>() : nullptr, h->V, h->dim,      \
-                                             h->ws_ptr.as<int64_t>(), h->ws_words.as<int32_t>(), ndocs,                 \
-                                             h->ws_v0.as<float>(), h->ws_seeds.as<uint64_t>(), epochs, alpha, min_alpha, \
-                                             h->negative, h->exp_scale, h->exp_table.as<float>(), out_dev);              \
-    else                                                                                                                 \
-        d2v_infer_kernel<E><<<grid, 256, 0, s>>>(h->syn1neg.as<float>(), h->cum_table.as<uint32_t>(),                   \
-                                             h->has_sample ? h->sample_int.as<uint32_t>() : nullptr, h->V, h->dim,      \
-                                             h->ws_ptr.as<int64_t>(), h->ws_words.as<int32_t>(), ndocs,                 \
-                                             h->ws_v0.as<float>(), h->ws_seeds.as<uint64_t>(), epochs, alpha, min_alpha, \
-                                             h->negative, h->exp_scale, h->exp_table.as<float>(), out_dev)
-    switch (epl) {
-        case 1: D2V_LAUNCH(1); break;
-        case 2: D2V_LAUNCH(2); break;
-        case 3: D2V_LAUNCH(3); break;
-        case 4: D2V_LAUNCH(4); break;
-        case 5: D2V_LAUNCH(5); break;
-        case 6: D2V_LAUNCH(6); break;
-        case 7: D2V_LAUNCH(7); break;
-        default: D2V_LAUNCH(8); break;
-    }
-#undef D2V_LAUNCH
-    HIPTS_LAUNCH_CHECK();
-    if (out_memspace != HIPTS_DEVICE) {
-        HIPTS_HIP(hipMemcpyAsync(out, out_dev, (size_t)ndocs * h->dim * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIPTS_HIP(hipStreamSynchronize(s));   // staging buffers are reused by the next call
-    return HIPTS_OK;
+    const Model m = model_of(h, planned ? h->syn_lane : h->syn1neg);
+    dispatch_epl((h->dim + 63) / 64, [&](auto epl) {
+        if (planned)
+            d2v_infer_plan_kernel<decltype(epl)::value><<<grid, 256, 0, s>>>(m.syn, m.cum_table, m.sample_int, m.V, m.dim, docs.doc_ptr, docs.words, docs.ndocs,
+                                                                              docs.v0, docs.seeds, epochs, alpha, min_alpha, m.negative, m.exp_scale,
+                                                                              m.exp_table, docs.out);
+        else d2v_infer_kernel<decltype(epl)::value><<<grid, 256, 0, s>>>(m, docs, Schedule{epochs, alpha, min_alpha});
+    });
+    return finish_documents(h, docs, out, out_memspace, s);
 }
 
 int hipts_d2v_set_word_vectors(hipts_d2v_t* h, const float* word_vectors) {
@@ -825,42 +837,14 @@ int hipts_d2v_infer_dm(hipts_d2v_t* h, const int64_t* doc_ptr, const int32_t* wo
         HIPTS_REQUIRE(doc_ptr[d + 1] >= doc_ptr[d] && doc_ptr[d + 1] - doc_ptr[d] <= DM_CAP,
                       "hipts_d2v_infer_dm: document %lld has %lld words, at most %d are supported", (long long)d,
                       (long long)(doc_ptr[d + 1] - doc_ptr[d]), DM_CAP);
-    HIPTS_TRY(h->ws_ptr.reserve((size_t)(ndocs + 1) * 8));
-    HIPTS_TRY(h->ws_words.reserve((size_t)(nw ? nw : 1) * 4));
-    HIPTS_TRY(h->ws_v0.reserve((size_t)ndocs * h->dim * 4));
-    HIPTS_TRY(h->ws_seeds.reserve((size_t)ndocs * 8));
-    HIPTS_HIP(hipMemcpyAsync(h->ws_ptr.p, doc_ptr, (size_t)(ndocs + 1) * 8, hipMemcpyHostToDevice, s));
-    if (nw) HIPTS_HIP(hipMemcpyAsync(h->ws_words.p, words, (size_t)nw * 4, hipMemcpyHostToDevice, s));
-    HIPTS_HIP(hipMemcpyAsync(h->ws_v0.p, v0, (size_t)ndocs * h->dim * 4, hipMemcpyHostToDevice, s));
-    HIPTS_HIP(hipMemcpyAsync(h->ws_seeds.p, seeds, (size_t)ndocs * 8, hipMemcpyHostToDevice, s));
-    float* out_dev = out;
-    if (out_memspace != HIPTS_DEVICE) {
-        HIPTS_TRY(h->ws_out.reserve((size_t)ndocs * h->dim * 4));
-        out_dev = h->ws_out.as<float>();
-    }
-    const int grid = ceil_div(ndocs, 4);
-    const int epl = (h->dim + 63) / 64;
-#define D2V_DM_LAUNCH(E)                                                                                                              \
-    d2v_infer_dm_kernel<E><<<grid, 256, 0, s>>>(h->syn1neg.as<float>(), h->word_vectors.as<float>(), h->cum_table.as<uint32_t>(),         \
-                                                h->has_sample ? h->sample_int.as<uint32_t>() : nullptr, h->V, h->dim,                 \
-                                                h->ws_ptr.as<int64_t>(), h->ws_words.as<int32_t>(), ndocs, h->ws_v0.as<float>(),       \
-                                                h->ws_seeds.as<uint64_t>(), epochs, alpha, min_alpha, h->negative, h->exp_scale,      \
-                                                h->exp_table.as<float>(), window, dm_mean ? 1 : 0, out_dev)
-    switch (epl) {
-        case 1: D2V_DM_LAUNCH(1); break;
-        case 2: D2V_DM_LAUNCH(2); break;
-        case 3: D2V_DM_LAUNCH(3); break;
-        case 4: D2V_DM_LAUNCH(4); break;
-        case 5: D2V_DM_LAUNCH(5); break;
-        case 6: D2V_DM_LAUNCH(6); break;
-        case 7: D2V_DM_LAUNCH(7); break;
-        default: D2V_DM_LAUNCH(8); break;
-    }
-#undef D2V_DM_LAUNCH
-    HIPTS_LAUNCH_CHECK();
-    if (out_memspace != HIPTS_DEVICE) HIPTS_HIP(hipMemcpyAsync(out, out_dev, (size_t)ndocs * h->dim * 4, hipMemcpyDeviceToHost, s));
-    HIPTS_HIP(hipStreamSynchronize(s));   // staging buffers are reused by the next call
-    return HIPTS_OK;
+    Docs docs;
+    HIPTS_TRY(stage_documents(h, doc_ptr, words, ndocs, v0, seeds, out, out_memspace, s, &docs));
+    const Schedule sched{epochs, alpha, min_alpha};
+    dispatch_epl((h->dim + 63) / 64, [&](auto epl) {
+        d2v_infer_dm_kernel<decltype(epl)::value><<<ceil_div(ndocs, 4), 256, 0, s>>>(model_of(h, h->syn1neg), h->word_vectors.as<float>(), docs, sched,
+                                                                                      window, dm_mean ? 1 : 0);
+    });
+    return finish_documents(h, docs, out, out_memspace, s);
 }
 
 int hipts_d2v_train(const uint32_t* cum_table, const uint32_t* sample_int, int64_t vocab, int dim, int negative, double exp_scale,
@@ -890,10 +874,7 @@ int hipts_d2v_train(const uint32_t* cum_table, const uint32_t* sample_int, int64
         }
     }
     float table[EXP_TABLE_SIZE];
-    for (int i = 0; i < EXP_TABLE_SIZE; ++i) {
-        const float e = (float)exp((i / (float)EXP_TABLE_SIZE * 2 - 1) * MAX_EXP);
-        table[i] = (float)(e / (e + 1));
-    }
+    exp_table_host(table);
     DevBuf d_syn, d_dv, d_cum, d_si, d_ptr, d_words, d_job, d_exp;
     HIPTS_TRY(d_syn.alloc((size_t)vocab * dim * 4));
     HIPTS_TRY(d_dv.alloc((size_t)ndocs * dim * 4));
@@ -913,27 +894,19 @@ int hipts_d2v_train(const uint32_t* cum_table, const uint32_t* sample_int, int64
         HIPTS_TRY(d_si.alloc((size_t)vocab * 4));
         HIPTS_TRY(upload(d_si.p, sample_int, (size_t)vocab * 4, s));
     }
-    const int epl = (dim + 63) / 64;
-#define D2V_TRAIN(E, SEQ, GRID, THREADS, E0, E1, D0, D1)                                                                                              \
-    d2v_train_kernel<E, SEQ><<<GRID, THREADS, 0, s>>>(d_syn.as<float>(), d_dv.as<float>(), d_cum.as<uint32_t>(),                               \
-                                                      sample_int ? d_si.as<uint32_t>() : nullptr, vocab, dim, d_ptr.as<int64_t>(),              \
-                                                      d_words.as<int32_t>(), d_job.as<int64_t>(), ndocs, E0, E1, epochs, alpha, min_alpha,      \
-                                                      negative, exp_scale, seed, d_exp.as<float>(), D0, D1)
-#define D2V_TRAIN_EPL(SEQ, GRID, THREADS, E0, E1, D0, D1)                 \
-    switch (epl) {                                                \
-        case 1: D2V_TRAIN(1, SEQ, GRID, THREADS, E0, E1, D0, D1); break;  \
-        case 2: D2V_TRAIN(2, SEQ, GRID, THREADS, E0, E1, D0, D1); break;  \
-        case 3: D2V_TRAIN(3, SEQ, GRID, THREADS, E0, E1, D0, D1); break;  \
-        case 4: D2V_TRAIN(4, SEQ, GRID, THREADS, E0, E1, D0, D1); break;  \
-        case 5: D2V_TRAIN(5, SEQ, GRID, THREADS, E0, E1, D0, D1); break;  \
-        case 6: D2V_TRAIN(6, SEQ, GRID, THREADS, E0, E1, D0, D1); break;  \
-        case 7: D2V_TRAIN(7, SEQ, GRID, THREADS, E0, E1, D0, D1); break;  \
-        default: D2V_TRAIN(8, SEQ, GRID, THREADS, E0, E1, D0, D1); break; \
-    }
+    const Model model{d_syn.as<float>(), d_cum.as<uint32_t>(), sample_int ? d_si.as<uint32_t>() : nullptr, d_exp.as<float>(), vocab, dim, negative, exp_scale};
+    const Schedule sched{epochs, alpha, min_alpha};
+    // sequential: one wavefront, documents [0, ndocs); parallel: a wavefront per document of [d0, d1).  A launch covers one epoch.
+    auto launch = [&](auto sequential, int grid, int threads, int e, int64_t d0, int64_t d1) {
+        dispatch_epl((dim + 63) / 64, [&](auto epl) {
+            d2v_train_kernel<decltype(epl)::value, decltype(sequential)::value><<<grid, threads, 0, s>>>(
+                model, sched, d_ptr.as<int64_t>(), d_words.as<int32_t>(), d_job.as<int64_t>(), ndocs, d_dv.as<float>(), seed, e, e + 1, d0, d1);
+        });
+    };
     if (mode == 0) {
         // one wavefront; a launch per epoch keeps each kernel bounded (a watchdog-safe few seconds even for mid-sized corpora)
         for (int e = 0; e < epochs; ++e) {
-            D2V_TRAIN_EPL(true, 1, 64, e, e + 1, 0, ndocs);
+            launch(std::true_type{}, 1, 64, e, 0, ndocs);
             HIPTS_LAUNCH_CHECK();
         }
     } else {
@@ -941,12 +914,10 @@ int hipts_d2v_train(const uint32_t* cum_table, const uint32_t* sample_int, int64
         for (int e = 0; e < epochs; ++e)
             for (int64_t d0 = 0; d0 < ndocs; d0 += chunk) {
                 const int64_t d1 = d0 + chunk < ndocs ? d0 + chunk : ndocs;
-                D2V_TRAIN_EPL(false, ceil_div(d1 - d0, 4), 256, e, e + 1, d0, d1);
+                launch(std::false_type{}, ceil_div(d1 - d0, 4), 256, e, d0, d1);
                 HIPTS_LAUNCH_CHECK();
             }
     }
-#undef D2V_TRAIN_EPL
-#undef D2V_TRAIN
     HIPTS_HIP(hipMemcpyAsync(syn1neg, d_syn.p, (size_t)vocab * dim * 4, hipMemcpyDeviceToHost, s));
     HIPTS_HIP(hipMemcpyAsync(doc_vectors, d_dv.p, (size_t)ndocs * dim * 4, hipMemcpyDeviceToHost, s));
     HIPTS_HIP(hipStreamSynchronize(s));

@@ -2,6 +2,8 @@
 and tag selection (index-exact vs the numpy oracle and the reference-captured golden lines)."""
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -91,6 +93,113 @@ def test_d2v_gensim_shaped_interface():
     np.testing.assert_array_equal(a, b)                      # deterministic, unlike gensim's hash()-seeded start
     c = model.infer_vector([toks[2]])
     assert not np.array_equal(a, c)
+
+
+# ------------------------------------------------------------------ every Doc2Vec inference kernel, row layout and chunk boundary
+# Two small corpora over V = 70.  A: 24 documents of 31..51 words, 23 of them longer than one 32-word chunk of the planned kernel, document
+# 3 wholly out of vocabulary.  B: lengths around the chunk boundaries, one empty document, one whose only word is out of vocabulary, and 9
+# documents (not a multiple of the 4 waves of a workgroup).  Model and inputs as in the tests above.
+_D2V_V = 70
+
+
+def _d2v_corpus_a():
+    from hiptagsearch import synth
+    ptr, terms = synth.tag_corpus(D=24, V=_D2V_V, seed=7, mean_len=45)
+    terms = terms.copy()
+    terms[::17] = -1
+    terms[ptr[3]:ptr[4]] = -1
+    return ptr, terms, [3]
+
+
+def _d2v_corpus_b():
+    lens = [0, 1, 31, 32, 33, 63, 64, 65, 97]
+    ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    terms = np.random.default_rng(11).integers(0, _D2V_V, int(ptr[-1])).astype(np.int32)
+    terms[::17] = -1
+    return ptr, terms, [0, 1]                                # document 1's one word is position 0: out of vocabulary
+
+
+def _check_d2v_infer(corpus, dim, epochs=3, with_sample=True, negative=5, dm=None):
+    """One inference call against the C oracle with the same explicit inputs, bit for bit; the documents named by the corpus come back as
+    their start vectors, every other one moves.  dm = (window, dm_mean) runs PV-DM."""
+    from hiptagsearch import synth
+    from hiptagsearch.d2v import Doc2VecInference
+    from oracle import d2v as od2v
+    ptr, terms, untouched = corpus
+    n = len(ptr) - 1
+    m = synth.d2v_model(synth.term_counts(ptr, terms, _D2V_V), dim=dim, seed=44)
+    v0, seeds = synth.d2v_inputs(n, dim, seed=44)
+    si = m["sample_int"] if with_sample else None
+    if dm is None:
+        model = Doc2VecInference(m["syn1neg"], m["cum_table"], si, {}, epochs=epochs, negative=negative)
+        want = od2v.infer(m["syn1neg"], m["cum_table"], si, ptr, terms, v0, seeds, epochs, negative=negative)
+    else:
+        window, dm_mean = dm
+        wv = (np.random.default_rng(46).standard_normal((_D2V_V, dim)) * 0.3).astype(np.float32)
+        model = Doc2VecInference(m["syn1neg"], m["cum_table"], si, {}, epochs=epochs, negative=negative, dm=1, word_vectors=wv,
+                                 window=window, dm_mean=dm_mean)
+        want = od2v.infer_dm(m["syn1neg"], wv, m["cum_table"], si, ptr, terms, v0, seeds, epochs, negative=negative, window=window,
+                             dm_mean=dm_mean)
+    got = model.infer_batch(ptr, terms, v0, seeds)
+    model.close()
+    assert np.isfinite(got).all()
+    assert got.tobytes() == want.tobytes()
+    for d in range(n):
+        assert np.array_equal(got[d], v0[d]) == (d in untouched), d
+
+
+@pytest.mark.parametrize("dim", [160, 256, 450, 512])
+def test_d2v_infer_row_layouts_bit_exact(dim):
+    """The planned kernel's lane-major rows (d2v_lane_major_kernel writes them, load_row reads them): 160 = 3 elements per lane, the tail
+    padded to 4; 256 = 4, no tail; 450 = 8 with the last element ragged (7 * 64 + 2); 512 = 8, full."""
+    _check_d2v_infer(_d2v_corpus_a(), dim)
+
+
+@pytest.mark.parametrize("negative", [5, 0])
+@pytest.mark.parametrize("with_sample", [True, False])
+@pytest.mark.parametrize("dim", [300, 64])
+def test_d2v_infer_chunk_boundaries_bit_exact(dim, with_sample, negative):
+    """Documents of 31 / 32 / 33 / 63 / 64 / 65 / 97 words around the planned kernel's 32-word chunks; negative 0 trains on positives only."""
+    _check_d2v_infer(_d2v_corpus_b(), dim, with_sample=with_sample, negative=negative)
+
+
+@pytest.mark.parametrize("with_sample", [True, False])
+def test_d2v_per_step_kernel_bit_exact(with_sample):
+    """negative = 6 is more than a planned group holds, so the default dispatch runs d2v_infer_kernel, the per-step kernel."""
+    _check_d2v_infer(_d2v_corpus_b(), 100, with_sample=with_sample, negative=6)
+
+
+def _check_d2v_plan_off():
+    assert os.environ.get("HIPTS_D2V_PLAN") == "0"
+    _check_d2v_infer(_d2v_corpus_b(), 300)
+    test_d2v_infer_bit_exact(64, 500, 8, 3, True)
+
+
+_D2V_CHILD = r"""
+import importlib.util, sys
+for p in %(paths)r:
+    sys.path.insert(0, p)
+spec = importlib.util.spec_from_file_location("d2v_plan_off", %(file)r)
+m = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(m)
+m._check_d2v_plan_off()
+"""
+
+
+def test_d2v_plan_switch_off_bit_exact():
+    """HIPTS_D2V_PLAN=0 sends negative <= 5 to the per-step kernel as well.  The switch is read once per process, hence the child."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = _D2V_CHILD % {"paths": [os.path.join(root, "anime-illust-image-searcher_amd"), root], "file": os.path.abspath(__file__)}
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, HIPTS_D2V_PLAN="0"), timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+
+
+@pytest.mark.parametrize("negative", [5, 0])
+@pytest.mark.parametrize("dim", [300, 100])
+@pytest.mark.parametrize("dm_mean", [1, 0])
+def test_d2v_infer_dm_chunk_boundaries_bit_exact(dm_mean, dim, negative):
+    """PV-DM over the same documents: reduced windows of width 5 cut the context inside every document longer than a few words."""
+    _check_d2v_infer(_d2v_corpus_b(), dim, negative=negative, dm=(5, dm_mean))
 
 
 # --------------------------------------------------------------------------------- tag selection
