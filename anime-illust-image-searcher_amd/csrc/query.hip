@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "rank_util.h"
+#include "topk.h"
 #include "../../include/hip_tagsearch_debug.h"
 
 using namespace hipts;
@@ -366,16 +367,6 @@ __global__ __launch_bounds__(1024) void rowmax_kernel(const T* __restrict__ v, i
     if (threadIdx.x == 0) out[blockIdx.x] = m;
 }
 
-// webui.py:377-383 (and :208 with norm flags off):
-//   out = wa * (a / max_a) + (double)((float)wb * (b / max_b))
-// The one statement of it: the batched combine, the fused top-k and the one-query kernels all call this.  A maximum <= 0 (or absent:
-// pass 0) means "do not divide".
-__device__ __forceinline__ double combine_score(double A, float B, double max_a, float max_b, double wa, float wb) {
-    if (max_a > 0.0) A = A / max_a;               // webui.py:379-380
-    if (max_b > 0.0f) B = B / max_b;              // webui.py:377-378
-    const float wB = wb * B;                      // python float * float32 array stays float32
-    return wa * A + (double)wB;                   // webui.py:383
-}
 __global__ __launch_bounds__(256) void combine_kernel(const double* __restrict__ a, const float* __restrict__ b, int64_t n,
                                                       double wa, float wb, const double* __restrict__ max_a,
                                                       const float* __restrict__ max_b, const uint32_t* __restrict__ max_b_keys,
@@ -653,634 +644,6 @@ __global__ __launch_bounds__(256) void retile_kernel(const float* __restrict__ r
 }
 
 // =============================================================================================
-// top-k by (value descending, index ascending): one workgroup per query.
-// MSB-first radix select over an order-preserving u64 image of the float64 value (12-bit digits,
-// LDS histogram), early exit once the survivors fit the LDS candidate buffer, then a bitonic
-// sort of the candidates.  Exact for ties (ordered gather of the lowest indices).
-// =============================================================================================
-constexpr int TOPK_CAP = 2048;
-constexpr int TOPK_MAX_K = 1024;
-
-__device__ __forceinline__ uint64_t order_key(double x) {
-    if (x == 0.0) x = 0.0;   // -0.0 and +0.0 compare equal in the reference's sort
-    uint64_t u = (uint64_t)__double_as_longlong(x);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_value(uint64_t k) {
-    uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)u);
-}
-
-// Monotone (non-decreasing) 12-bit digit of a score, uniform in VALUE over [-2, 2): the fast path of the
-// top-k histograms on it.  Everything below -2 (and NaN) is digit 0, everything from 2 up is 4095.
-__device__ __forceinline__ uint32_t value_digit(double x) {
-    const double t = (x + 2.0) * 1024.0;
-    return t >= 4095.0 ? 4095u : (t > 0.0 ? (uint32_t)t : 0u);
-}
-
-// Histogram increment that survives concentration: when many lanes of a wave hold the SAME digit (ties: every
-// document a required term excludes scores -inf; exponent digits of like-sized scores) plain LDS atomics
-// serialise on one address.  The lanes that share the first active lane's digit are counted with one ballot
-// and added once; the remaining lanes add individually.
-__device__ __forceinline__ void hist_add(uint32_t* hist, uint32_t d, bool active) {
-    const uint64_t act = __ballot(active);
-    if (act == 0) return;
-    const int leader = __ffsll((unsigned long long)act) - 1;
-    const uint32_t dl = __shfl(d, leader);
-    const uint64_t same = __ballot(active && d == dl);
-    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&hist[dl], (uint32_t)__popcll(same));
-    else if (active && d != dl) atomicAdd(&hist[d], 1u);
-}
-
-// A workgroup streams its query's scores several times; each pass is bound by load latency x loads in flight,
-// so every thread keeps TOPK_U independent 8-byte loads outstanding (128 KB per workgroup).
-constexpr int TOPK_U = 16;
-constexpr int TOPK_SORT_TARGET = 256;
-
-struct Search1State;
-struct Search1Witness;
-__device__ void search1_state_clear(Search1State* st);
-__device__ void search1_state_debug(Search1State* st, uint32_t cnt, uint32_t fast);
-constexpr int S1_BLOCK_CAP = 64;     // candidates one search1_collect_kernel workgroup (1024 documents) may hand on: at least this many (search_one sizes it)
-constexpr int S1_GATHER_BLOCKS = 1024;  // up to this many workgroups' slots are gathered through an offset table in LDS
-
-#ifdef HIPTS_X_TOPK_STAMPS          // measurement-only build (tools/gpurun/r3_topk_stamps.sh): wall-clock stamps of workgroup 0, 10 ns units
-__device__ unsigned long long g_topk_stamps[16];
-#define TOPK_STAMP(i) do { __syncthreads(); if (blockIdx.x == HIPTS_X_TOPK_STAMPS && threadIdx.x == 0) g_topk_stamps[i] = wall_clock64(); } while (0)
-#else
-#define TOPK_STAMP(i) do { } while (0)
-#endif
-
-// The score rows as the two addends of webui.py:377-383 instead of their sum: with `a` set the kernel computes
-// wa * (a / max_a) + (double)(wb * (b / max_b)) (combine_score) wherever it reads a score,
-// and the batched search neither writes nor re-reads the combined rows (round 3: 20 B per score of traffic less, one launch less).
-struct TopkFused {
-    const double* a = nullptr;       // [nq][n] BM25 scores
-    const float* b = nullptr;        // [nq][n] index products
-    double wa = 0.0;
-    float wb = 0.f;
-    const double* max_a = nullptr;   // [nq] row maxima (normalise when > 0)
-    const float* max_b = nullptr;
-    const float* max_b_parts = nullptr;      // instead of max_b: [query / 256][SIMW_MAX_GRID][256] per-workgroup maxima of sim_mfma_wide_kernel,
-    int parts = 0;                           //   `parts` workgroups each
-};
-
-__global__ __launch_bounds__(1024) void topk_kernel(const double* __restrict__ vals, int64_t n, int k,
-                                                    int32_t* __restrict__ ids_out, double* __restrict__ vals_out,
-                                                    Search1State* __restrict__ pre = nullptr, const uint32_t* __restrict__ pre_cnt = nullptr,
-                                                    const uint32_t* __restrict__ pre_flag = nullptr, const unsigned long long* __restrict__ pre_key = nullptr,
-                                                    const uint32_t* __restrict__ pre_id = nullptr, int pre_blocks = 0,
-                                                    uint32_t* __restrict__ done_flag = nullptr, uint32_t done_seq = 0, int pre_cap = S1_BLOCK_CAP,
-                                                    const TopkFused fz = TopkFused()) {
-    __shared__ uint32_t hist[4096];
-    __shared__ uint64_t ckey[TOPK_CAP];
-    __shared__ uint32_t cid[TOPK_CAP];
-    __shared__ int scratch[17];
-    __shared__ int sh_digit, sh_need, sh_bin, sh_cnt;
-    __shared__ unsigned long long sh_z0;       // largest order key among the scores of digit 0 (fast path that has to dip into that bin)
-    __shared__ int soff[S1_GATHER_BLOCKS];
-    const int tid = threadIdx.x;
-    const bool fused = fz.a != nullptr;
-    const double* __restrict__ v = fused ? nullptr : vals + (int64_t)blockIdx.x * n;
-    const double* __restrict__ fa = fused ? fz.a + (int64_t)blockIdx.x * n : nullptr;
-    const float* __restrict__ fb = fused ? fz.b + (int64_t)blockIdx.x * n : nullptr;
-    const double f_ma = fused ? fz.max_a[blockIdx.x] : 0.0;
-    float f_mb = 0.f;
-    if (fused) {
-        if (fz.max_b_parts) {        // the maximum over the product kernel's workgroups (exact: the same value rowmax_kernel finds in the stored row)
-            const float* pp = fz.max_b_parts + (int64_t)(blockIdx.x >> 8) * (256 * 256) + (blockIdx.x & 255);
-            f_mb = block_max<1024>(tid < fz.parts ? pp[(int64_t)tid * 256] : -INFINITY);
-        } else {
-            f_mb = fz.max_b[blockIdx.x];
-        }
-    }
-    auto comb = [&](double A, float B) -> double { return combine_score(A, B, f_ma, f_mb, fz.wa, fz.wb); };
-    auto val = [&](int64_t i) -> double { return fused ? comb(fa[i], fb[i]) : v[i]; };
-    auto val2 = [&](int64_t i) -> double2 {              // scores i, i + 1 (i even, rows 16-byte aligned: `wide`)
-        if (fused) {
-            const double2 A = *reinterpret_cast<const double2*>(fa + i);
-            const float2 B = *reinterpret_cast<const float2*>(fb + i);
-            return make_double2(comb(A.x, B.x), comb(A.y, B.y));
-        }
-        return *reinterpret_cast<const double2*>(v + i);
-    };
-    if ((int64_t)k > n) k = (int)n;
-    // ---- fast path (measured: the exact radix select below spends ~200 us of a 233 us single-query call in the
-    // LDS atomics of its first histogram, 100 k of them).  Estimate the threshold from a 1/8 sample instead:
-    // histogram the sample over a VALUE-uniform 12-bit digit (scores are normalised sums in about [-1, 1], so
-    // the bins spread and the atomics do not pile up on a few exponents), pick the digit below which the sample
-    // holds ~k/8 + 3 sigma entries, and collect every score with digit >= that one.  The digit is monotone in
-    // the score, so the collected set is exactly "all scores >= a pivot": if it has at least k and at most CAP
-    // members it contains the top k and the sort below finishes the job; otherwise the exact path runs.
-    bool done_fast = false;
-    int fill_need = 0;        // results still missing after the candidates: the lowest-index -inf scores (candidate path only)
-    TOPK_STAMP(12);
-    if (pre) {
-        // Candidates handed on by search1_collect_kernel (per-workgroup slots): every score whose digit is at or above a threshold
-        // digit, i.e. all scores >= a pivot.  With at least k and at most CAP of them the top k are among them.  With fewer than
-        // k, and nothing but -inf below the pivot, they are ALL results and the rest are -inf ties in index order.
-        int mine = 0, bad = 0, other = 0;
-        for (int b = tid; b < pre_blocks; b += 1024) {
-            const int cb = (int)pre_cnt[b];
-            bad |= cb > pre_cap;
-            mine += cb > pre_cap ? pre_cap : cb;
-            other |= (int)pre_flag[b];
-        }
-        int c;
-        const int excl = block_excl_scan(mine, scratch, &c);
-        bad = __syncthreads_or(bad);
-        const bool only_inf_below = __syncthreads_or(other) == 0;
-        done_fast = !bad && c <= TOPK_CAP && (c >= k || only_inf_below);
-        if (done_fast && pre_blocks <= S1_GATHER_BLOCKS) {
-            // one thread per CANDIDATE: its workgroup by bisection of the offsets (a workgroup may hand on hundreds when k is a large
-            // part of a small index; a thread per workgroup copying them one by one took a round trip each)
-            if (tid < pre_blocks) soff[tid] = excl;
-            __syncthreads();
-            for (int j = tid; j < c; j += 1024) {
-                int lo = 0, hi = pre_blocks - 1;                   // last block whose offset is <= j
-                while (lo < hi) {
-                    const int mid = (lo + hi + 1) >> 1;
-                    if (soff[mid] <= j) lo = mid; else hi = mid - 1;
-                }
-                const int64_t src = (int64_t)lo * pre_cap + (j - soff[lo]);
-                ckey[j] = pre_key[src];
-                cid[j] = pre_id[src];
-            }
-            if (tid == 0) sh_cnt = c;
-            if (c < k) fill_need = k - c;
-        } else if (done_fast) {
-            int off = excl;
-            for (int b = tid; b < pre_blocks; b += 1024) {
-                const int cb = (int)pre_cnt[b];
-                for (int i = 0; i < cb; ++i) {
-                    ckey[off + i] = pre_key[(int64_t)b * pre_cap + i];
-                    cid[off + i] = pre_id[(int64_t)b * pre_cap + i];
-                }
-                off += cb;
-            }
-            if (tid == 0) sh_cnt = c;
-            if (c < k) fill_need = k - c;
-        }
-        __syncthreads();
-        TOPK_STAMP(13);
-        search1_state_clear(pre);               // the maxima slots are zero again for the next query (search1_combine_kernel has read them)
-        search1_state_debug(pre, (uint32_t)c, done_fast ? 1u : 0u);
-    }
-    TOPK_STAMP(0);
-    if (!done_fast && n >= 8192) {
-        for (int i = tid; i < 4096; i += 1024) hist[i] = 0;
-        if (tid == 0) sh_cnt = 0;
-        __syncthreads();
-        // the first 1024 of every 8192 scores; TOPK_U loads per thread in flight (one load per step made the sample a chain of ~13
-        // dependent round trips for 100 k scores: ~25 us of the kernel's ~80 per workgroup)
-        // 16-byte loads where the row allows it (even length, 16-byte aligned): 8-byte loads reach about 0.6 of the 16-byte rate on this
-        // part (MI355X_MICROARCH.md, "8-B accesses 0.54-0.70x the 16-B rate"), and both passes of the fast path are pure streams
-        const bool wide = (n & 1) == 0 && (fused ? ((reinterpret_cast<uintptr_t>(fa) & 15) == 0 && (reinterpret_cast<uintptr_t>(fb) & 7) == 0)
-                                                 : (reinterpret_cast<uintptr_t>(v) & 15) == 0);
-        constexpr int UW = TOPK_U / 2;
-        uint32_t smax = 0u;
-        bool shave = false;
-        if (wide) {
-            // the first 2048 of every 16384 scores (the same 1/8 sample)
-            for (int64_t base0 = 0; base0 < n; base0 += (int64_t)UW * 16384) {
-                double2 sx[UW];
-#pragma unroll
-                for (int u = 0; u < UW; ++u) {
-                    const int64_t i = base0 + (int64_t)u * 16384 + 2 * tid;
-                    sx[u] = i < n ? val2(i) : make_double2(0.0, 0.0);
-                }
-#pragma unroll
-                for (int u = 0; u < UW; ++u) {
-                    const int64_t i = base0 + (int64_t)u * 16384 + 2 * tid;
-                    if (i < n) {
-                        const uint32_t d0 = value_digit(sx[u].x), d1 = value_digit(sx[u].y);
-                        smax = max(smax, max(d0, d1));
-                        shave = true;
-                    }
-                }
-            }
-        } else
-        for (int64_t base0 = 0; base0 < n; base0 += (int64_t)TOPK_U * 8192) {
-            double sx[TOPK_U];
-#pragma unroll
-            for (int u = 0; u < TOPK_U; ++u) {
-                const int64_t i = base0 + (int64_t)u * 8192 + tid;
-                sx[u] = i < n ? val(i) : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < TOPK_U; ++u) {
-                const int64_t i = base0 + (int64_t)u * 8192 + tid;
-                if (i < n) {
-                    smax = max(smax, value_digit(sx[u]));
-                    shave = true;
-                }
-            }
-        }
-        // ONE histogram entry per thread: the largest digit among its ~12 samples.  The number of samples at or above a digit is at least
-        // the number of thread maxima there, so the digit chosen below still leaves >= `want` samples above it (a few more when two of a
-        // thread's samples qualify: 0.6 expected at k = 100, +9 % at k = 1024) -- and the histogram takes 1 k LDS atomics instead of 12.5 k
-        // spread over 4096 bins (12 us of the kernel's 77 at k = 100: tools/topk_k.py, tools/topk_cases.py).
-        TOPK_STAMP(1);
-        hist_add(hist, smax, shave);
-        __syncthreads();
-        TOPK_STAMP(2);
-        const int want = k / 8 + 3 * (int)ceilf(sqrtf((float)k / 8.0f)) + 4;
-        int own[4], ssum = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            own[j] = (int)hist[4095 - (4 * tid + j)];
-            ssum += own[j];
-        }
-        int total;
-        const int excl = block_excl_scan(ssum, scratch, &total);
-        if (tid == 0) sh_digit = 0;                              // fewer sampled entries than `want`: take everything
-        __syncthreads();
-        if (excl < want && want <= excl + ssum) {
-            int run = excl;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (run < want && want <= run + own[j]) sh_digit = 4095 - (4 * tid + j);
-                run += own[j];
-            }
-        }
-        __syncthreads();
-        // The sample holds fewer than `want` entries above digit 0 when a required term has left most of the row -inf (digit 0): the top k
-        // then reach into that bin.  Round 2 took "everything", overflowed the candidate buffer and fell to the exact radix select -- six
-        // passes, 130-200 us for a row with fewer than ~300 finite scores, and the slowest row sets the launch time (measured:
-        // tools/topk_cases.py).  Now: collect everything ABOVE digit 0 and look at what the bin holds; if nothing but -inf (the common case),
-        // the candidates are all results and the rest are -inf ties in index order (the ordered fill at the end of the kernel).
-        TOPK_STAMP(3);
-        const bool dip = sh_digit == 0;
-        const uint32_t dmin = dip ? 1u : (uint32_t)sh_digit;
-        if (tid == 0) sh_z0 = 0ull;
-        __syncthreads();
-        unsigned long long z0 = 0ull;
-        // the next step's TOPK_U loads are requested before this step's values are examined (two register sets): the pass was a chain of
-        // load round trips, one per 16 k scores
-        // Candidates go into the wave's OWN 128 slots of ckey / cid, placed by ballot and a wave-uniform count -- no atomics: ~250 adds on
-        // one LDS counter were 14 us of the kernel at k = 100.  A wave whose slots are full (skewed rows, k = 1024) appends to an overflow
-        // list that lives in the histogram's memory (free now) through a shared counter; the lists are packed below.
-        constexpr int WSLOTS = TOPK_CAP / 16, OVCAP = 1024;
-        uint64_t* ovk = reinterpret_cast<uint64_t*>(hist);                  // 8 KB
-        uint32_t* ovi = hist + 2 * OVCAP;                                   // 4 KB behind it
-        const int wv = tid >> 6, ln = tid & 63;
-        int wcnt = 0;
-        __syncthreads();                                                    // every thread has read its bins of the histogram
-        auto examine = [&](double xv, int64_t i) {
-            const bool c = i < n && value_digit(xv) >= dmin;
-            const unsigned long long m = __ballot(c);
-            if (m) {
-                if (c) {
-                    const int pos = wcnt + __popcll(m & ((1ull << ln) - 1ull));
-                    if (pos < WSLOTS) {
-                        ckey[wv * WSLOTS + pos] = order_key(xv);
-                        cid[wv * WSLOTS + pos] = (uint32_t)i;
-                    } else {
-                        const int slot = atomicAdd(&sh_cnt, 1);
-                        if (slot < OVCAP) {
-                            ovk[slot] = order_key(xv);
-                            ovi[slot] = (uint32_t)i;
-                        }
-                    }
-                }
-                wcnt += __popcll(m);
-            }
-            if (!c && dip && i < n) {
-                const unsigned long long kx = order_key(xv);
-                z0 = kx > z0 ? kx : z0;
-            }
-        };
-        if (wide) {
-            double2 x[UW], xn[UW];
-#pragma unroll
-            for (int u = 0; u < UW; ++u) {
-                const int64_t i = (int64_t)u * 2048 + 2 * tid;
-                x[u] = i < n ? val2(i) : make_double2(-INFINITY, -INFINITY);
-            }
-            for (int64_t i0 = 0; i0 < n; i0 += UW * 2048) {
-                const int64_t i1 = i0 + UW * 2048;
-#pragma unroll
-                for (int u = 0; u < UW; ++u) {
-                    const int64_t i = i1 + u * 2048 + 2 * tid;
-                    xn[u] = i < n ? val2(i) : make_double2(-INFINITY, -INFINITY);
-                }
-#pragma unroll
-                for (int u = 0; u < UW; ++u) {
-                    const int64_t i = i0 + u * 2048 + 2 * tid;
-                    examine(x[u].x, i);
-                    examine(x[u].y, i + 1);
-                }
-#pragma unroll
-                for (int u = 0; u < UW; ++u) x[u] = xn[u];
-            }
-        } else {
-        double x[TOPK_U], xn[TOPK_U];
-#pragma unroll
-        for (int u = 0; u < TOPK_U; ++u) {
-            const int64_t i = (int64_t)u * 1024 + tid;
-            x[u] = i < n ? val(i) : -INFINITY;
-        }
-        for (int64_t i0 = 0; i0 < n; i0 += TOPK_U * 1024) {
-            const int64_t i1 = i0 + TOPK_U * 1024;
-#pragma unroll
-            for (int u = 0; u < TOPK_U; ++u) {
-                const int64_t i = i1 + u * 1024 + tid;
-                xn[u] = i < n ? val(i) : -INFINITY;
-            }
-#pragma unroll
-            for (int u = 0; u < TOPK_U; ++u) examine(x[u], i0 + u * 1024 + tid);
-#pragma unroll
-            for (int u = 0; u < TOPK_U; ++u) x[u] = xn[u];
-        }
-        }
-        if (dip) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const unsigned long long other = __shfl_xor(z0, o);
-                z0 = other > z0 ? other : z0;
-            }
-            if ((tid & 63) == 0) atomicMax(&sh_z0, z0);
-        }
-        TOPK_STAMP(4);
-        // pack the sixteen wave lists and the overflow list into ckey / cid [0, total): through registers (source and destination overlap)
-        if (ln == 0) scratch[wv] = wcnt < WSLOTS ? wcnt : WSLOTS;
-        __syncthreads();
-        {
-            const int nov = sh_cnt;                                         // entries the waves tried to append to the overflow list
-            int off[17];
-            off[0] = 0;
-#pragma unroll
-            for (int w = 0; w < 16; ++w) off[w + 1] = off[w] + scratch[w];
-            const int total = off[16] + (nov < OVCAP ? nov : OVCAP);
-            uint64_t mk[3];
-            uint32_t mi[3];
-            int md[3];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {                                    // wave-list slots tid and tid + 1024
-                const int sl = tid + e * 1024, w = sl / WSLOTS, j = sl - w * WSLOTS;
-                md[e] = j < scratch[w] ? off[w] + j : -1;
-                mk[e] = ckey[sl];
-                mi[e] = cid[sl];
-            }
-            md[2] = tid < nov && tid < OVCAP ? off[16] + tid : -1;           // overflow slot tid
-            mk[2] = ovk[tid];
-            mi[2] = ovi[tid];
-            __syncthreads();
-#pragma unroll
-            for (int e = 0; e < 3; ++e)
-                if (md[e] >= 0 && md[e] < TOPK_CAP) {
-                    ckey[md[e]] = mk[e];
-                    cid[md[e]] = mi[e];
-                }
-            __syncthreads();
-            if (tid == 0) sh_cnt = nov > OVCAP ? TOPK_CAP + 1 : total;      // an overflowing overflow list: not a fast-path row
-        }
-        __syncthreads();
-        if (dip) {
-            // digit 0 empty (z0 == 0: every score was collected) or nothing but -inf in it
-            done_fast = sh_cnt <= TOPK_CAP && (sh_z0 == 0ull || sh_z0 == order_key(-INFINITY));
-            if (done_fast && sh_cnt < k) fill_need = k - sh_cnt;
-        } else {
-            done_fast = sh_cnt >= k && sh_cnt <= TOPK_CAP;
-        }
-        __syncthreads();
-    }
-    TOPK_STAMP(5);
-    uint64_t prefix = 0;
-    int pbits = 0;
-    int need = k;            // how many of the keys matching `prefix` are still wanted
-    bool fits = done_fast;
-    const int shifts[6] = {52, 40, 28, 16, 4, 0};
-    for (int pass = 0; pass < 6 && !fits; ++pass) {
-        const int shift = shifts[pass];
-        const int dbits = pass == 5 ? 4 : 12;
-        for (int i = tid; i < 4096; i += 1024) hist[i] = 0;
-        __syncthreads();
-        for (int64_t i0 = 0; i0 < n; i0 += TOPK_U * 1024) {
-            uint64_t key[TOPK_U];
-#pragma unroll
-            for (int u = 0; u < TOPK_U; ++u) {
-                const int64_t i = i0 + u * 1024 + tid;
-                key[u] = i < n ? order_key(val(i)) : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < TOPK_U; ++u) {
-                const int64_t i = i0 + u * 1024 + tid;
-                hist_add(hist, (uint32_t)(key[u] >> shift) & ((1u << dbits) - 1), i < n && (pbits == 0 || (key[u] >> (64 - pbits)) == prefix));
-            }
-        }
-        __syncthreads();
-        // walk bins from the top: thread t owns reversed bins 4t..4t+3
-        int own[4], s = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            own[j] = (int)hist[4095 - (4 * tid + j)];
-            s += own[j];
-        }
-        int total;
-        int excl = block_excl_scan(s, scratch, &total);
-        if (excl < need && need <= excl + s) {
-            int run = excl;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (run < need && need <= run + own[j]) {
-                    sh_digit = 4095 - (4 * tid + j);
-                    sh_need = need - run;
-                    sh_bin = own[j];
-                }
-                run += own[j];
-            }
-        }
-        __syncthreads();
-        prefix = (prefix << dbits) | (uint64_t)(sh_digit & ((1 << dbits) - 1));
-        pbits += dbits;
-        const int above = k - sh_need;          // keys strictly above the chosen bin (all wanted)
-        need = sh_need;
-        // stop refining once the candidate set is small enough to SORT cheaply: the final bitonic sort costs
-        // log^2 barriers (2048 candidates = 66 stages ~ 100 us, 256 = 36), a further pass over the scores ~15 us;
-        // past the last digit (64 bits) whatever fits the LDS buffers is taken
-        fits = above + sh_bin <= (pbits < 64 ? max(TOPK_SORT_TARGET, k + 64) : TOPK_CAP);
-        __syncthreads();
-        if (pass == 0 && !fits && sh_bin > TOPK_CAP) {
-            // A first bin with more members than the buffers hold is usually one value repeated (every document
-            // a required term rules out scores -inf).  One pass decides: if the smallest and the largest key
-            // in the bin agree, the remaining five digit passes are known in advance.
-            uint64_t mn = ~0ull, mx = 0ull;
-            for (int64_t i = tid; i < n; i += 1024) {
-                const uint64_t key = order_key(val(i));
-                if ((key >> (64 - pbits)) == prefix) {
-                    mn = key < mn ? key : mn;
-                    mx = key > mx ? key : mx;
-                }
-            }
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-                const uint64_t a = __shfl_xor(mn, o), b = __shfl_xor(mx, o);
-                mn = a < mn ? a : mn;
-                mx = b > mx ? b : mx;
-            }
-            if ((tid & 63) == 0) {
-                ckey[tid >> 6] = mn;
-                ckey[16 + (tid >> 6)] = mx;
-            }
-            __syncthreads();
-            mn = ckey[0];
-            mx = ckey[16];
-            for (int w = 1; w < 16; ++w) {
-                mn = ckey[w] < mn ? ckey[w] : mn;
-                mx = ckey[16 + w] > mx ? ckey[16 + w] : mx;
-            }
-            __syncthreads();
-            if (mn == mx) {
-                prefix = mn;
-                pbits = 64;
-                break;              // fits stays false: the ordered tie compaction below takes the `need` lowest indices
-            }
-        }
-    }
-    const uint64_t low = pbits == 64 ? prefix : (prefix << (64 - pbits));
-    if (!done_fast) {
-    if (tid == 0) sh_cnt = 0;
-    __syncthreads();
-    if (fits) {
-        for (int64_t i0 = 0; i0 < n; i0 += TOPK_U * 1024) {
-            uint64_t key[TOPK_U];
-#pragma unroll
-            for (int u = 0; u < TOPK_U; ++u) {
-                const int64_t i = i0 + u * 1024 + tid;
-                key[u] = i < n ? order_key(val(i)) : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < TOPK_U; ++u) {
-                const int64_t i = i0 + u * 1024 + tid;
-                if (i < n && key[u] >= low) {
-                    const int slot = atomicAdd(&sh_cnt, 1);
-                    ckey[slot] = key[u];
-                    cid[slot] = (uint32_t)i;
-                }
-            }
-        }
-        __syncthreads();
-    } else {
-        // pbits == 64 and more than CAP exact ties at the threshold: everything above it, then the
-        // `need` lowest indices among the ties (ordered compaction).
-        for (int64_t i = tid; i < n; i += 1024) {
-            const uint64_t key = order_key(val(i));
-            if (key > low) {
-                const int slot = atomicAdd(&sh_cnt, 1);
-                ckey[slot] = key;
-                cid[slot] = (uint32_t)i;
-            }
-        }
-        __syncthreads();
-        int base = sh_cnt, taken = 0;
-        for (int64_t i0 = 0; i0 < n && taken < need; i0 += 1024) {
-            const int64_t i = i0 + tid;
-            const int flag = (i < n && order_key(val(i)) == low) ? 1 : 0;
-            int total;
-            const int excl = block_excl_scan(flag, scratch, &total);
-            if (flag && taken + excl < need) {
-                ckey[base + taken + excl] = low;
-                cid[base + taken + excl] = (uint32_t)i;
-            }
-            taken += total;
-        }
-        __syncthreads();
-        if (tid == 0) sh_cnt = base + (taken < need ? taken : need);
-        __syncthreads();
-    }
-    }
-    const int cnt = sh_cnt;
-    const int kout = cnt < k ? cnt : k;
-    TOPK_STAMP(6);
-    if (cnt <= 640) {
-        // few candidates: rank by counting -- rank(i) = #{j : j before i in (key desc, id asc)} -- no barriers, LDS broadcasts
-        // P adjacent lanes (as many as 1024 threads allow) share a candidate, each counting over every P-th entry (one thread per candidate walked the whole list as a
-        // chain of LDS round trips: 26 us of the workgroup's 67 at k = 100 -- tools/topk_stamps.py); partial ranks meet by lane swaps
-        __syncthreads();
-        const int P = cnt <= 64 ? 16 : cnt <= 128 ? 8 : cnt <= 256 ? 4 : cnt <= 512 ? 2 : 1;
-        const int c = tid / P, part = tid - c * P;
-        const bool live = c < cnt;
-        const uint64_t ki = live ? ckey[c] : 0ull;
-        const uint32_t ii = live ? cid[c] : 0u;
-        int rank = 0;
-        if (live) {
-#pragma unroll 4
-            for (int j = part; j < cnt; j += P) {
-                const uint64_t kj = ckey[j];
-                const uint32_t ij = cid[j];
-                rank += (kj > ki || (kj == ki && ij < ii)) ? 1 : 0;
-            }
-        }
-        if (P >= 2) rank += __shfl_xor(rank, 1);
-        if (P >= 4) rank += __shfl_xor(rank, 2);
-        if (P >= 8) rank += __shfl_xor(rank, 4);
-        if (P >= 16) rank += __shfl_xor(rank, 8);
-        if (live && part == 0 && rank < kout) {
-            ids_out[(int64_t)blockIdx.x * k + rank] = (int32_t)ii;
-            vals_out[(int64_t)blockIdx.x * k + rank] = key_value(ki);
-        }
-    } else {
-        int np2 = 64;
-        while (np2 < cnt) np2 <<= 1;
-        for (int i = cnt + tid; i < np2; i += 1024) {
-            ckey[i] = 0;
-            cid[i] = 0xffffffffu;
-        }
-        __syncthreads();
-        // bitonic sort, "greater first": (key desc, id asc)
-        for (int size = 2; size <= np2; size <<= 1) {
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                for (int t = tid; t < (np2 >> 1); t += 1024) {
-                    const int lo = ((t / stride) * stride * 2) + (t % stride);
-                    const int hi = lo + stride;
-                    const bool desc = ((lo & size) == 0);
-                    const uint64_t ka = ckey[lo], kb = ckey[hi];
-                    const uint32_t ia = cid[lo], ib = cid[hi];
-                    const bool a_first = (ka > kb) || (ka == kb && ia < ib);
-                    if (a_first != desc) {
-                        ckey[lo] = kb; ckey[hi] = ka;
-                        cid[lo] = ib; cid[hi] = ia;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        for (int i = tid; i < kout; i += 1024) {
-            ids_out[(int64_t)blockIdx.x * k + i] = (int32_t)cid[i];
-            vals_out[(int64_t)blockIdx.x * k + i] = key_value(ckey[i]);
-        }
-    }
-    TOPK_STAMP(7);
-    if (fill_need > 0) {
-        // the remaining results are -inf scores in ascending index order (ordered compaction; stops as soon as enough are found)
-        const uint64_t ninf = order_key(-INFINITY);
-        int taken = 0;
-        for (int64_t i0 = 0; i0 < n && taken < fill_need; i0 += 1024) {
-            const int64_t i = i0 + tid;
-            const int flag = (i < n && order_key(val(i)) == ninf) ? 1 : 0;
-            int total;
-            const int excl = block_excl_scan(flag, scratch, &total);
-            if (flag && taken + excl < fill_need) {
-                ids_out[(int64_t)blockIdx.x * k + cnt + taken + excl] = (int32_t)i;
-                vals_out[(int64_t)blockIdx.x * k + cnt + taken + excl] = -INFINITY;
-            }
-            taken += total;
-        }
-    }
-    TOPK_STAMP(14);
-    if (done_flag) {
-        // The results above went to pinned host memory.  Publish them to the HOST without waiting for the runtime's completion
-        // signal (a hipStreamSynchronize wake-up costs ~10 us): every storing thread fences at system scope, the workgroup meets,
-        // one lane releases the sequence number the host is spinning on.
-        __threadfence_system();
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(done_flag, done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    TOPK_STAMP(15);
-}
-
-// =============================================================================================
 // One query at a time -- the reference's real call (webui.py:586: find_similar_documents(query, topn=800)).
 // The batched kernels above give one workgroup to a query for BM25, the row maxima and the top-k: at nq = 1 that is
 // one CU of 256 busy for ~120 of the ~170 us a query took.  Here every step runs over the whole chip, thread per
@@ -1326,17 +689,6 @@ struct Search1Witness {          // 32 B per wave of search1_score_kernel (64 do
     double bm_b;                 // the BM25 score of the document with ...
     float sim_b, pad1;           // ... the wave's largest index product
 };
-
-__device__ void search1_state_clear(Search1State* st) {
-    uint32_t* w = reinterpret_cast<uint32_t*>(st);
-    for (int i = threadIdx.x; i < (int)(offsetof(Search1State, dbg) / 4); i += blockDim.x) w[i] = 0;
-}
-__device__ void search1_state_debug(Search1State* st, uint32_t cnt, uint32_t fast) {
-    if (threadIdx.x == 0) {
-        st->dbg[0] = cnt;
-        st->dbg[1] = fast;
-    }
-}
 
 // PIPE (round 5, the default; HIPTS_S1_PIPE=0 runs the sequential form): the BM25 part is a chain of dependent round trips -- the span's
 // bounds, its term ids (up to 12 passes of four loads -> LDS, each a round trip of its own), the matches' tf, the idf values -- about 12 of
@@ -1714,7 +1066,6 @@ constexpr int S1_COLLECT_THREADS = 1024;
 struct S1HandOn {                // LDS of one workgroup of search1_collect_kernel / search1_finish_kernel
     uint32_t hist[4096];
     int scan[17];
-    int dmin;
     uint32_t n, other;
 };
 
@@ -1737,28 +1088,8 @@ __device__ __forceinline__ uint32_t s1_threshold_digit(S1HandOn& sh, int groups,
         hist_add(sh.hist, dg, dg != 0u);
     }
     __syncthreads();
-    // walk the bins from the top: thread t owns reversed bins 4t .. 4t + 3
-    int own[4], ssum = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int bin = 4095 - (4 * tid + j);
-        own[j] = bin >= 1 ? (int)sh.hist[bin] : 0;
-        ssum += own[j];
-    }
-    int total;
-    const int excl = block_excl_scan(ssum, sh.scan, &total);
-    if (tid == 0) sh.dmin = 1;
-    __syncthreads();
-    if (excl < k && k <= excl + ssum) {
-        int run = excl;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (run < k && k <= run + own[j]) sh.dmin = 4095 - (4 * tid + j);
-            run += own[j];
-        }
-    }
-    __syncthreads();
-    return (uint32_t)sh.dmin;
+    const int digit = find_bin_from_top(sh.hist, k, sh.scan, 1).digit;
+    return digit < 0 ? 1u : (uint32_t)digit;
 }
 
 // Document d (score f) is a candidate if its digit is at or above the threshold: the candidates go to this workgroup's own slots (LDS
@@ -1899,6 +1230,13 @@ struct hipts_index {
 };
 
 namespace {
+
+// topk_kernel's score source for plain rows, [nq][n]
+TopkScores plain_rows(const double* v) {
+    TopkScores sc;
+    sc.v = v;
+    return sc;
+}
 
 // HIPTS_SIM_PARTS=0: the batched search takes the index products' row maxima with rowmax_kernel again (A/B; default: from the accumulators)
 bool sim_parts_enabled() {
@@ -2162,7 +1500,20 @@ int search_one(hipts_bm25* bm25, hipts_index* index, const int32_t* q_terms, con
     }
     {
         QueryProfScope ps(bm25, s, QP_S1_TOPK, (double)kk * 24.0);
-        topk_kernel<<<1, 1024, 0, s>>>(final_dev, D, kk, oi, ov, st, bcnt, bflag, bkey, bid, blocks3, use_flag ? flag : nullptr, seq, bcap);
+        TopkHandOn hand;
+        hand.clear = reinterpret_cast<uint32_t*>(st);                  // the maxima slots, up to dbg
+        hand.clear_words = (int)(offsetof(Search1State, dbg) / 4);
+        hand.dbg = hand.clear + hand.clear_words;
+        hand.counts = bcnt;
+        hand.flags = bflag;
+        hand.keys = bkey;
+        hand.ids = bid;
+        hand.blocks = blocks3;
+        hand.cap = bcap;
+        TopkPublish pub;
+        pub.flag = use_flag ? flag : nullptr;
+        pub.seq = seq;
+        topk_kernel<<<1, 1024, 0, s>>>(plain_rows(final_dev), D, kk, oi, ov, hand, pub);
         HIPTS_LAUNCH_CHECK();
     }
     bm25->s1_dirty = false;
@@ -2600,7 +1951,7 @@ int hipts_topk(const double* vals, int nq, int64_t n, int k, int32_t* ids_out, d
     const int kk = (int)std::min<int64_t>(k, n);
     if (out_memspace == HIPTS_DEVICE) {
         HIPTS_REQUIRE(kk == k, "hipts_topk: k > n needs host outputs");
-        topk_kernel<<<nq, 1024, 0, s>>>(vals, n, k, ids_out, vals_out);
+        topk_kernel<<<nq, 1024, 0, s>>>(plain_rows(vals), n, k, ids_out, vals_out);
         HIPTS_LAUNCH_CHECK();
         return HIPTS_OK;
     }
@@ -2608,7 +1959,7 @@ int hipts_topk(const double* vals, int nq, int64_t n, int k, int32_t* ids_out, d
     HIPTS_TRY(obuf.reserve((size_t)nq * kk * 12 + 64));
     double* ov = obuf.as<double>();
     int32_t* oi = reinterpret_cast<int32_t*>(ov + (size_t)nq * kk);
-    topk_kernel<<<nq, 1024, 0, s>>>(vals, n, kk, oi, ov);
+    topk_kernel<<<nq, 1024, 0, s>>>(plain_rows(vals), n, kk, oi, ov);
     HIPTS_LAUNCH_CHECK();
     std::vector<int32_t> hi((size_t)nq * kk);
     std::vector<double> hv((size_t)nq * kk);
@@ -2702,7 +2053,7 @@ static int search_submit_impl(hipts_bm25_t* bm25, hipts_index_t* index, const in
     const float* qvec = reinterpret_cast<const float*>(bm25->ws_q.as<char>() + off_v);
     HIPTS_TRY(bm25->ws_scores.reserve((size_t)nq * D * 8));
     HIPTS_TRY(bm25->ws_sims.reserve((size_t)nq * D * 4));
-    // Without a caller who wants the combined rows they are never written: the top-k kernel combines on the fly (TopkFused;
+    // Without a caller who wants the combined rows they are never written: the top-k kernel combines on the fly (TopkScores::a;
     // HIPTS_SEARCH_FUSED_TOPK=0 restores combine_kernel + top-k over the stored rows, for A/B).
     static const bool fuse_topk = !(getenv("HIPTS_SEARCH_FUSED_TOPK") && atoi(getenv("HIPTS_SEARCH_FUSED_TOPK")) == 0);
     const bool fused = fuse_topk && final_out_device == nullptr;
@@ -2772,7 +2123,7 @@ static int search_submit_impl(hipts_bm25_t* bm25, hipts_index_t* index, const in
     {
         QueryProfScope ps(bm25, s, QP_TOPK, (double)nq * D * (fused ? 12.0 : 8.0));
         if (fused) {
-            TopkFused fz;
+            TopkScores fz;                       // the two addends, combined where the kernel reads them
             fz.a = bm25->ws_scores.as<double>();
             fz.b = bm25->ws_sims.as<float>();
             fz.wa = w_bm25;
@@ -2784,9 +2135,9 @@ static int search_submit_impl(hipts_bm25_t* bm25, hipts_index_t* index, const in
                 fz.max_b_parts = bm25->ws_parts.as<float>();
                 fz.parts = parts_grid;
             }
-            topk_kernel<<<nq, 1024, 0, s>>>(nullptr, D, kk, oi, ov, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0u, S1_BLOCK_CAP, fz);
+            topk_kernel<<<nq, 1024, 0, s>>>(fz, D, kk, oi, ov);
         } else {
-            topk_kernel<<<nq, 1024, 0, s>>>(final_dev, D, kk, oi, ov);
+            topk_kernel<<<nq, 1024, 0, s>>>(plain_rows(final_dev), D, kk, oi, ov);
         }
         HIPTS_LAUNCH_CHECK();
     }

@@ -155,7 +155,7 @@ def test_config2_100k_docs_top100_rank_equal(corpus100k):
 
 def test_config2_benched_shape_256_queries_fused_topk(corpus100k):
     """The shape bench.py times -- 256 queries x 100k documents through ONE call without `final_out`: the one-pass index product
-    (sim_mfma_wide_kernel<8>) and the top-k that combines the scores where it reads them (TopkFused, no stored rows) -- checked
+    (sim_mfma_wide_kernel<8>) and the top-k that combines the scores where it reads them (TopkScores::a / b, no stored rows) -- checked
     DIRECTLY against the oracle (webui.py:345-383,191-192 restated), not through the stored-row form: ids and values of the top 100
     for 12 of the queries spread over the batch (the first, the last, one per query block of 32 and three more), byte-equal;
     and the whole batch against the stored-row form of the same call."""

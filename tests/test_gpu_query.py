@@ -259,12 +259,13 @@ def test_search_rank_equal(corpus20k):
         assert vals[i].tobytes() == wv.tobytes()
 
 
-@pytest.mark.parametrize("D,V", [(300, 60), (9000, 800), (20000, 2000)])
+@pytest.mark.parametrize("D,V", [(300, 60), (9000, 800), (9001, 800), (20000, 2000)])
 def test_search_without_stored_rows_equals_search_with_them(D, V):
     """hipts_search for a batch, final_out absent: the top-k kernel combines BM25 and index scores where it reads them (no combine launch,
     no stored rows).  Same ids and bit-identical scores as the call that stores the combined rows -- the form test_search_rank_equal pins to
     the oracle -- for k below / above the candidate capacity, plain / required / excluded terms, indexes below and above the fast path's
-    8192-document floor (the exact radix select reads its scores through the same expression)."""
+    8192-document floor (the exact radix select reads its scores through the same expression), an even and an odd row length
+    (16-byte and 8-byte loads of the two addends)."""
     import torch
     from hiptagsearch import synth
     from hiptagsearch.bm25 import BM25Index

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Development aid (gpurun only): hipts_topk (batched, 256 queries x 100 k scores, k = 100) by kind of score row -- all finite, or all but
+"""Development aid (needs the GPU): hipts_topk (batched, 256 queries x 100 k scores, k = 100 or argv[1]) by kind of score row -- all finite, or all but
 N finite scores -inf (what a required term leaves) -- to see which rows set the launch time (one workgroup per query, one round)."""
 import ctypes, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "anime-illust-image-searcher_amd"))
 import numpy as np, torch
 from hiptagsearch import _lib
-NQ, D, K = 256, 100_000, 100
+NQ, D, K = 256, 100_000, int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = np.random.default_rng(0)
 ids = torch.empty((NQ, K), dtype=torch.int32, device="cuda"); vals = torch.empty((NQ, K), dtype=torch.float64, device="cuda")
 def run(name, rows):
