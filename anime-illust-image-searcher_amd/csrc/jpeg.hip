@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "jpeg_slot.h"
+#include "png.h"
 
 #include "../../include/hip_tagsearch.h"
 
@@ -296,28 +297,40 @@ extern "C" int hipts_jpeg_decode_rgb(const void* slot, int64_t slot_bytes, uint8
     return HIPTS_OK;
 }
 
-extern "C" int hipts_jpeg_batch_u8(const uint8_t* slots, int64_t slot_stride, const int32_t* kinds, const int32_t* hw, int n, int pad_square,
-                                   uint8_t* dst_device, int size, int filter, int device, void* stream) {
-    HIPTS_REQUIRE(slots && kinds && hw && dst_device && n >= 1 && size >= 1 && slot_stride >= HIPTS_JPEG_HEADER_BYTES, "hipts_jpeg_batch_u8: bad arguments");
-    HIPTS_REQUIRE(device >= 0 && device < 64, "hipts_jpeg_batch_u8: device index");
+namespace {
+
+// The batch entries: ring slots of kinds 0 (decoded RGB), 1 (JPEG coefficient blocks) and -- `png` -- 2 (filtered PNG scanlines) ->
+// the decoded images side by side in device memory -> hipts_resize_batch_u8.
+int decode_batch(const char* who, bool png, const uint8_t* slots, int64_t slot_stride, const int32_t* kinds, const int32_t* hw, int n, int pad_square,
+                 uint8_t* dst_device, int size, int filter, int device, void* stream) {
+    HIPTS_REQUIRE(slots && kinds && hw && dst_device && n >= 1 && size >= 1 && slot_stride >= HIPTS_JPEG_HEADER_BYTES, "%s: bad arguments", who);
+    HIPTS_REQUIRE(device >= 0 && device < 64, "%s: device index", who);
     std::vector<JpegImage> ims((size_t)n);
+    std::vector<PngImage> pngs;
     std::vector<size_t> stage_off((size_t)n), plane_off((size_t)n);
     size_t stage_total = 0, plane_total = 0, rgb_stride = 0;
     for (int i = 0; i < n; ++i) {
         const int h = hw[2 * i], w = hw[2 * i + 1];
-        HIPTS_REQUIRE(h >= 1 && w >= 1, "hipts_jpeg_batch_u8: image %d is %d x %d", i, h, w);
+        HIPTS_REQUIRE(h >= 1 && w >= 1, "%s: image %d is %d x %d", who, i, h, w);
         rgb_stride = std::max(rgb_stride, align256((size_t)h * w * 3));
         if (kinds[i] == 1) {
             const hipts_jpeg_header* hd = reinterpret_cast<const hipts_jpeg_header*>(slots + (size_t)i * slot_stride);
             size_t pb = 0;
             HIPTS_TRY(describe(hd, slot_stride, &ims[i], &pb));
-            HIPTS_REQUIRE(hd->height == h && hd->width == w, "hipts_jpeg_batch_u8: image %d: header %d x %d, caller %d x %d", i, hd->height, hd->width, h, w);
+            HIPTS_REQUIRE(hd->height == h && hd->width == w, "%s: image %d: header %d x %d, caller %d x %d", who, i, hd->height, hd->width, h, w);
             stage_off[i] = stage_total;
             plane_off[i] = plane_total;
             stage_total += align256((size_t)hd->total_bytes);
             plane_total += pb;
+        } else if (png && kinds[i] == 2) {
+            const hipts_png_header* hd = reinterpret_cast<const hipts_png_header*>(slots + (size_t)i * slot_stride);
+            PngImage pi{};
+            HIPTS_TRY(png_describe(hd, slot_stride, &pi));
+            HIPTS_REQUIRE(hd->height == h && hd->width == w, "%s: image %d: header %d x %d, caller %d x %d", who, i, hd->height, hd->width, h, w);
+            stage_off[i] = stage_total;
+            stage_total += align256((size_t)hd->total_bytes + PNG_STAGE_PAD);
         } else {
-            HIPTS_REQUIRE(kinds[i] == 0 && (int64_t)h * w * 3 <= slot_stride, "hipts_jpeg_batch_u8: image %d: kind %d, %d x %d in a slot of %lld bytes", i,
+            HIPTS_REQUIRE(kinds[i] == 0 && (int64_t)h * w * 3 <= slot_stride, "%s: image %d: kind %d, %d x %d in a slot of %lld bytes", who, i,
                           kinds[i], h, w, (long long)slot_stride);
         }
     }
@@ -340,6 +353,17 @@ extern "C" int hipts_jpeg_batch_u8(const uint8_t* slots, int64_t slot_stride, co
                 uint8_t* d = st.stage[device].as<uint8_t>() + stage_off[i];
                 HIPTS_HIP(hipMemcpyAsync(d, sp, (size_t)hd->total_bytes, hipMemcpyHostToDevice, s));
                 bind(ims[i], d, st.planes[device].as<uint8_t>() + plane_off[i]);
+            } else if (kinds[i] == 2) {
+                const hipts_png_header* hd = reinterpret_cast<const hipts_png_header*>(sp);
+                uint8_t* d = st.stage[device].as<uint8_t>() + stage_off[i];
+                HIPTS_HIP(hipMemcpyAsync(d, sp, (size_t)hd->total_bytes, hipMemcpyHostToDevice, s));
+                PngImage pi{};
+                pi.src = d + HIPTS_PNG_HEADER_BYTES;
+                pi.rgb = rgb + (size_t)i * rgb_stride;
+                pi.width = hd->width;
+                pi.height = hd->height;
+                pi.channels = hd->channels;
+                pngs.push_back(pi);
             } else {
                 HIPTS_HIP(hipMemcpyAsync(rgb + (size_t)i * rgb_stride, sp, (size_t)hw[2 * i] * hw[2 * i + 1] * 3, hipMemcpyHostToDevice, s));
             }
@@ -367,10 +391,24 @@ extern "C" int hipts_jpeg_batch_u8(const uint8_t* slots, int64_t slot_stride, co
             }
             HIPTS_TRY(flush());
         }
+        // the scanline slots, one workgroup per image
+        if (!pngs.empty()) HIPTS_TRY(png_launch(pngs.data(), (int)pngs.size(), s));
         // pad + resize of the decoded images (resize.hip; same stream, so ordered behind the kernels above)
         const int rs = hipts_resize_batch_u8(rgb, HIPTS_DEVICE, (int64_t)rgb_stride, hw, n, pad_square, dst_device, size, filter, device, stream);
         HIPTS_HIP(hipEventRecord(st.last[device], s));
         if (rs != HIPTS_OK) return rs;
     }
     return HIPTS_OK;
+}
+
+}  // namespace
+
+extern "C" int hipts_jpeg_batch_u8(const uint8_t* slots, int64_t slot_stride, const int32_t* kinds, const int32_t* hw, int n, int pad_square,
+                                   uint8_t* dst_device, int size, int filter, int device, void* stream) {
+    return decode_batch("hipts_jpeg_batch_u8", false, slots, slot_stride, kinds, hw, n, pad_square, dst_device, size, filter, device, stream);
+}
+
+extern "C" int hipts_decode_batch_u8(const uint8_t* slots, int64_t slot_stride, const int32_t* kinds, const int32_t* hw, int n, int pad_square,
+                                     uint8_t* dst_device, int size, int filter, int device, void* stream) {
+    return decode_batch("hipts_decode_batch_u8", true, slots, slot_stride, kinds, hw, n, pad_square, dst_device, size, filter, device, stream);
 }

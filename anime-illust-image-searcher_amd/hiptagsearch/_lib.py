@@ -125,6 +125,8 @@ _SIGNATURES = {
     "hipts_jpeg_slot_bytes": [c_int, c_int],
     "hipts_jpeg_decode_rgb": [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_void_p],
     "hipts_jpeg_batch_u8": [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
+    "hipts_png_decode_rgb": [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_void_p],
+    "hipts_decode_batch_u8": [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
     "hipts_ccip_metric": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p],
     "hipts_comm_unique_id": [c_void_p, c_size_t],
     "hipts_comm_create": [c_void_p, c_size_t, c_int, c_int, c_int, POINTER(c_void_p)],

@@ -26,6 +26,13 @@ resize on the host, which the reference does on 8 threads inside the GIL (taggin
                  (`hipts_jpeg_batch_u8`).  Files that path does not take (PNG, CMYK JPEGs, alpha, anything irregular) are
                  decoded by Pillow in the same worker as before; the two kinds mix freely inside a batch.
 
+  DecodePool(device_resize=True, device_png=True)   hybrid PNG decode, the same split: for a completely regular 8-bit, non-interlaced grey /
+                 grey + alpha / RGB / RGBA PNG the worker only checks the chunk stream and inflates the IDAT data (png_host.py: struct, zlib
+                 and numpy) -- the scanlines go into the ring slot still filtered; undoing the filters, grey -> RGB and the composite
+                 of alpha over white run on the device (csrc/png.hip, Pillow's bytes exactly) in front of the pad + resize
+                 (`hipts_decode_batch_u8`).  Palette, 16-bit, interlaced, tRNS, APNG and anything irregular go to Pillow as before.
+                 device_jpeg and device_png combine freely; a batch then mixes the three kinds of slot.
+
 Workers are started with the `forkserver` method so that no child is forked from a process that holds a GPU
 context; create the pool before or after the model, either is safe.
 """
@@ -35,6 +42,8 @@ from multiprocessing import shared_memory
 from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
+
+from . import png_host
 
 TAGGER = "tagger"      # white composite, centred pad to square, bicubic resize (tagging.py:100-120 + timm eval transform)
 CCIP = "ccip"          # white composite, bilinear resize (gen_cfeatures.py:285-295, 106)
@@ -95,40 +104,54 @@ def load_jpeg_host_lib():
     return lib
 
 
-def _raw_slot_bytes(raw_max_pixels: int, size: int, jpeg: bool) -> int:
+def _raw_slot_bytes(raw_max_pixels: int, size: int, jpeg: bool, png: bool = False) -> int:
     """Bytes of a ring slot in raw mode: the decoded image, or -- device_jpeg -- the coefficient blocks of a 4:2:0 / 4:2:2 JPEG of that
     many pixels: 2 B per sample, at most 2 samples per pixel, planes padded to whole 16 x 16 MCUs, a 1 KB header (csrc/jpeg_slot.h).
-    A JPEG that does not fit (4:4:4 above two thirds of max_pixels) is decoded by Pillow like any other file."""
+    A JPEG that does not fit (4:4:4 above two thirds of max_pixels) is decoded by Pillow like any other file.  device_png: the filtered
+    scanlines of an RGBA image of that many pixels which is at least 16 pixels wide -- 4 B per pixel, a filter byte per row, a 1 KB header
+    (csrc/png_slot.h); a narrower one that does not fit goes to Pillow too."""
     px = max(raw_max_pixels, size * size)
-    return px * 3 if not jpeg else px * 4 + 2 * 16 * 4 * (int(px ** 0.5) + 16) + 4096
+    nb = px * 3 if not jpeg else px * 4 + 2 * 16 * 4 * (int(px ** 0.5) + 16) + 4096
+    return max(nb, px * 4 + px // 16 + 1024 + 64) if png else nb
 
 
-def _worker_init(shm_name: str, slots: int, size: int, mode: str, raw_max_pixels: int = 0, jpeg: bool = False) -> None:
+def _worker_init(shm_name: str, slots: int, size: int, mode: str, raw_max_pixels: int = 0, jpeg: bool = False, png: bool = False) -> None:
     shm = shared_memory.SharedMemory(name=shm_name)
     _W["shm"] = shm
     if raw_max_pixels > 0:
-        _W["ring"] = np.ndarray((slots, _raw_slot_bytes(raw_max_pixels, size, jpeg)), dtype=np.uint8, buffer=shm.buf)
+        _W["ring"] = np.ndarray((slots, _raw_slot_bytes(raw_max_pixels, size, jpeg, png)), dtype=np.uint8, buffer=shm.buf)
     else:
         _W["ring"] = np.ndarray((slots, size, size, 3), dtype=np.uint8, buffer=shm.buf)
     _W["size"] = size
     _W["mode"] = mode
     _W["raw"] = raw_max_pixels
     _W["jpeg"] = load_jpeg_host_lib() if jpeg else None
+    _W["png"] = png
 
 
 def _worker_decode(task: Tuple[int, str]):
     """-> False (decode failed), True (model-input image in the slot), (h, w) (raw mode: the composited image at its own size) or
-    (h, w, 1) (raw mode with device_jpeg: the slot holds the JPEG's coefficient blocks, csrc/jpeg_slot.h)."""
+    (h, w, 1) (raw mode with device_jpeg: the slot holds the JPEG's coefficient blocks, csrc/jpeg_slot.h) or (h, w, 2) (raw mode with
+    device_png: the slot holds the PNG's filtered scanlines, csrc/png_slot.h)."""
     slot, path = task
-    if _W.get("jpeg") is not None:
+    jpeg, png = _W.get("jpeg"), _W.get("png")
+    if jpeg is not None or png:
         try:
             with open(path, "rb") as f:
-                data = f.read(2)
-                if data == b"\xff\xd8":            # a JPEG by its first marker: the whole file; anything else is left to Pillow unread
+                data = f.read(8)
+                # a JPEG by its first marker, a PNG by its signature: the whole file; anything else is left to Pillow unread
+                if (jpeg is not None and data[:2] == b"\xff\xd8") or (png and data == png_host.SIGNATURE):
                     data += f.read()
+                else:
+                    data = b""
         except OSError:
             data = b""
-        if len(data) > 4:
+        if png and data[:8] == png_host.SIGNATURE:
+            row = _W["ring"][slot]
+            if png_host.png_inflate_into(data, row) == 0:
+                hd = row[:16].view(np.int32)
+                return (int(hd[3]), int(hd[2]), 2)
+        elif len(data) > 4:
             row = _W["ring"][slot]
             src = np.frombuffer(data, dtype=np.uint8)
             if _W["jpeg"].hipts_jpeg_entropy_decode(src.ctypes.data, len(data), row.ctypes.data, row.nbytes) == 0:
@@ -155,9 +178,10 @@ class DecodePool:
     Files that fail to decode are dropped from `paths` (message printed by the worker), like the reference."""
 
     def __init__(self, workers: Optional[int] = None, size: int = 448, batch: int = 64, mode: str = TAGGER,
-                 device_resize: bool = False, device: int = 0, max_pixels: int = 1600 * 1600, device_jpeg: bool = False):
-        if device_jpeg and not device_resize:
-            raise ValueError("device_jpeg needs device_resize: the decoded image only exists on the device")
+                 device_resize: bool = False, device: int = 0, max_pixels: int = 1600 * 1600, device_jpeg: bool = False,
+                 device_png: bool = False):
+        if (device_jpeg or device_png) and not device_resize:
+            raise ValueError("device_jpeg and device_png need device_resize: the decoded image only exists on the device")
         self.workers = max(1, workers or (os.cpu_count() or 1))
         self.size, self.batch, self.mode = size, batch, mode
         # ring parts: two batches (one being decoded, one being consumed); with the device resize three -- two batches at the workers, so
@@ -167,9 +191,10 @@ class DecodePool:
         self.raw = max(int(max_pixels), size * size) if device_resize else 0
         self.device = device
         self.jpeg = bool(device_jpeg)
+        self.png = bool(device_png)
         self._pinned = False
         self._events = [None] * 3
-        slot_bytes = _raw_slot_bytes(self.raw, size, self.jpeg) if self.raw else size * size * 3
+        slot_bytes = _raw_slot_bytes(self.raw, size, self.jpeg, self.png) if self.raw else size * size * 3
         self._shm = shared_memory.SharedMemory(create=True, size=self.slots * slot_bytes)
         if self.raw:
             self._ring = np.ndarray((self.slots, slot_bytes), dtype=np.uint8, buffer=self._shm.buf)
@@ -181,7 +206,7 @@ class DecodePool:
         else:
             self._ring = np.ndarray((self.slots, size, size, 3), dtype=np.uint8, buffer=self._shm.buf)
         ctx = mp.get_context("forkserver")
-        self._pool = ctx.Pool(self.workers, initializer=_worker_init, initargs=(self._shm.name, self.slots, size, mode, self.raw, self.jpeg))
+        self._pool = ctx.Pool(self.workers, initializer=_worker_init, initargs=(self._shm.name, self.slots, size, mode, self.raw, self.jpeg, self.png))
 
     def _to_device(self, base: int, results, stream) -> "object":
         """Raw mode: the ring slots base .. of one decoded batch -> uint8 [n,S,S,3] CUDA tensor on `stream`: copied, padded (tagger: white,
@@ -191,10 +216,10 @@ class DecodePool:
         from . import _lib
         S = self.size
         out = torch.empty((len(results), S, S, 3), dtype=torch.uint8, device="cuda:%d" % self.device)
-        if self.jpeg:       # coefficient slots and Pillow-decoded slots side by side: decode on the device, then the same pad + resize
+        if self.jpeg or self.png:       # coefficient, scanline and Pillow-decoded slots side by side: decode on the device, then the same pad + resize
             hw = np.ascontiguousarray(np.asarray([r[:2] for r in results], dtype=np.int32))
-            kinds = np.ascontiguousarray(np.asarray([1 if len(r) > 2 else 0 for r in results], dtype=np.int32))
-            _lib.call("hipts_jpeg_batch_u8", self._ring[base].ctypes.data, self._ring.shape[1], _lib.ptr(kinds), _lib.ptr(hw), len(results),
+            kinds = np.ascontiguousarray(np.asarray([r[2] if len(r) > 2 else 0 for r in results], dtype=np.int32))
+            _lib.call("hipts_decode_batch_u8", self._ring[base].ctypes.data, self._ring.shape[1], _lib.ptr(kinds), _lib.ptr(hw), len(results),
                       1 if self.mode == TAGGER else 0, _lib.ptr(out), S, 3 if self.mode == TAGGER else 2, self.device, stream.cuda_stream)
             return out
         hw = np.ascontiguousarray(np.asarray(results, dtype=np.int32).reshape(-1, 2))
@@ -229,7 +254,7 @@ class DecodePool:
                     yield [chunk[i] for i in keep], np.ascontiguousarray(view[keep])
 
     def _batches_raw(self, chunks):
-        """decode (worker processes, batches k + 2 and k + 3: the ring has three parts)  ||  copy + JPEG device half + pad + resize (this
+        """decode (worker processes, batches k + 2 and k + 3: the ring has three parts)  ||  copy + JPEG / PNG device half + pad + resize (this
         producer thread, its own stream, batch k + 1)  ||  the consumer's forward (caller's stream, batch k).  The hand-over is a queue of
         (paths, tensor, event)."""
         import queue

@@ -303,7 +303,7 @@ class Predictor:
     seeded synthetic stand-ins."""
 
     def __init__(self, device: int = 0, max_batch: int = 64, compat: bool = False, gpu_resize: bool = False, gpu_jpeg: bool = False,
-                 precise: bool = False) -> None:
+                 precise: bool = False, gpu_png: bool = False) -> None:
         self.device = device
         # precise: operand_f16 |= 16 (HIPTS_OPERAND_SPLIT_ATT, include/hip_tagsearch.h) for ViT and EVA02 -- the attention output reaches the
         # output projection as a hi | lo pair of halves.  Flat pictures' logit error 1.7e-3 -> 2.1e-4 for about 5 % of the throughput
@@ -313,6 +313,7 @@ class Predictor:
         self.compat = compat            # reproduce the reference's dropped tail batch
         self.gpu_resize = gpu_resize    # the decode threads only decode and pad; Resize(bicubic) runs on the device (hipts_resize_u8)
         self.gpu_jpeg = gpu_jpeg        # worker processes only entropy-decode baseline JPEGs; the rest of libjpeg runs on the device (pipeline.DecodePool)
+        self.gpu_png = gpu_png          # worker processes only inflate regular PNGs; unfiltering and the white composite run on the device (pipeline.DecodePool)
         self.tagger_model: Optional[ViTTagger] = None
         self.selector: Optional[TagSelector] = None
         self.tag_names: Optional[List[str]] = None
@@ -533,7 +534,7 @@ class Predictor:
             from . import pipeline
             mine = file_list[lo:hi]
             where = {p: i for i, p in enumerate(mine)}
-            pool = pipeline.DecodePool(workers, size, bs, pipeline.TAGGER, device_resize=self.gpu_resize, device=self.device, device_jpeg=self.gpu_jpeg)
+            pool = pipeline.DecodePool(workers, size, bs, pipeline.TAGGER, device_resize=self.gpu_resize, device=self.device, device_jpeg=self.gpu_jpeg, device_png=self.gpu_png)
             def batches():
                 for kept, images in pool.batches(mine):
                     yield [where[p] for p in kept], images
@@ -635,7 +636,7 @@ class Predictor:
                 source = pipeline.iter_shards(shards, min(batch_size, self.max_batch))
             else:
                 pool = pipeline.DecodePool(workers, size, min(batch_size, self.max_batch), pipeline.TAGGER, device_resize=self.gpu_resize,
-                                           device=self.device, device_jpeg=self.gpu_jpeg)
+                                           device=self.device, device_jpeg=self.gpu_jpeg, device_png=self.gpu_png)
                 source = pool.batches(file_list)
             # predict() in two halves: while one thread selects, formats and writes the lines of batch k (the reference does that part on
             # the CPU too, tagging.py:185-232), this one is already in the forward of batch k + 1 -- one worker, so the file keeps its order

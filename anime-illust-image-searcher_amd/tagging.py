@@ -42,6 +42,9 @@ def main(arg_str: list) -> None:
     parser.add_argument('--gpu-jpeg', action='store_true',
                         help='with --workers and --gpu-resize: the worker processes only entropy-decode baseline JPEGs; inverse DCT, chroma '
                              'upsampling and colour conversion (libjpeg-turbo\'s arithmetic, byte for byte) run on the device; other files as before')
+    parser.add_argument('--gpu-png', action='store_true',
+                        help='with --workers and --gpu-resize: the worker processes only inflate regular 8-bit PNGs; undoing the scanline filters and '
+                             'the composite of alpha over white (Pillow\'s bytes exactly) run on the device; other files as before')
     parser.add_argument('--synthetic', type=int, default=0, metavar='N',
                         help='tag N images of the synthetic benchmark corpus generated on the device (BASELINE.json configs[3]; --dir is ignored)')
     parser.add_argument('--precise', action='store_true',
@@ -57,8 +60,8 @@ def main(arg_str: list) -> None:
     from hiptagsearch import dist as hdist
     dist, rank, world, device = hdist.init_from_env(args.device)
     from hiptagsearch.tagger import Predictor
-    predictor = Predictor(device=device, max_batch=args.batch, compat=args.compat, gpu_resize=args.gpu_resize or args.gpu_jpeg, gpu_jpeg=args.gpu_jpeg,
-                          precise=args.precise)
+    predictor = Predictor(device=device, max_batch=args.batch, compat=args.compat, gpu_resize=args.gpu_resize or args.gpu_jpeg or args.gpu_png,
+                          gpu_jpeg=args.gpu_jpeg, precise=args.precise, gpu_png=args.gpu_png)
     from hiptagsearch import synth
     model_cfg = {'vit-b16': synth.VIT_B16_448, 'eva02-l14': synth.EVA02_L14_448, 'convnext-b': synth.CONVNEXT_B_448, 'swinv2-b': synth.SWINV2_B_448,
                  'vit-tiny': synth.VIT_TINY, 'convnext-tiny': synth.CONVNEXT_TINY, 'swinv2-tiny': synth.SWINV2_TINY}[args.model]   # *-tiny: test geometries

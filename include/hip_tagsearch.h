@@ -335,6 +335,22 @@ int hipts_jpeg_decode_rgb(const void* slot, int64_t slot_bytes, uint8_t* rgb_out
 int hipts_jpeg_batch_u8(const uint8_t* slots, int64_t slot_stride, const int32_t* kinds, const int32_t* hw, int n, int pad_square,
                         uint8_t* dst_device, int size, int filter, int device, void* stream);
 
+/* ---- Hybrid PNG decode.  What stands behind it in the reference: the same Image.open(path) plus the composite of alpha over white in
+ * Predictor.prepare_image (tagging.py:103-106).  The serial half -- the chunk stream and inflate -- runs on the host, in the decode worker
+ * processes (hiptagsearch/png_host.py: png_inflate_into, pure Python over zlib); undoing the scanline filters, grey -> RGB and the white
+ * composite run on the device, byte for byte what Pillow returns.  A "slot" = hipts_png_header (csrc/png_slot.h) + the inflated
+ * scanlines with their filter bytes; 8-bit grey, grey + alpha, RGB and RGBA, not interlaced, at most 8192 pixels wide.
+ *
+ * One slot (host memory) -> uint8 [height][width][3] RGB = the bytes of PIL.Image.open(file) composited over white / converted to RGB;
+ * rgb_out in host or device memory with room for out_capacity bytes.  Synchronises `stream`. */
+int hipts_png_decode_rgb(const void* slot, int64_t slot_bytes, uint8_t* rgb_out, int out_memspace, int64_t out_capacity, int device, void* stream);
+
+/* hipts_jpeg_batch_u8 with a third kind of slot: kinds[i] = 0 (decoded uint8 [h][w][3]), 1 (JPEG coefficient blocks) or 2 (PNG
+ * scanlines).  Decode, then exactly hipts_resize_batch_u8; ordered on `stream` behind the previous call that used the shared staging,
+ * nothing is synchronised.  A slot header that disagrees with hw is refused. */
+int hipts_decode_batch_u8(const uint8_t* slots, int64_t slot_stride, const int32_t* kinds, const int32_t* hw, int n, int pad_square,
+                          uint8_t* dst_device, int size, int filter, int device, void* stream);
+
 /* The synthetic image corpus of the benchmark configurations (BASELINE.json configs[3]: "1M synthetic images sharded
  * 8xMI355X"), generated on the device with no host I/O: images first_index .. first_index + count - 1 of the corpus `seed`, uint8
  * [count][image_size][image_size][3], every byte a counter-hash of (seed, GLOBAL image index, byte offset) -- so a rank produces its own
