@@ -1104,6 +1104,9 @@ int launch_t(const GemmArgs& a, hipStream_t s) {
             }
             break;
         case HIPTSDBG_GEMM_DW: {
+            // this loop's staged epilogues finish a folded LayerNorm from the first four partial pairs only (row_stat_request)
+            if constexpr (EPI == EPI_VT || EPI == EPI_GELU || EPI == EPI_STAR || EPI == EPI_QK || EPI == EPI_QK_ROPE || EPI == EPI_SWIGLU)
+                HIPTS_REQUIRE(!(a.stat_in && a.stat_in_blocks > 4), "gemm: the two-workgroups-per-CU loop folds at most 4 stat_in pairs per row (%d given)", a.stat_in_blocks);
             static PerDevice once;
             HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_dw_kernel<EPI, false>, gemm_dw_kernel<EPI, true>));
             if (f16) go(gemm_dw_kernel<EPI, true>);
@@ -1209,6 +1212,8 @@ int launch_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
     HIPTS_REQUIRE(a.M >= 1 && a.N >= 1, "gemm: empty problem");
     if (epi != EPI_HEAD) HIPTS_REQUIRE(a.N % 16 == 0, "gemm: N=%d must be a multiple of 16", a.N);
     if (epi == EPI_VT) HIPTS_REQUIRE(a.M % 4 == 0 && a.tokens % 4 == 0, "gemm: V^T epilogue needs tokens %% 4 == 0");
+    if (epi == EPI_VT && a.tokens % 8 == 0 && a.tokens_pad % 8 == 0)      // the staged V^T store writes eight tokens of a column at a time
+        HIPTS_REQUIRE(a.M % 8 == 0, "gemm: V^T epilogue with tokens %% 8 == 0 needs M %% 8 == 0 (M = %d)", a.M);
     if (epi == EPI_QK || epi == EPI_VT) HIPTS_REQUIRE(a.hd_log2 == 5 || a.hd_log2 == 6, "gemm: head_dim must be 32 or 64");
     if (epi == EPI_QK || epi == EPI_QK_ROPE)
         HIPTS_REQUIRE(a.out_bf16 && a.out2_bf16 && a.dim > 0 && a.N <= 3 * a.dim && (a.N <= 2 * a.dim || a.out3_bf16), "gemm: q / k / v outputs missing for N = %d, dim = %d", a.N, a.dim);

@@ -83,6 +83,50 @@ typedef struct hiptsdbg_gemm_plan_t {
  * refuses returns its error (and out->error). */
 int hiptsdbg_gemm_plan(int epi, int M, int N, int K, int f16, int shared_chip, unsigned features, int ld_out, int dim, int cus,
                        unsigned q4_mask, hiptsdbg_gemm_plan_t* out);
+/* ONE production launch -- launch_gemm(epi, g, null stream): the plan is gemm_plan()'s for this process and device, nothing is forced --
+ * on caller-supplied operands, every output copied back whole (csrc/gemm_dbg.hip; tests/test_gpu_gemm_epi.py).
+ * Inputs (host): a [M][K] and w [N][K] as 16-bit patterns (bf16, or IEEE half with f16 = 1; the entry pads w with zero rows to a multiple
+ * of 256); the per-column float32 vectors bias / res_scale / ln_gamma / ln_beta / col_u of N elements (ln_gamma of EPI_SWIGLU: N / 2);
+ * pos [tokens][N]; rowstat [M] pairs (rstd, rstd * mean) or stat_in [stat_in_blocks][stat_in_stride] pairs (sum, sum of squares);
+ * rope [rope_tokens][32] pairs (sin, cos).  A null vector is absent from GemmArgs, except bias: null = zeros.  The scalar fields are
+ * GemmArgs' of the same name (csrc/vit_internal.h); sk_ws != 0 hands the launch a zeroed split-K workspace as the forwards do.
+ * Outputs: the caller sizes every buffer (hiptsdbg_gemm_out_t: host pointer and bytes; 0 bytes = the pointer stays null in GemmArgs) --
+ * what the epilogue may write plus as many guard rows and pad elements as the test wants to watch.  The entry refuses a buffer smaller
+ * than the launch's extent, fills each whole device buffer with the byte `fill`, copies x_init (x_init_bytes <= x_bytes; the fp32 stream's
+ * initial contents, row-major or in the blocked layout as x_blocked says: [m / 16][n / 16][m % 16][n % 16], ld_out % 16 == 0, rows up to
+ * a multiple of 16) over the start of x, launches once and copies every buffer back whole: a byte outside [M][N] that no longer holds
+ * `fill` was written by the kernel.
+ *   x: out_f32 (the fp32 stream; EPI_HEAD: logits)    rowmajor: resid_rowmajor_out    probs: out2_f32 (EPI_HEAD)
+ *   out16[0..2]: out_bf16, out2_bf16, out3_bf16       stat_part: [column tile][stat_stride] pairs (EPI_SWIGLU, EPI_RESID_XG / XGI) */
+typedef struct hiptsdbg_gemm_case_t {
+    int32_t epi, M, N, K, f16, shared_chip;
+    const uint16_t* a;
+    const uint16_t* w;
+    const float* bias;
+    const float* pos;
+    const float* res_scale;
+    const float* ln_gamma;
+    const float* ln_beta;
+    const float* col_u;
+    const float* rowstat;
+    const float* stat_in;
+    const float* rope;
+    const float* x_init;
+    uint64_t x_init_bytes;
+    int32_t tokens, tokens_pad, heads, dim, hd_log2;
+    int32_t stat_in_blocks, stat_in_stride, ln_dim, rope_tokens, stat_stride;
+    int32_t gelu_tanh, star_kind, ld_out, x_blocked, sk_ws, fill;
+    float qscale, ln_eps, star_scale, star_bias;
+} hiptsdbg_gemm_case_t;
+typedef struct hiptsdbg_gemm_out_t {
+    void* x;
+    void* rowmajor;
+    void* probs;
+    void* out16[3];
+    void* stat_part;
+    uint64_t x_bytes, rowmajor_bytes, probs_bytes, out16_bytes[3], stat_part_bytes;
+} hiptsdbg_gemm_out_t;
+int hiptsdbg_gemm_epilogue(const hiptsdbg_gemm_case_t* in, hiptsdbg_gemm_out_t* out);
 /* out_host float32 [M][N] = A W^T for bf16 bit patterns a_bf16 [M][K], w_bf16 [N][K] (plain epilogue). */
 int hiptsdbg_gemm_run(int M, int N, int K, const uint16_t* a_bf16, const uint16_t* w_bf16, float* out_host);
 /* The e4m3 operand path: a_f32 / w_f32 are quantised by the library (per-tensor power-of-two weight scale returned in

@@ -15,7 +15,7 @@ PKG = os.path.join(ROOT, "anime-illust-image-searcher_amd")
 sys.path.insert(0, PKG)
 
 V1, PP, S3, PP2, DW, Q4, PP_E4M3 = range(7)                                     # hiptsdbg_gemm_plan_t::loop
-QK, RESID, GELU, HEAD, RESID_XG = 1, 3, 4, 5, 13                                # GemmEpilogue
+QK, RESID, GELU, HEAD, RESID_LN, RESID_XG, RESID_LS = 1, 3, 4, 5, 9, 13, 15            # GemmEpilogue
 STAT_PART, SK_WS, POS, RES_SCALE, COPY16, STAT_IN, OP8, STAMPS = (1 << i for i in range(8))
 FIELDS = ["loop", "mr", "interior", "stamped", "tiles_m", "tiles_n", "grid", "block", "lds_bytes", "sk_first", "sk_slices",
           "raster_gm", "raster_gn", "epi_prio", "epi_prefetch", "error"]
@@ -57,6 +57,20 @@ TABLE = [
     ("ViT proj / fc2", XG_VIT, dict(PP_GEOM, mr=8, interior=1, tiles_m=98, tiles_n=3, grid=256, raster_gm=0, raster_gn=0)),
     ("ViT patch GEMM", dict(XG_VIT, features=STAT_PART | COPY16 | POS), dict(PP_GEOM, mr=8, interior=0, tiles_m=98, tiles_n=3, grid=256)),
     ("ViT fc1", dict(VIT, epi=GELU, N=3072), dict(PP_GEOM, mr=8, tiles_m=98, tiles_n=12, grid=256, raster_gm=8, raster_gn=6)),
+    # batch-specific tile heights / loops of the ViT forward (tests/gemm_epi_ref.py sweeps every batch; tests/test_gpu_gemm_epi.py runs each arm)
+    ("ViT fc1, batch 12: 224 rows", dict(epi=GELU, M=12 * 784, N=3072, K=768, f16=1, features=STAT_IN),
+     dict(PP_GEOM, mr=7, tiles_m=42, tiles_n=12, grid=256, raster_gm=8, raster_gn=6)),
+    ("ViT q|k|v, batch 7: 224 rows, one round", dict(epi=QK, M=7 * 784, N=2304, K=768, f16=1, features=STAT_IN, dim=768),
+     dict(PP_GEOM, mr=7, tiles_m=25, tiles_n=9, grid=225, raster_gm=8, raster_gn=6)),
+    ("ViT proj / fc2, batch 45: 224 rows, general form", dict(XG_VIT, M=23 * 784, features=STAT_PART | COPY16 | SK_WS),
+     dict(PP_GEOM, mr=7, interior=0, tiles_m=81, tiles_n=3, grid=243)),
+    ("ViT last fc2, batch 13: two per CU", dict(epi=RESID, M=13 * 784, N=768, K=3072, f16=1, features=SK_WS), dict(DW_GEOM, tiles_m=40, tiles_n=6, grid=240)),
+    ("ViT last fc2, batch 14: 192 rows", dict(epi=RESID, M=14 * 784, N=768, K=3072, f16=1, features=SK_WS),
+     dict(PP_GEOM, mr=6, interior=0, tiles_m=58, tiles_n=3, grid=174)),
+    ("ConvNeXt-B stage 2 fc2, batch 8: two per CU", dict(epi=RESID_LS, M=8 * 784, N=512, K=2048, f16=1, features=RES_SCALE | COPY16),
+     dict(DW_GEOM, tiles_m=25, tiles_n=4, grid=100)),
+    ("CAFormer stage 0 residual + LayerNorm, 32 images: persistent, one column tile", dict(epi=RESID_LN, M=32 * 9216, N=128, K=256, f16=1, shared_chip=1, features=COPY16),
+     dict(PP_GEOM, mr=8, interior=0, tiles_m=1152, tiles_n=1, grid=256)),
     # EVA02-L, a sub-batch of 5 images of 1025 tokens (padded to 1032 rows): never the dw loop, which has no statistics epilogue
     ("EVA02-L proj", dict(epi=RESID_XG, M=5160, N=1024, K=1024, f16=1, shared_chip=1, features=STAT_PART | COPY16),
      dict(PP_GEOM, mr=6, interior=0, tiles_m=27, tiles_n=4, grid=108)),
