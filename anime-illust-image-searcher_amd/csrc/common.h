@@ -141,4 +141,9 @@ int current_device_cus(int* dev_out = nullptr);
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// Internal (C++ linkage, not part of the ABI): the tile-major copy of a dense index as the product kernels of query.hip read it --
+// float4 tl[(T * dim/4 + kq) * 32 + c] = row[32 T + c][4 kq .. 4 kq + 3], rows past `len` inside the last tile zero; *tiled is null
+// while the index is empty.  For radius.hip, which multiplies the index with itself.
+int index_tiled_view(const hipts_index_t* h, const float4** tiled, int64_t* len, int* dim, int* device);
+
 }  // namespace hipts

@@ -1860,6 +1860,19 @@ int hipts_index_data(const hipts_index_t* h, void** device_ptr) {
     return HIPTS_OK;
 }
 
+}  // extern "C"
+
+int hipts::index_tiled_view(const hipts_index_t* h, const float4** tiled, int64_t* len, int* dim, int* device) {
+    HIPTS_REQUIRE(h && tiled && len && dim && device, "null argument");
+    *tiled = h->len > 0 ? h->tiled.as<float4>() : nullptr;
+    *len = h->len;
+    *dim = h->dim;
+    *device = h->device;
+    return HIPTS_OK;
+}
+
+extern "C" {
+
 int hipts_index_query(hipts_index_t* h, const float* queries, int queries_memspace, int nq, float* scores_out,
                       int out_memspace, void* stream) {
     HIPTS_REQUIRE(h && queries && scores_out && nq >= 1, "hipts_index_query: bad arguments");

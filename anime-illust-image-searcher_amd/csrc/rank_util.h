@@ -1,5 +1,5 @@
-// rank_util.h -- the small pieces the ranking kernels of query.hip, crerank.hip and tags.hip share: the order-preserving u32 image of a
-// float, the block-wide exclusive scan and the block-wide maximum.  Device code only.  Everything lives in an anonymous namespace, so
+// rank_util.h -- the small pieces the ranking kernels of query.hip, crerank.hip and tags.hip share (radius.hip: the scan): the
+// order-preserving u32 image of a float, the block-wide exclusive scan and the block-wide maximum.  Device code only.  Everything lives in an anonymous namespace, so
 // each including object gets its own copy under the same symbol names.
 #pragma once
 #include <cstdint>

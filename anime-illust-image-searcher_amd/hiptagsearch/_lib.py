@@ -141,6 +141,11 @@ _SIGNATURES = {
     "hipts_crerank_destroy": [c_void_p],
     "hipts_crerank_run": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "hipts_crerank_read": [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p],
+    "hipts_radius_create": [c_void_p, c_float, c_int64, c_void_p, POINTER(c_void_p)],
+    "hipts_radius_destroy": [c_void_p],
+    "hipts_radius_info": [c_void_p, POINTER(c_int64), POINTER(c_int64)],
+    "hipts_radius_read": [c_void_p, c_void_p, c_void_p],
+    "hipts_radius_dbscan": [c_void_p, c_int, c_void_p, POINTER(c_int64), POINTER(c_int32)],
     "hipts_rerank_finish": [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "hipts_query_profile_enable": [c_void_p, c_int],
     "hipts_query_profile_read": [c_void_p, c_int, POINTER(c_double), POINTER(c_int64), POINTER(c_double)],

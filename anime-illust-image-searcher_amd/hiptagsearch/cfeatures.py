@@ -229,6 +229,53 @@ class CharacterFeatureIndex:
             q = q / nq
         return np.float32(1.0) - self.index.query(q)[0]
 
+    # ---- which rows show the same character (hipts_radius_*) ----------------------------------------------------------------
+    def _radius(self, threshold, max_pairs):
+        import ctypes
+        from . import _lib
+        t = _threshold_f32(self.cosine_diff_threshold if threshold is None else threshold)
+        h = ctypes.c_void_p()
+        _lib.call("hipts_radius_create", self.index._h, ctypes.c_float(float(t)), ctypes.c_int64(int(max_pairs)), _lib.current_stream_ptr(),
+                  ctypes.byref(h))
+        return h
+
+    def radius_neighbors(self, threshold=None, max_pairs: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """(ptr int64 [n + 1], ids int32 [pairs]): ids[ptr[i]:ptr[i + 1]] are, ascending, the rows j with
+        `float32(1) - index.query(row i)[j] < threshold` in float32 -- row i itself among them unless it is all zero.  The product
+        runs on the device for all pairs at once and stores no score.  threshold None: cosine_diff_threshold; a Python float or a
+        numpy float64 cut behaves as in DeviceReranker (_threshold_f32).  max_pairs: the call refuses (HipTagSearchError naming the
+        count) when more pairs than this lie under the threshold; 0 = what fits in half of the free device memory.  An empty
+        index is refused."""
+        import ctypes
+        from . import _lib
+        h = self._radius(threshold, max_pairs)
+        try:
+            rows, pairs = ctypes.c_int64(), ctypes.c_int64()
+            _lib.call("hipts_radius_info", h, ctypes.byref(rows), ctypes.byref(pairs))
+            ptr = np.empty(rows.value + 1, dtype=np.int64)
+            ids = np.empty(pairs.value, dtype=np.int32)
+            _lib.call("hipts_radius_read", h, _lib.ptr(ptr), _lib.ptr(ids))
+        finally:
+            _lib.call("hipts_radius_destroy", h)
+        return ptr, ids
+
+    def cluster(self, threshold=None, min_samples: int = 2, max_pairs: int = 0) -> np.ndarray:
+        """DBSCAN labels int32 [n] over radius_neighbors' relation, in its canonical, order-independent form: row i is core when it has
+        at least min_samples neighbours (itself included); clusters are the connected components of the core rows, numbered from 0 by
+        their smallest core row; a non-core row with core neighbours takes the smallest label among them; every other row is -1.
+        The default min_samples = 2 makes any two neighbouring pictures a group.  `last_cluster_stats` keeps (clusters, sweeps)."""
+        import ctypes
+        from . import _lib
+        h = self._radius(threshold, max_pairs)
+        try:
+            labels = np.empty(len(self.index), dtype=np.int32)
+            clusters, sweeps = ctypes.c_int64(), ctypes.c_int32()
+            _lib.call("hipts_radius_dbscan", h, int(min_samples), _lib.ptr(labels), ctypes.byref(clusters), ctypes.byref(sweeps))
+        finally:
+            _lib.call("hipts_radius_destroy", h)
+        self.last_cluster_stats = (clusters.value, sweeps.value)
+        return labels
+
 
 def ccip_batch_differences(features: np.ndarray, device: int = 0) -> np.ndarray:
     """gen_cfeatures.py:257-274: the matrix of pairwise differences of a list of feature vectors -- float32 [n, n].  The reference runs its

@@ -541,7 +541,36 @@ int hipts_crerank_run(hipts_crerank_t* h, hipts_index_t* features, const float* 
 int hipts_crerank_read(hipts_crerank_t* h, int query, int64_t first, int64_t count, int32_t* docs_out, double* scores_out);
 
 /* ------------------------------------------------------------------------------------------
- * Normal-mode rerank, finishing stage for a batch.   Replaces the host list code of
+ * Fixed-radius neighbour lists over a feature index, and DBSCAN on them.   Beyond the reference: "which
+ * pictures show the same character?" for the index gen_cfeatures.py builds.
+ *
+ * Relation: for rows i, j of `features` and a float32 threshold T,   j in N(i)  <=>  1.0f - s(i, j) < T   in float32,
+ * where s(i, j) is what hipts_index_query returns for row i as the query against row j (the k-ascending fmaf chain;
+ * symmetric bit for bit).  It holds for every j, j == i included; an all-zero row has s = 0 and is nobody's neighbour.
+ *
+ * create: both passes of the thresholded all-pairs product (degrees, then ids) -- half the block pairs, no score ever
+ * stored -- and the CSR lists on the device: ptr int64 [rows + 1], ids int32 [pairs], every row's ids ascending; the
+ * same bytes run to run.  The index dimension must be a multiple of 4, the index non-empty (an empty one is refused),
+ * rows < 2^31.  After the first pass the total is known: when it exceeds max_pairs the call fails with
+ * HIPTS_ERR_INVALID and a message naming the count, before anything of that size is allocated; max_pairs 0 stands
+ * for half of the device memory free at the call, in ids.  Synchronises `stream`.  The handle does not refer to
+ * `features` afterwards.
+ * info / read: the sizes; the CSR into host arrays.
+ * dbscan: canonical DBSCAN over the lists, min_samples >= 1.  Row i is core when |N(i)| >= min_samples (N(i) counts i
+ * itself); clusters are the connected components of the core rows under the relation, numbered 0, 1, ... by their
+ * smallest core row; a core row gets its cluster's number, a non-core row with core neighbours the SMALLEST label
+ * among them, every other row -1.  labels_out int32 [rows] (host).  The components come from min-label propagation,
+ * one launch per sweep driven by the host; *sweeps_out receives the number of sweeps (the last one changes nothing).
+ * More than `rows` sweeps cannot be needed; if that cap is reached the call fails instead of returning labels. */
+typedef struct hipts_radius hipts_radius_t;
+int hipts_radius_create(hipts_index_t* features, float threshold, int64_t max_pairs, void* stream, hipts_radius_t** out);
+int hipts_radius_destroy(hipts_radius_t* h);
+int hipts_radius_info(const hipts_radius_t* h, int64_t* rows, int64_t* pairs);
+int hipts_radius_read(hipts_radius_t* h, int64_t* ptr_out, int32_t* ids_out);
+int hipts_radius_dbscan(hipts_radius_t* h, int min_samples, int32_t* labels_out, int64_t* num_clusters, int32_t* sweeps_out);
+
+/* ------------------------------------------------------------------------------------------
+ * Normal-mode rerank, finishing stage for a batch.  Replaces the host list code of
  * webui.py:210-240 after the second ranking: division by the maximum, the top ten pinned at 1.0,
  * removal of their duplicates, the gap filter (webui.py:63-80) and the cut to topn.
  *
