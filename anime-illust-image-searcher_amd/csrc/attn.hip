@@ -17,13 +17,10 @@
 // LDS rows are padded (K: 144 B, V^T: 136 B) so the b128 / b64 fragment reads are conflict free.
 // Keys beyond `tokens` (padding up to a multiple of 64) are masked to -inf; padded K / V^T entries
 // are zero (buffers are cleared once and the epilogues never write there).
-#include "vit_internal.h"
+// What this kernel and attn2.hip's must agree on -- the reference exponent and its head room, the row-sum window test, crow, the
+// HIPTS_ATTN_CLASSIC switch -- is in attn_common.h; the XCD remap of the work id is vit_internal.h's xcd_work_id.
+#include "attn_common.h"      // shared with attn2.hip: HIPTS_ATTN_REF_MARGIN, crow, ref_exponent, row_sum_left_window, attn_classic_switch
 
-// head room of the half-operand reference exponent: see attn2.hip (a row's first key tile is not representative of the row -- padding,
-// background -- and a workgroup that leaves the window runs both passes)
-#ifndef HIPTS_ATTN_REF_MARGIN
-#define HIPTS_ATTN_REF_MARGIN 10
-#endif
 namespace hipts {
 namespace {
 
@@ -46,8 +43,6 @@ template <int HD> struct Geo {
 // on MFMA results otherwise costs (45 v_max + 9 v_max3 per tile instead of 17 v_max3); no NaN can
 // occur: every tile has at least one unmasked key, so the running maximum is finite.
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-
-__device__ __forceinline__ int crow(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 // The per-tile work of one wave (32 queries x 64 keys), split in three so that the loop can be
 // software-pipelined:   S(t) MFMAs | P(t-1) V(t-1) MFMAs | softmax(t) on the VALU.
@@ -143,16 +138,10 @@ __device__ __forceinline__ void softmax_tile(const f32x16 (&sacc)[2], bf16x8 (&p
 // -- is detected at the end (attn_kernel, on the BITS of l so that a NaN cannot slip through -fno-honor-nans) and the workgroup
 // repeats the block with the classic per-tile maximum, which cannot overflow.
 // (Round 2 ran P = 2^S for half operands too, and its window check on l could not see a P that had already become +inf.)
-template <bool F16, int HD, int GH = 2>
-__device__ __forceinline__ void softmax_first(const f32x16 (&sacc)[2], bf16x8 (&pf)[2][2], float& l_run, float& m_ref) {
-    if constexpr (F16) {
-        float mx = sacc[0][0];
-#pragma unroll
-        for (int g = 0; g < GH; ++g)
-#pragma unroll
-            for (int i = (g == 0 ? 1 : 0); i < 16; ++i) mx = fmaxf(mx, sacc[g][i]);
-        m_ref = fmaxf(mx, __shfl_xor(mx, 32)) + (float)HIPTS_ATTN_REF_MARGIN;          // finite: tile 0 holds at least one unmasked key
-    }
+// FIRST (tile 0): half operands fix the row's reference exponent here.
+template <bool F16, bool FIRST, int GH = 2>
+__device__ __forceinline__ void softmax_fixed(const f32x16 (&sacc)[2], bf16x8 (&pf)[2][2], float& l_run, float& m_ref) {
+    if constexpr (F16 && FIRST) m_ref = ref_exponent<GH>(sacc);
     float lsum0 = 0.f, lsum1 = 0.f;
 #pragma unroll
     for (int g = 0; g < GH; ++g)
@@ -165,21 +154,7 @@ __device__ __forceinline__ void softmax_first(const f32x16 (&sacc)[2], bf16x8 (&
     l_run += lsum0 + lsum1;
 }
 
-template <bool F16, int HD, int GH = 2>
-__device__ __forceinline__ void softmax_nomax(const f32x16 (&sacc)[2], bf16x8 (&pf)[2][2], float& l_run, float m_ref) {
-    float lsum0 = 0.f, lsum1 = 0.f;
-#pragma unroll
-    for (int g = 0; g < GH; ++g)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float p = __builtin_amdgcn_exp2f(F16 ? sacc[g][i] - m_ref : sacc[g][i]);
-            if (i & 1) lsum1 += p; else lsum0 += p;
-            pf[g][i >> 3][i & 7] = to_op<F16>(p);
-        }
-    l_run += lsum0 + lsum1;
-}
-
-// CLASSIC: online softmax with the per-tile running maximum (softmax_tile); otherwise softmax_nomax.  Returns true when the
+// CLASSIC: online softmax with the per-tile running maximum (softmax_tile); otherwise softmax_fixed.  Returns true when the
 // fast path's row sum left its safe window (nothing is stored then).
 template <bool F16, int HD, bool CLASSIC>
 __device__ __forceinline__ bool attn_body(char* __restrict__ smem, const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
@@ -193,15 +168,8 @@ __device__ __forceinline__ bool attn_body(char* __restrict__ smem, const bf16_t*
     // softmax (VALU) runs under the others' MFMAs.
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
-    // XCD-aware work id: workgroups are dealt round-robin over the 8 XCDs (ids equal mod 8 share an
-    // L2).  Remap so that consecutive work items -- the query blocks of one (image, head), which all
-    // stream the same K / V^T -- run on ONE XCD and hit its L2 instead of each pulling its own copy
-    // through the fabric (measured: 1.23 GB fetched per launch vs 0.23 GB algorithmic before this).
-    int wid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, qd = nwg >> 3, rm = nwg & 7, xcd = wid & 7, loc = wid >> 3;
-        wid = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + loc;
-    }
+    // the query blocks of one (image, head) all stream the same K / V^T: consecutive work ids, one XCD's L2
+    const int wid = xcd_work_id(blockIdx.x, gridDim.x);
     const int bh = wid / qblocks, qb = wid - bh * qblocks;
     const int b = bh / heads, head = bh - b * heads;
     const int q0 = (qb * 4 + wave) * 32;
@@ -258,7 +226,7 @@ __device__ __forceinline__ bool attn_body(char* __restrict__ smem, const bf16_t*
 #pragma unroll
         for (int blk = 0; blk < HD / 32; ++blk) o[blk][i] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
-    float m_ref = 0.f;                  // fast path: the row's reference exponent, fixed by tile 0 (softmax_first)
+    float m_ref = 0.f;                  // fast path: the row's reference exponent, fixed by tile 0 (softmax_fixed<FIRST>)
     f32x16 sacc[2];
     bf16x8 pf[2][2];
 
@@ -275,10 +243,10 @@ __device__ __forceinline__ bool attn_body(char* __restrict__ smem, const bf16_t*
     auto softmax_last = [&](bool first) {
         if constexpr (CLASSIC) softmax_tile<F16, HD>(sacc, pf, o, m_run, l_run);
         else if (first) {
-            if (half_tail) softmax_first<F16, HD, 1>(sacc, pf, l_run, m_ref);
-            else softmax_first<F16, HD>(sacc, pf, l_run, m_ref);
-        } else if (half_tail) softmax_nomax<F16, HD, 1>(sacc, pf, l_run, m_ref);
-        else softmax_nomax<F16, HD>(sacc, pf, l_run, m_ref);
+            if (half_tail) softmax_fixed<F16, true, 1>(sacc, pf, l_run, m_ref);
+            else softmax_fixed<F16, true>(sacc, pf, l_run, m_ref);
+        } else if (half_tail) softmax_fixed<F16, false, 1>(sacc, pf, l_run, m_ref);
+        else softmax_fixed<F16, false>(sacc, pf, l_run, m_ref);
     };
     attn_load(0);
     attn_write(0, 0);
@@ -292,7 +260,7 @@ __device__ __forceinline__ bool attn_body(char* __restrict__ smem, const bf16_t*
         } else {
             s_tile<false, F16, HD>(smem, 0, tokens, r, h, qf, sacc);
             if constexpr (CLASSIC) softmax_tile<F16, HD>(sacc, pf, o, m_run, l_run);
-            else softmax_first<F16, HD>(sacc, pf, l_run, m_ref);
+            else softmax_fixed<F16, true>(sacc, pf, l_run, m_ref);
         }
     }
     if (nkv > 1) attn_write(1, 1);
@@ -306,7 +274,7 @@ __device__ __forceinline__ bool attn_body(char* __restrict__ smem, const bf16_t*
             s_tile<false, F16, HD>(smem + (t & 1) * K_BYTES, t * KV, tokens, r, h, qf, sacc);
             pv_tile<F16, HD>(smem + V_BASE + vprev * V_BYTES, r, h, pf, o);
             if constexpr (CLASSIC) softmax_tile<F16, HD>(sacc, pf, o, m_run, l_run);
-            else softmax_nomax<F16, HD>(sacc, pf, l_run, m_ref);
+            else softmax_fixed<F16, false>(sacc, pf, l_run, m_ref);
             attn_write((t + 1) & 1, vnxt);
             __syncthreads();
             vprev = vcur;
@@ -339,11 +307,7 @@ __device__ __forceinline__ bool attn_body(char* __restrict__ smem, const bf16_t*
     const float inv = 1.0f / l_tot;
     const int qi = q0 + r;
     if constexpr (!CLASSIC) {
-        // 0.5 <= l < 2^15 (half) / 2^-100 <= l < 2^100 (bf16), tested on the bit pattern: positive floats order like their bits, a
-        // negative value or a NaN (>= 0x7f800001, or sign bit set) falls outside whatever the compiler assumes about NaNs
-        const uint32_t lb = __float_as_uint(l_tot);
-        constexpr uint32_t LO = F16 ? 0x3f000000u - ((uint32_t)HIPTS_ATTN_REF_MARGIN << 23) : 0x0d800000u, HI = F16 ? 0x47000000u : 0x71800000u;
-        if (!(lb >= LO && lb < HI)) return true;
+        if (row_sum_left_window<F16>(l_tot)) return true;
     }
     if (qi < tokens) {
         bf16_t* op = out + ((size_t)b * out_stride + qi) * (heads * HD) + head * HD;
@@ -382,7 +346,7 @@ int launch_attention(const bf16_t* q, const bf16_t* k, const bf16_t* vT, bf16_t*
     const int qtiles = (tokens + 31) / 32;
     const int qblocks = (qtiles + 3) / 4;
     const int grid = batch * heads * qblocks;
-    static const int classic = (getenv("HIPTS_ATTN_CLASSIC") && atoi(getenv("HIPTS_ATTN_CLASSIC"))) ? 1 : 0;
+    const int classic = attn_classic_switch();
     static const int trim = (getenv("HIPTS_ATTN_TRIM") && atoi(getenv("HIPTS_ATTN_TRIM")) == 0) ? 0 : 1;
     if (head_dim == 64) {
         if (f16) attn_kernel<true, 64><<<grid, 256, 0, s>>>(q, k, vT, out, heads, tokens, tokens_pad, qblocks, ost, classic, trim);

@@ -17,48 +17,33 @@
 // softmax with a FIXED reference exponent (see attn.hip: bf16 operands P = 2^S, half operands P = 2^(S - m_ref) with m_ref the row's
 // maximum over the first key tile) and the classic per-tile-maximum body as the fallback of a workgroup whose row sum leaves the window.
 //
-// LDS images (both 128 B per key row, filled lane-linear by the DMA with the swizzle on the SOURCE chunk):
+// LDS images (both 128 B per key row, filled lane-linear by the DMA with the swizzle on the SOURCE chunk).  Each is defined once, below:
+// the writer's side as k_src_chunk / v_src_chunk (row, lane), the reader's as k_frag_addrs / v_frag_addrs (lane, base); the four bodies
+// of this file and attn3.h (attn2_body, attn2_seq_body, attn2_classic, attn3_body) call them -- but for the reader's side in attn3_body,
+// which keeps the two loops written out (called, hipcc puts one more s_waitcnt into the half-operand attn3_kernel).
 //   K  chunk c of row r at position c ^ ((r >> 1) & 7): the 16 lanes of a ds_read_b128 group read 16 different 16 B slots.
 //   V  chunk c of row r at position c ^ (((r >> 1) & 1) << 2): the 4 rows x 64 B a half-wave of ds_read_b64_tr_b16 covers
 //      lie in the four different 64 B quarters of the 64 banks.
+// Shared by the same bodies: the clamped Q^T fragment load (q_frag_ptr / load_q_frags), the exp / row-sum / convert loop of a 32-key
+// score block (exp_sum_pack); with attn.hip (attn_common.h): the reference exponent, the row-sum window test, crow and the
+// HIPTS_ATTN_CLASSIC switch; the XCD remap is vit_internal.h's xcd_work_id.  (The first / middle / last walk over the key tiles stays
+// written out in attn2_body and attn2_seq_body: as a function taking the step it changed both loops' code, LABNOTES.md.)
 #include <mutex>
 #include <type_traits>
 
-#include "vit_internal.h"
+#include "attn_common.h"      // shared with attn.hip: HIPTS_ATTN_REF_MARGIN, crow, ref_exponent, row_sum_left_window, attn_classic_switch
 
-// Head room of the half-operand fast path's reference exponent (round 4): m_ref = (the row's maximum over its first 32 keys) + this many
-// bits, so P = 2^(S - m_ref) overflows half only when a later score exceeds that maximum by 15 + MARGIN bits, and the row sum's window is
-// [2^(-1 - MARGIN), 2^15); keys more than 14 - MARGIN bits below the reference become half subnormals (their P keeps an absolute
-// precision of 2^-24, against a row sum of at least 2^-MARGIN).  With 0 a padded picture (prepare_image's white bars are the first keys of every row, tagging.py:100-120) sent most
-// query blocks through the fast pass AND the classic one: 4.6 k images/s where noise runs at 5.3 k (tools/vit_content_bench.py).
-#ifndef HIPTS_ATTN_REF_MARGIN
-#define HIPTS_ATTN_REF_MARGIN 10     // measured (tools/gpurun/r4_margin.sh), padded picture: 0 / 4 / 8 / 10 / 12 bits -> 4667 / 4979 / 5199-5298 / 5261 / 5311 images/s (noise 5340-5435 at every setting); EVA02-L 1129 / 1158 / 1164 at 8 / 10 / 12 (noise 1176); at 12 an attention test fails (the reference keys' P sits two bits above the half subnormals), at 10 the oracle check of the structured images is unchanged
-#endif
 namespace hipts {
 namespace {
 
-#ifndef HIPTS_ATTN2_ASM_ADD
-#define HIPTS_ATTN2_ASM_ADD 0       // 1: the row sums as single v_add_f32 in (non-volatile) inline asm -- what first kept hipcc from pairing them into v_pk_add_f32; the Makefile's -fno-slp-vectorize does the same without asm (with the sampled reference below the asm form came out WRONG: negative row sums, every workgroup on the fallback pass)
-#endif
-#ifndef HIPTS_ATTN_SAMPLED_REF
-#define HIPTS_ATTN_SAMPLED_REF 0     // attn2_seq_body, half operands: the reference exponent from 32 keys sampled across the sequence instead of the first 32 (then 4 bits of head room do: -DHIPTS_ATTN_REF_MARGIN=4).  Correct; alone the same 84-88 us; forward 5369 against 5400-5407 images/s on noise, 5367-5372 against 5333-5338 on the padded test picture: costs what it gains, off
-#endif
-#ifndef HIPTS_ATTN2_PV_SNAKE
-#define HIPTS_ATTN2_PV_SNAKE 0
-#endif
-#ifndef HIPTS_ATTN2_MFMA_SUM
-#define HIPTS_ATTN2_MFMA_SUM 0      // 1: the row sums as two more MFMAs per 32 keys (ones x P^T) instead of 32 v_add_f32 -- the loop is bound by vector issue, the matrix pipe ~40 % busy.  Measured and NOT usable with half operands: the MFMA reads half subnormals as zero.  In the P V product that loss is invisible (0.1-0.2 % of a peaked row's mass times the averaged V of its small keys; the default path's error is the same 1.902e-3 for 0 .. 10 bits of head room, profiles/r05_attn_margin_error.txt), but in the SUM it is a pure scale error of the row's output: a few rows of 784 come out 1.0013-1.0017 x too large = 5.9e-3 (profiles/r05_attn_mfma_sum_debug.txt; 3 = both sums side by side, they agree to 4e-5 elsewhere).  P once more as bf16 for the sum MFMAs alone fails too (9e-3: a peaked row's sum is only as good as its largest term's 8 mantissa bits)
-#endif
 #ifndef HIPTS_ATTN2_SEQ_WAVES
 #define HIPTS_ATTN2_SEQ_WAVES 3          // waves per SIMD the sequential body (MODE 1) is compiled for: 4 -> 128 registers, 3 -> 168
 #endif
 constexpr int KV = 64;                   // keys per tile
 constexpr int HD = 64;
 constexpr int TILE = KV * HD * 2;        // 8 KiB
-#ifndef HIPTS_ATTN2_SEQ_SLOTS
-#define HIPTS_ATTN2_SEQ_SLOTS 2
-#endif
 constexpr int NSK = 3, NSV = 3;          // ring slots: K two tiles ahead, V one (its tile t - 1 is still being multiplied during step t)
+constexpr int SNS = 2;                   // ring slots per operand of the sequential body (MODE 1): one tile in flight
 constexpr int V_BASE = NSK * TILE;
 constexpr int LDS_BYTES = (NSK + NSV) * TILE;      // 48 KiB: three workgroups per CU
 
@@ -78,8 +63,6 @@ __device__ unsigned long long g_attn2_stamps[4096];
 #define HIPTS_STAMP(slot) do { } while (0)
 #endif
 
-__device__ __forceinline__ int crow(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
-
 __device__ __forceinline__ void glds16(const void* g, void* lds) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
 }
@@ -96,6 +79,56 @@ __device__ __forceinline__ void wait_vm() {
     else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else static_assert(N < 0, "unsupported count");
+}
+
+// ---- the K image: a tile is 64 key rows of 128 B; chunk c (16 B) of row r sits at position c ^ ((r >> 1) & 7).
+// k_src_chunk: the source chunk that the DMA lane `lane` (which fills position lane & 7 of its row) fetches for key row `row`.
+// k_frag_addrs: byte addresses from `base` (the tile's first half; + 4096 for the second) of the A-operand fragments of lane (r = lane & 31,
+// h = lane >> 5): key row r, logical chunk 2 s + h of k-step s.  (r and h come from the caller, which has them anyway: computed here from
+// the lane, hipcc folds them differently and nine of the ten attn2_kernel instantiations come out with other register counts.)
+__device__ __forceinline__ int k_src_chunk(int row, int lane) { return (lane & 7) ^ ((row >> 1) & 7); }
+template <class T>
+__device__ __forceinline__ void k_frag_addrs(int r, int h, T base, T (&ka)[4]) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) ka[s] = base + r * 128 + (((2 * s + h) ^ ((r >> 1) & 7)) * 16);
+}
+// ---- the V image: chunk c of row r at position c ^ (((r >> 1) & 1) << 2).
+// v_frag_addrs: what ds_read_b64_tr_b16 reads for the V^T fragments: lane 4 qd + p of a 16-lane group -> row 4 h + qd (+ 8, 16, 24 and
+// + 32 g by the caller), columns 16 dgrp + 4 p .. + 3 (+ 32 blk).
+__device__ __forceinline__ int v_src_chunk(int row, int lane) { return (lane & 7) ^ (((row >> 1) & 1) << 2); }
+template <class T>
+__device__ __forceinline__ void v_frag_addrs(int lane, int h, T base, T (&va)[2]) {
+    const int l16 = lane & 15, qd = l16 >> 2, p = l16 & 3, dgrp = (lane >> 4) & 1;
+    const int x = qd >> 1;                       // ((row >> 1) & 1) for row = 4 h + qd (+ multiples of 8)
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk) va[blk] = base + (4 * h + qd) * 128 + (2 * dgrp + (p >> 1) + 4 * (blk ^ x)) * 16 + (p & 1) * 8;
+}
+
+// Q^T fragments (B operand) of query row `qrow` (rows past tokens_pad read the last row; they are never stored): lane half h, k-step s:
+// d = 16 s + 8 h .. + 7 at q_frag_ptr(...) + 16 s
+__device__ __forceinline__ const bf16_t* q_frag_ptr(const bf16_t* q, int bh, int tokens_pad, int qrow, int h) {
+    qrow = qrow < tokens_pad ? qrow : tokens_pad - 1;
+    return q + ((size_t)bh * tokens_pad + qrow) * HD + 8 * h;
+}
+__device__ __forceinline__ void load_q_frags(const bf16_t* q, int bh, int tokens_pad, int qrow, int h, bf16x8 (&qf)[4]) {
+    const bf16_t* qp = q_frag_ptr(q, bh, tokens_pad, qrow, h);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
+}
+
+// 16 scores of a 32-key block -> P = 2^(S - m_ref) (PRESUB: the accumulator started at -m_ref; bf16 operands: m_ref = 0, nothing to
+// subtract) as operand words w0 (keys crow(0 .. 7)) / w1 (crow(8 .. 15)), the row sum in two alternating partial sums.
+// (sacc by value: by reference the two-block geometry, QB = 2, came out with other registers and 256 instead of 80 B of scratch.)
+template <bool F16, bool PRESUB>
+__device__ __forceinline__ void exp_sum_pack(const f32x16 sacc, const float m_ref, bf16x8& w0, bf16x8& w1, float& ls0, float& ls1) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float p0 = __builtin_amdgcn_exp2f((F16 && !PRESUB) ? sacc[i] - m_ref : sacc[i]);
+        const float p1 = __builtin_amdgcn_exp2f((F16 && !PRESUB) ? sacc[8 + i] - m_ref : sacc[8 + i]);
+        if (i & 1) ls1 += p0 + p1; else ls0 += p0 + p1;
+        w0[i] = to_op<F16>(p0);
+        w1[i] = to_op<F16>(p1);
+    }
 }
 
 // One workgroup's pass over its query blocks with the fixed-reference softmax.  Returns true when a row sum left its window
@@ -156,8 +189,8 @@ __device__ __forceinline__ bool attn2_body(char* __restrict__ smem, const bf16_t
     for (int pc = 0; pc < PCS; ++pc) {
         const int piece = wave + NW * pc;
         const int row = piece * 8 + (lane >> 3);
-        kg[pc] = k + ((size_t)bh * tokens_pad + row) * HD + (((lane & 7) ^ ((row >> 1) & 7)) * 8);
-        vg[pc] = v + ((size_t)bh * tokens_pad + row) * HD + (((lane & 7) ^ (((row >> 1) & 1) << 2)) * 8);
+        kg[pc] = k + ((size_t)bh * tokens_pad + row) * HD + k_src_chunk(row, lane) * 8;
+        vg[pc] = v + ((size_t)bh * tokens_pad + row) * HD + v_src_chunk(row, lane) * 8;
         dst[pc] = piece * 1024;
     }
     auto stage_k = [&](int t) __attribute__((always_inline)) {                      // tile t -> K slot t % 3
@@ -169,32 +202,17 @@ __device__ __forceinline__ bool attn2_body(char* __restrict__ smem, const bf16_t
         for (int pc = 0; pc < PCS; ++pc) glds16(vg[pc] + (size_t)t * (KV * HD), smem + V_BASE + (t % NSV) * TILE + dst[pc]);
     };
 
-    // ---- Q^T fragments (B operand): lane (query r, half h), k-step s: d = 16 s + 8 h .. + 7
     bf16x8 qf[QB][4];
 #pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
-        int qrow = q0 + 32 * qb + r;
-        qrow = qrow < tokens_pad ? qrow : tokens_pad - 1;
-        const bf16_t* qp = q + ((size_t)bh * tokens_pad + qrow) * HD + 8 * h;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) qf[qb][s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
-    }
+    for (int qb = 0; qb < QB; ++qb) load_q_frags(q, bh, tokens_pad, q0 + 32 * qb + r, h, qf[qb]);
     const int nkv = tokens_pad / KV;
     stage_k(0);                                      // issue order K0 V0 K1 | step 0: V1 K2 | step 1: V2 K3 | ...: at the top of step t the
     stage_v(0);                                      // youngest requests are K(t + 1)'s, everything older -- K(t), V(t) -- is what vmcnt(PCS) waits for
     if (nkv > 1) stage_k(1);
 
-    // ---- fragment addresses inside a tile
-    int ka[4];                                       // K row r, logical chunk 2 s + h
-#pragma unroll
-    for (int s = 0; s < 4; ++s) ka[s] = r * 128 + (((2 * s + h) ^ ((r >> 1) & 7)) * 16);
-    int va[2];                                       // V: lane 4 qd + p of a 16-lane group -> row 4 h + qd, columns 16 dgrp + 4 p .. + 3 (+ 32 blk)
-    {
-        const int l16 = lane & 15, qd = l16 >> 2, p = l16 & 3, dgrp = (lane >> 4) & 1;
-        const int x = qd >> 1;                       // ((row >> 1) & 1) for row = 4 h + qd (+ multiples of 8)
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk) va[blk] = (4 * h + qd) * 128 + (2 * dgrp + (p >> 1) + 4 * (blk ^ x)) * 16 + (p & 1) * 8;
-    }
+    int ka[4], va[2];                                // fragment addresses inside a tile
+    k_frag_addrs(r, h, 0, ka);
+    v_frag_addrs(lane, h, 0, va);
 
     f32x16 o[QB][2], sacc[QB][2];
     bf16x8 pf[QB][2][2];
@@ -256,26 +274,12 @@ __device__ __forceinline__ bool attn2_body(char* __restrict__ smem, const bf16_t
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) {
             {
-                if constexpr (F16 && FIRST) {
-                    float mx = sacc[qb][0][0];
-#pragma unroll
-                    for (int g = 0; g < GH; ++g)
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[qb][g][i]);
-                    m_ref[qb] = fmaxf(mx, __shfl_xor(mx, 32)) + (float)HIPTS_ATTN_REF_MARGIN;      // finite: tile 0 holds at least one unmasked key
-                }
+                if constexpr (F16 && FIRST) m_ref[qb] = ref_exponent<GH>(sacc[qb]);
                 float ls0 = 0.f, ls1 = 0.f;
 #pragma unroll
                 for (int g = 0; g < GH; ++g) {
                     bf16x8 w0, w1;                    // whole-vector writes into pf: element-wise writes sent the array to scratch memory (QB = 2)
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const float p0 = __builtin_amdgcn_exp2f(F16 ? sacc[qb][g][i] - m_ref[qb] : sacc[qb][g][i]);
-                        const float p1 = __builtin_amdgcn_exp2f(F16 ? sacc[qb][g][8 + i] - m_ref[qb] : sacc[qb][g][8 + i]);
-                        if (i & 1) ls1 += p0 + p1; else ls0 += p0 + p1;
-                        w0[i] = to_op<F16>(p0);
-                        w1[i] = to_op<F16>(p1);
-                    }
+                    exp_sum_pack<F16, false>(sacc[qb][g], m_ref[qb], w0, w1, ls0, ls1);
                     pf[qb][g][0] = w0;
                     pf[qb][g][1] = w1;
                 }
@@ -327,11 +331,7 @@ __device__ __forceinline__ bool attn2_body(char* __restrict__ smem, const bf16_t
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
         const float l_tot = l_run[qb] + __shfl_xor(l_run[qb], 32);
-        {   // 0.5 <= l < 2^15 (half) / 2^-100 <= l < 2^100 (bf16) on the bit pattern: a NaN or a negative value fails whatever -fno-honor-nans assumes
-            const uint32_t lb = __float_as_uint(l_tot);
-            constexpr uint32_t LO = F16 ? 0x3f000000u - ((uint32_t)HIPTS_ATTN_REF_MARGIN << 23) : 0x0d800000u, HI = F16 ? 0x47000000u : 0x71800000u;
-            if (!(lb >= LO && lb < HI)) bad = true;
-        }
+        if (row_sum_left_window<F16>(l_tot)) bad = true;
         l_run[qb] = 1.0f / l_tot;
     }
     if (__builtin_amdgcn_ballot_w64(bad) != 0) return true;      // wave-uniform: the lane swaps below need every lane
@@ -360,7 +360,6 @@ __device__ __forceinline__ bool attn2_seq_body(char* __restrict__ smem, const bf
                                                const bf16_t* __restrict__ v, bf16_t* __restrict__ out, int heads, int tokens, int tokens_pad,
                                                int bh, int blk0, int nblk, int out_stride, int out_ld, int lo_off, float lo_scale) {
     constexpr int PCS = 8 / NW;
-    constexpr int SNS = HIPTS_ATTN2_SEQ_SLOTS;       // ring slots per operand: 2 = one tile in flight, 3 = two
     constexpr int VB = SNS * TILE;                   // V slots behind the K slots
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // in an SGPR: LDS-DMA bases and the active test stay scalar
@@ -377,8 +376,8 @@ __device__ __forceinline__ bool attn2_seq_body(char* __restrict__ smem, const bf
 #pragma unroll
     for (int pc = 0; pc < PCS; ++pc) {
         const int row = (wave + NW * pc) * 8 + (lane >> 3);
-        kgo[pc] = row * HD + (((lane & 7) ^ ((row >> 1) & 7)) * 8);
-        vgo[pc] = row * HD + (((lane & 7) ^ (((row >> 1) & 1) << 2)) * 8);
+        kgo[pc] = row * HD + k_src_chunk(row, lane) * 8;
+        vgo[pc] = row * HD + v_src_chunk(row, lane) * 8;
     }
     const bf16_t* kb = k + (size_t)bh * tokens_pad * HD;
     const bf16_t* vb = v + (size_t)bh * tokens_pad * HD;
@@ -390,60 +389,17 @@ __device__ __forceinline__ bool attn2_seq_body(char* __restrict__ smem, const bf
         for (int pc = 0; pc < PCS; ++pc) glds16(vb + (size_t)t * (KV * HD) + vgo[pc], smem + VB + sl + (wave + NW * pc) * 1024);
     };
     bf16x8 qf[4];
-    {
-        int qrow = q0 + r;
-        qrow = qrow < tokens_pad ? qrow : tokens_pad - 1;
-        const bf16_t* qp = q + ((size_t)bh * tokens_pad + qrow) * HD + 8 * h;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
-    }
+    load_q_frags(q, bh, tokens_pad, q0 + r, h, qf);
     stage(0);
-    if (SNS == 3 && nkv > 1) stage(1);
-    int ka[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) ka[s] = r * 128 + (((2 * s + h) ^ ((r >> 1) & 7)) * 16);
-    int va[2];
-    {
-        const int l16 = lane & 15, qd = l16 >> 2, p = l16 & 3, dgrp = (lane >> 4) & 1;
-        const int x = qd >> 1;
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk) va[blk] = VB + (4 * h + qd) * 128 + (2 * dgrp + (p >> 1) + 4 * (blk ^ x)) * 16 + (p & 1) * 8;
-    }
+    int ka[4], va[2];
+    k_frag_addrs(r, h, 0, ka);
+    v_frag_addrs(lane, h, VB, va);
     f32x16 o[2];
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk)
 #pragma unroll
         for (int i = 0; i < 16; ++i) o[blk][i] = 0.f;
     float l_run = 0.f, m_ref = 0.f;
-#if HIPTS_ATTN_SAMPLED_REF
-    if constexpr (F16) {
-        // The reference exponent of the half-operand fast path: this row's maximum over 32 keys SAMPLED across the sequence (one extra
-        // 32 x 32 score block, the K rows straight from memory in the A-operand layout) + the head room.  The first keys' maximum was
-        // the bar of a padded picture; a sample sees what the row will meet, so the head room can be smaller and fewer P fall below
-        // half's normal range (the MFMA reads half subnormals as zero).
-        const int stride = tokens >= 32 ? tokens / 32 : 1;
-        int krow = r * stride + (stride >> 1);
-        krow = krow < tokens ? krow : tokens - 1;
-        const bf16_t* kp = kb + (size_t)krow * HD + 8 * h;
-        f32x16 sref;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sref[i] = 0.f;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) sref = mfma_32x32x16<F16>(*reinterpret_cast<const bf16x8*>(kp + 16 * s), qf[s], sref);
-        float mx = sref[0];
-#pragma unroll
-        for (int i = 1; i < 16; ++i) mx = fmaxf(mx, sref[i]);
-        m_ref = fmaxf(mx, __shfl_xor(mx, 32)) + (float)HIPTS_ATTN_REF_MARGIN;
-    }
-#endif
-#if HIPTS_ATTN2_MFMA_SUM
-    f32x16 lacc;                                     // every row: the sum over the keys of P[key][query r]
-    bf16x8 ones;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) lacc[i] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ones[i] = to_op<F16>(1.0f);
-#endif
     const int tail_keys = tokens - (nkv - 1) * KV;
     using T_ = std::true_type;
     using F_ = std::false_type;
@@ -469,7 +425,7 @@ __device__ __forceinline__ bool attn2_seq_body(char* __restrict__ smem, const bf
     // loop; 32 v_sub per tile otherwise).  The very first half (FIRST) defines m_ref and subtracts explicitly.
     auto s_mfma = [&](const bf16x8 (&kf)[4], int t, int g, f32x16& sacc, auto first_c, auto last_c) __attribute__((always_inline)) {
         constexpr bool FIRST = decltype(first_c)::value, LAST = decltype(last_c)::value;
-        constexpr bool PRESUB = F16 && (!FIRST || HIPTS_ATTN_SAMPLED_REF);
+        constexpr bool PRESUB = F16 && !FIRST;
         const float c0 = PRESUB ? -m_ref : 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -481,76 +437,30 @@ __device__ __forceinline__ bool attn2_seq_body(char* __restrict__ smem, const bf
     };
     auto soft = [&](const f32x16& sacc, bf16x8& w0, bf16x8& w1, auto first_c) __attribute__((always_inline)) {
         constexpr bool FIRST = decltype(first_c)::value;
-        constexpr bool PRESUB = F16 && (!FIRST || HIPTS_ATTN_SAMPLED_REF);
-        if constexpr (F16 && FIRST && !HIPTS_ATTN_SAMPLED_REF) {                // the reference: this row's maximum over the first 32 keys
-            float mx = sacc[0];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) mx = fmaxf(mx, sacc[i]);
-            m_ref = fmaxf(mx, __shfl_xor(mx, 32)) + (float)HIPTS_ATTN_REF_MARGIN;
-        }
+        constexpr bool PRESUB = F16 && !FIRST;
+        if constexpr (F16 && FIRST) m_ref = ref_exponent<1>(&sacc);      // the reference: this row's maximum over the first 32 keys
         float ls0 = 0.f, ls1 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-#ifdef HIPTS_X_NOEXP
-            const float p0 = (F16 && !PRESUB) ? sacc[i] - m_ref : sacc[i], p1 = (F16 && !PRESUB) ? sacc[8 + i] - m_ref : sacc[8 + i];
-#else
-            const float p0 = __builtin_amdgcn_exp2f((F16 && !PRESUB) ? sacc[i] - m_ref : sacc[i]);
-            const float p1 = __builtin_amdgcn_exp2f((F16 && !PRESUB) ? sacc[8 + i] - m_ref : sacc[8 + i]);
-#endif
-#if HIPTS_ATTN2_MFMA_SUM == 1
-#elif !defined(HIPTS_X_NOSUM)
-#if HIPTS_ATTN2_ASM_ADD
-            asm("v_add_f32 %0, %0, %1" : "+v"(ls0) : "v"(p0));      // single adds: hipcc pairs plain ones into v_pk_add_f32, which costs more issue cycles than two v_add_f32
-            asm("v_add_f32 %0, %0, %1" : "+v"(ls1) : "v"(p1));
-#else
-            if (i & 1) ls1 += p0 + p1; else ls0 += p0 + p1;
-#endif
-#endif
-            w0[i] = to_op<F16>(p0);
-            w1[i] = to_op<F16>(p1);
-        }
-#ifdef HIPTS_X_NOSUM
-        ls0 = sacc[0];
-#endif
+        exp_sum_pack<F16, PRESUB>(sacc, m_ref, w0, w1, ls0, ls1);
         l_run += ls0 + ls1;
     };
     auto pv = [&](const bf16x8 (&vf)[2][2], const bf16x8& w0, const bf16x8& w1) __attribute__((always_inline)) {
-#if HIPTS_ATTN2_PV_SNAKE      // every MFMA shares an operand with its predecessor (gemm.hip: HIPTS_MFMA_ORDER); same chain per accumulator, same bits
-        o[0] = mfma_32x32x16<F16>(vf[0][0], w0, o[0]);
-        o[1] = mfma_32x32x16<F16>(vf[1][0], w0, o[1]);
-        o[1] = mfma_32x32x16<F16>(vf[1][1], w1, o[1]);
-        o[0] = mfma_32x32x16<F16>(vf[0][1], w1, o[0]);
-#else
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk) {
             o[blk] = mfma_32x32x16<F16>(vf[blk][0], w0, o[blk]);
             o[blk] = mfma_32x32x16<F16>(vf[blk][1], w1, o[blk]);
         }
-#endif
-#if HIPTS_ATTN2_MFMA_SUM
-        lacc = mfma_32x32x16<F16>(ones, w0, lacc);
-        lacc = mfma_32x32x16<F16>(ones, w1, lacc);
-#endif
     };
     auto step = [&](int t, auto first_c, auto last_c) __attribute__((always_inline)) {
         constexpr bool LAST = decltype(last_c)::value;
         HIPTS_STAMP(t * 16 + 0);
-        // tile t (requested SNS - 1 steps ago) has landed for this wave; with three slots tile t + 1's pieces stay in flight ...
-        if (SNS == 3 && t + 1 < nkv) wait_vm<2 * PCS>();
-        else wait_vm<0>();
+        wait_vm<0>();                                // tile t (requested one step ago) has landed for this wave ...
         HIPTS_STAMP(t * 16 + 5);
-#ifndef HIPTS_X_NOBARRIER                            // (HIPTS_X_*: measurement-only builds, tools/gpurun/r3_attn_x.sh -- results are wrong with them)
         __builtin_amdgcn_s_barrier();                // ... and for every wave; tile t - 1's slots are free
-#endif
         HIPTS_STAMP(t * 16 + 6);
-#ifdef HIPTS_X_NODMA
-        if (t == 0)
-#endif
         if (t + SNS - 1 < nkv) stage(t + SNS - 1);
         if (!active) return;
         HIPTS_STAMP(t * 16 + 1);
         int sl = (t % SNS) * TILE;
-        if (SNS == 3) asm volatile("" : "+s"(sl));      // a per-step scalar: three hoisted sets of LDS addresses would not fit the register budget
         const bool two = !(LAST && tail_keys <= 32);
         bf16x8 kf0[4], kf1[4], vf[2][2], w0, w1;
         f32x16 sacc;
@@ -561,21 +471,15 @@ __device__ __forceinline__ bool attn2_seq_body(char* __restrict__ smem, const bf
         HIPTS_STAMP(t * 16 + 2);
         v_reads(sl, 0, vf);
         __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);       // 8 DS reads (transposed)
-#ifndef HIPTS_ATTN2_NO_KPREFETCH
         if (two) {
             k_reads(sl, 1, kf1);
             __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
         }
-#endif
         soft(sacc, w0, w1, first_c);
         HIPTS_STAMP(t * 16 + 3);
         pv(vf, w0, w1);
         HIPTS_STAMP(t * 16 + 4);
         if (two) {
-#ifdef HIPTS_ATTN2_NO_KPREFETCH
-            k_reads(sl, 1, kf1);
-            __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-#endif
             s_mfma(kf1, t, 1, sacc, F_{}, last_c);
             __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
             HIPTS_STAMP(t * 16 + 10);
@@ -595,23 +499,8 @@ __device__ __forceinline__ bool attn2_seq_body(char* __restrict__ smem, const bf
     }
     if (!active) return false;
 
-#if HIPTS_ATTN2_MFMA_SUM == 3
     const float l_tot = l_run + __shfl_xor(l_run, 32);
-    if (blockIdx.x < 2 && wave == 0 && (lane == 0 || lane == 1 || lane == 33)) printf("blk %d lane %d: adds %.9g  mfma %.9g %.9g %.9g\n", (int)blockIdx.x, lane, l_tot, lacc[0], lacc[5], lacc[15]);
-#elif HIPTS_ATTN2_MFMA_SUM
-    const float l_tot = lacc[0];                     // over all keys already (the MFMA sums the two lane halves' keys)
-#else
-    const float l_tot = l_run + __shfl_xor(l_run, 32);
-#endif
-    bool bad;
-    {
-        const uint32_t lb = __float_as_uint(l_tot);
-        constexpr uint32_t LO = F16 ? 0x3f000000u - ((uint32_t)HIPTS_ATTN_REF_MARGIN << 23) : 0x0d800000u, HI = F16 ? 0x47000000u : 0x71800000u;
-        bad = !(lb >= LO && lb < HI);
-    }
-#ifndef HIPTS_X_NOFALLBACK
-    if (__builtin_amdgcn_ballot_w64(bad) != 0) return true;
-#endif
+    if (__builtin_amdgcn_ballot_w64(row_sum_left_window<F16>(l_tot)) != 0) return true;
     const float inv = 1.0f / l_tot;
     const int qi = q0 + r;
     bf16_t* op = out + ((size_t)b * out_stride + qi) * out_ld + head * HD;
@@ -637,25 +526,14 @@ __device__ __forceinline__ void attn2_classic(char* __restrict__ smem, const bf1
     const int r = lane & 31, h = lane >> 5;
     const int b = bh / heads, head = bh - b * heads;
     const int nkv = tokens_pad / KV;
-    int ka[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) ka[s] = r * 128 + (((2 * s + h) ^ ((r >> 1) & 7)) * 16);
-    int va[2];
-    {
-        const int l16 = lane & 15, qd = l16 >> 2, p = l16 & 3, dgrp = (lane >> 4) & 1;
-        const int x = qd >> 1;
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk) va[blk] = (4 * h + qd) * 128 + (2 * dgrp + (p >> 1) + 4 * (blk ^ x)) * 16 + (p & 1) * 8;
-    }
+    int ka[4], va[2];
+    k_frag_addrs(r, h, 0, ka);
+    v_frag_addrs(lane, h, 0, va);
     for (int qb = 0; qb < QB; ++qb) {
         const int q0 = wave_blk0 >= 0 ? (wave_blk0 + qb) * 32 : (blk0 + wave) * (32 * QB) + 32 * qb;
         const bool active = wave_blk0 >= 0 ? qb < wave_nq : wave < nblk;
-        int qrow = q0 + r;
-        qrow = qrow < tokens_pad ? qrow : tokens_pad - 1;
-        const bf16_t* qp = q + ((size_t)bh * tokens_pad + qrow) * HD + 8 * h;
         bf16x8 qf[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
+        load_q_frags(q, bh, tokens_pad, q0 + r, h, qf);
         f32x16 o[2];
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk)
@@ -669,8 +547,8 @@ __device__ __forceinline__ void attn2_classic(char* __restrict__ smem, const bf1
                 const int piece = wave + NW * pc;
                 const int row = piece * 8 + (lane >> 3);
                 const size_t g0 = ((size_t)bh * tokens_pad + (size_t)t * KV + row) * HD;
-                glds16(k + g0 + (((lane & 7) ^ ((row >> 1) & 7)) * 8), smem + piece * 1024);
-                glds16(v + g0 + (((lane & 7) ^ (((row >> 1) & 1) << 2)) * 8), smem + V_BASE + piece * 1024);
+                glds16(k + g0 + k_src_chunk(row, lane) * 8, smem + piece * 1024);
+                glds16(v + g0 + v_src_chunk(row, lane) * 8, smem + V_BASE + piece * 1024);
             }
             wait_vm<0>();
             __syncthreads();
@@ -747,16 +625,12 @@ __global__ __launch_bounds__(NW * 64, MODE == 1 ? HIPTS_ATTN2_SEQ_WAVES : 2) voi
     // ALL of the kernel's LDS is this one array (ring + the fallback flag word): with a second LDS object in the kernel -- __syncthreads_or()
     // brings one -- hipcc puts an s_waitcnt vmcnt(0) in front of the first ds_read of every tile step and the DMA ring never runs ahead
     // (cdna_hip_programming.md section 5, "three .s-level traps" (a); seen in this kernel's .s).
-    constexpr int RING = MODE == 1 ? 2 * HIPTS_ATTN2_SEQ_SLOTS * TILE : LDS_BYTES;
+    constexpr int RING = MODE == 1 ? 2 * SNS * TILE : LDS_BYTES;
     __shared__ __attribute__((aligned(16))) char smem[RING + 16];
     int* redo = reinterpret_cast<int*>(smem + RING);
     if (threadIdx.x == 0) *redo = classic;           // ordered before every reader by the barriers of the tile loop
-    // XCD-aware work id (attn.hip): the workgroups of one (image, head) stream the same K / V -- keep them on one XCD's L2
-    int wid = blockIdx.x;
-    {
-        const int nwg = gridDim.x, qd = nwg >> 3, rm = nwg & 7, xcd = wid & 7, loc = wid >> 3;
-        wid = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + loc;
-    }
+    // the workgroups of one (image, head) stream the same K / V: consecutive work ids, one XCD's L2
+    const int wid = xcd_work_id(blockIdx.x, gridDim.x);
     const int bh = wid / chunks, c = wid - bh * chunks;
     const int nb = (tokens + 32 * QB - 1) / (32 * QB);              // query blocks of the (image, head), dealt evenly to its workgroups
     const int blk0 = (c * nb) / chunks, nblk = ((c + 1) * nb) / chunks - blk0;
@@ -797,8 +671,7 @@ __global__ __launch_bounds__(256, 1) void attn3_kernel(const bf16_t* __restrict_
     // XCD-aware item -> work id (attn.hip): the chunks of one (image, head) stream the same K / V -- same XCD, same round.  The chunk roles
     // rotate with the round, so that the workgroup that had the larger chunk (a wave with four blocks) gets a smaller one next.
     auto item_bh = [&](int item, int round, int& c) __attribute__((always_inline)) -> int {
-        const int qd = nitems >> 3, rm = nitems & 7, xcd = item & 7, loc = item >> 3;
-        const int wid = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + loc;
+        const int wid = xcd_work_id(item, nitems);
         const int bh = wid / chunks;
         c = (wid - bh * chunks + round) % chunks;
         return bh;
@@ -881,7 +754,7 @@ int launch_attention2(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t*
     // split_lo: rows of `out` are [hi (heads * 64) | lo (heads * 64)] -- the output as a hi | lo pair of 16-bit halves
     const int out_ld = split_lo ? 2 * heads * HD : heads * HD, lo_off = split_lo ? heads * HD : 0;
     HIPTS_REQUIRE(tokens_pad % KV == 0 && tokens_pad >= tokens && tokens >= 1, "attention: tokens_pad must be a multiple of %d", KV);
-    static const int classic = (getenv("HIPTS_ATTN_CLASSIC") && atoi(getenv("HIPTS_ATTN_CLASSIC"))) ? 1 : 0;
+    const int classic = attn_classic_switch();
     static const int env_variant = getenv("HIPTS_ATTN2") ? atoi(getenv("HIPTS_ATTN2")) : 0;
     if (variant == 0) variant = env_variant ? env_variant : 5;
 #define HIPTS_ATTN2_CASE(QB_, NW_, MODE_)                                                                                        \

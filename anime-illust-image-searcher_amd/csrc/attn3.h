@@ -1,6 +1,7 @@
 // attn3.h -- the head_dim-64 attention with ONE wave per SIMD and a hand-placed instruction stream (round 5; timm Attention inside
 // tagging.py:174).  Included by attn2.hip inside namespace hipts { namespace { -- it shares attn2's LDS images, fragment layouts, fixed
-// reference softmax, output path and fallback.
+// reference softmax, output path and fallback: the DMA's source swizzle is attn2.hip's k_src_chunk / v_src_chunk, the Q^T row its
+// q_frag_ptr, the window test attn_common.h's row_sum_left_window.
 //
 // What differs from attn2_seq_body (three waves per SIMD, 32 query rows per wave, the hardware left to overlap one wave's softmax with
 // another's MFMAs: the matrix pipe ~40 % busy):
@@ -296,8 +297,8 @@ __device__ __forceinline__ bool attn3_body(unsigned lds0, const bf16_t* __restri
 #pragma unroll
     for (int pc = 0; pc < 2; ++pc) {
         const int row = (wave + 4 * pc) * 8 + (lane >> 3);
-        d.kvo[pc] = (unsigned)(row * HD + (((lane & 7) ^ ((row >> 1) & 7)) * 8)) * 2u;
-        d.vvo[pc] = (unsigned)(row * HD + (((lane & 7) ^ (((row >> 1) & 1) << 2)) * 8)) * 2u;
+        d.kvo[pc] = (unsigned)(row * HD + k_src_chunk(row, lane) * 8) * 2u;
+        d.vvo[pc] = (unsigned)(row * HD + v_src_chunk(row, lane) * 8) * 2u;
     }
 #ifdef HIPTS_A3_STAMPS
 #ifndef HIPTS_A3_STAMP_WAVE
@@ -331,9 +332,7 @@ __device__ __forceinline__ bool attn3_body(unsigned lds0, const bf16_t* __restri
     // waited for together with the epilogue stores of the previous item in front of B_0 (the compiler knows nothing of these loads)
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
-        int qrow = q0 + 32 * qb + r;
-        qrow = qrow < tokens_pad ? qrow : tokens_pad - 1;
-        const bf16_t* qp = q + ((size_t)bh * tokens_pad + qrow) * HD + 8 * h;
+        const bf16_t* qp = q_frag_ptr(q, bh, tokens_pad, q0 + 32 * qb + r, h);
         A3_QLOAD(R.Q[qb][0], qp, 0);
         A3_QLOAD(R.Q[qb][1], qp, 32);
         A3_QLOAD(R.Q[qb][2], qp, 64);
@@ -346,7 +345,7 @@ __device__ __forceinline__ bool attn3_body(unsigned lds0, const bf16_t* __restri
 #pragma unroll
             for (int i = 0; i < 16; ++i) R.O[qb][blk][i] = 0.f;
     }
-    // fragment addresses inside a tile (attn2_seq_body's)
+    // fragment addresses inside a tile: attn2.hip's k_frag_addrs / v_frag_addrs, written out (see the note at the head of attn2.hip)
     unsigned ka[4], va[2];
 #pragma unroll
     for (int s = 0; s < 4; ++s) ka[s] = lds0 + r * 128 + (((2 * s + h) ^ ((r >> 1) & 7)) * 16);
@@ -463,9 +462,7 @@ __device__ __forceinline__ bool attn3_body(unsigned lds0, const bf16_t* __restri
         for (int qb = 0; qb < QB; ++qb) {
             const float ls = R.l0[qb] + R.l1[qb];
             const float l_tot = ls + __shfl_xor(ls, 32);
-            const uint32_t lb = __float_as_uint(l_tot);
-            constexpr uint32_t LO = F16 ? 0x3f000000u - ((uint32_t)HIPTS_ATTN_REF_MARGIN << 23) : 0x0d800000u, HI = F16 ? 0x47000000u : 0x71800000u;
-            if (qb < nq && !(lb >= LO && lb < HI)) bad = true;
+            if (qb < nq && row_sum_left_window<F16>(l_tot)) bad = true;
             inv[qb] = 1.0f / l_tot;
         }
         A3_STAMP(2);

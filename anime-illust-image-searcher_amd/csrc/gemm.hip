@@ -56,11 +56,7 @@ __global__ __launch_bounds__(512) void gemm_kernel(const GemmArgs a, int tiles_m
 
     // XCD-aware, bijective remap of the workgroup id (8 XCDs, round-robin dispatch)
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const int bid = xcd_work_id(blockIdx.x, nwg);
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     const int K = a.K, nt = K / BK;
@@ -172,8 +168,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(HIPTS_INT_DEPTH
     // hands neighbouring tiles to the workgroups that share an L2.
     const int nwg = tiles_m * tiles_n;
     auto tile_origin = [&](int id, int& m0, int& n0) {
-        const int q = nwg >> 3, r = nwg & 7, xcd = id & 7, loc = id >> 3;
-        const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+        const int bid = xcd_work_id(id, nwg);
         if (a.raster_gn > 0) {
             // Column groups outermost: all row panels x raster_gn column tiles, row-major inside the group, then the next group.
             // An XCD's contiguous chunk of the order then lies inside one group (or two): its slice of W (raster_gn panels) is all the
@@ -646,11 +641,7 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(const GemmArgs a, int til
     const int wave_m = wave >> 2, wave_n = wave & 3;
 
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const int bid = xcd_work_id(blockIdx.x, nwg);
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     const int K = a.K, nt = K / BK;
@@ -808,11 +799,7 @@ __global__ __launch_bounds__(256, 2) void gemm_s3_kernel(const GemmArgs a, int t
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave_m = wave >> 1, wave_n = wave & 1;
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const int bid = xcd_work_id(blockIdx.x, nwg);
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = tm * BM, n0 = tn * S3_BN;
     const int nt = a.K / S3_BK;
@@ -888,11 +875,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(const GemmArgs a, int t
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave_m = wave >> 1, wave_n = wave & 1;
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const int bid = xcd_work_id(blockIdx.x, nwg);
     const int tm = bid / tiles_n, tn = bid % tiles_n;
     const int m0 = tm * DW_BM, n0 = tn * DW_BN;
     const int K = a.K, nt = K / DW_BK;

@@ -194,8 +194,7 @@ __global__ __launch_bounds__(256, 1) void gemm_q4_kernel(const GemmArgs a, int t
 
     const int nwg = tiles_m * tiles_n;
     auto tile_origin = [&](int id, int& m0, int& n0) {      // as gemm_pp_kernel: XCD-aware bijective remap, then the launcher's raster
-        const int q = nwg >> 3, r = nwg & 7, xcd = id & 7, loc = id >> 3;
-        const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+        const int bid = xcd_work_id(id, nwg);
         if (a.raster_gn > 0) {
             const int per = tiles_m * a.raster_gn, grp = bid / per, rem = bid - grp * per;
             const int left = tiles_n - grp * a.raster_gn, gn = left < a.raster_gn ? left : a.raster_gn;

@@ -53,6 +53,15 @@ __device__ __forceinline__ f32x16 mfma_32x32x16(bf16x8 a, bf16x8 b, f32x16 c) {
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+// XCD-aware, bijective remap of a work id (a workgroup's blockIdx.x, or a persistent workgroup's tile / item number) among n: ids
+// are dealt round-robin over the 8 XCDs (ids equal mod 8 share an L2), so XCD x is handed the x-th contiguous eighth of 0 .. n - 1 and
+// consecutive work items -- neighbouring GEMM tiles, the query blocks of one (image, head) -- run on ONE XCD and reuse what its L2
+// holds (attention: 1.23 GB fetched per launch against 0.23 GB algorithmic before this).
+__device__ __forceinline__ int xcd_work_id(int id, int n) {
+    const int q = n >> 3, r = n & 7, xcd = id & 7, loc = id >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+}
+
 // ---- 8-bit operands (OCP e4m3fn, the gfx950 fp8; BASELINE.json configs[4]) ----
 // v_cvt_pk_fp8_f32 rounds to nearest even and turns everything above 464 into NaN (measured, tools/micro/
 // fp8_mfma.hip), so values are clamped to the largest finite e4m3 (448) first.
