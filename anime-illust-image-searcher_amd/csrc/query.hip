@@ -20,6 +20,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "bm25_index.h"
 #include "common.h"
 #include "rank_util.h"
 #include "topk.h"
@@ -30,46 +31,6 @@ using namespace hipts;
 // =============================================================================================
 // BM25
 // =============================================================================================
-struct hipts_bm25 {
-    int device = 0;
-    int64_t D = 0, nnz = 0;
-    int32_t V = 0;
-    double avgdl = 0.0;
-    std::vector<int64_t> h_ptr, h_dl, h_df;
-    std::vector<int32_t> h_term, h_tf;
-    std::vector<double> h_idf;
-    DevBuf d_ptr, d_term, d_tf, d_dl, d_idf;   // int64[D+1], int32[nnz], int32[nnz], int32[D], double[V]
-    DevBuf d_tptr, d_tdoc, d_ttf;              // term-major postings: int64[V+1], int32[nnz], int32[nnz]
-    DevBuf d_tslice;                           // int64[V][BM25_SLICES + 1]: a term's postings cut at fixed document boundaries (bm25_postings_sliced_kernel)
-    DevBuf ws_maxpart;                         // [queries][slices] partial row maxima of that kernel
-    int64_t slice_docs = 0;                    // documents per slice (a multiple of 8); 0: the index is too small to be sliced
-    DevBuf ws_q, ws_scores, ws_sims, ws_max, ws_final, ws_mark, ws_out, ws_parts;
-    PinBuf pin_in, pin_out;                    // hipts_search: one H2D of the packed queries, one D2H of the packed results
-    // hipts_search_submit / _collect (round 4): two batches in flight -- the host packs and launches batch i + 1 while the device runs batch i.
-    // The device workspaces are shared (the batches run on one stream, in order); only the pinned buffers exist per slot.
-    struct SearchSlot {
-        PinBuf pin_in, pin_out;
-        hipEvent_t done = nullptr;
-        int nq = 0, k = 0, kk = 0;
-        hipStream_t stream = nullptr;                   // the stream of the pending batch (both slots share the device workspaces: one stream)
-        bool pending = false, host_result = false;      // host_result: the one-query path ran synchronously, its results wait in ids1 / vals1
-        std::vector<int32_t> ids1;
-        std::vector<double> vals1;
-    } slot[2];
-    DevBuf s1_state;                           // one-query path: Search1State + group maxima + per-workgroup candidate slots
-    uint32_t s1_seq = 0;                       // sequence number of the last one-query call (completion flag in pinned memory)
-    bool s1_dirty = true;                      // s1_state may hold leftovers (first use, or a call that failed half way)
-    // batched hipts_search (round 4): BM25 postings on a side stream beside the index product -- the two do not depend on each other
-    hipStream_t side = nullptr;
-    hipEvent_t ev_in = nullptr, ev_bm25 = nullptr;
-    // per-kernel HIP-event timing (hipts_query_profile_*): events on the stream each kernel is launched on
-    bool prof = false;
-    struct ProfRec { int cat; hipEvent_t a, b; double bytes; };
-    std::vector<ProfRec> prof_recs;
-    std::vector<hipEvent_t> prof_pool;
-    double prof_ms[HIPTS_QUERY_PROF_CATEGORIES] = {0}, prof_bytes[HIPTS_QUERY_PROF_CATEGORIES] = {0};
-    int64_t prof_n[HIPTS_QUERY_PROF_CATEGORIES] = {0};
-};
 
 namespace {
 
@@ -1712,6 +1673,8 @@ int hipts_bm25_destroy(hipts_bm25_t* h) {
             if (sl.done) (void)hipEventDestroy(sl.done);
         if (h->ev_in) (void)hipEventDestroy(h->ev_in);
         if (h->ev_bm25) (void)hipEventDestroy(h->ev_bm25);
+        for (auto& ev : h->rel_ev)
+            if (ev) (void)hipEventDestroy(ev);
         delete h;
     }
     return HIPTS_OK;

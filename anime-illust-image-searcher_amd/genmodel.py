@@ -6,7 +6,9 @@ and the five BM25 pickles.  Like the reference (genmodel.py:159-162) it TRAINS t
 epochs, on the GPU (hipts_d2v_train) -- then infers every document vector and builds the BM25 statistics, also on the GPU.
 --epochs N shortens training and inference (tests); --d2v-mode sequential|parallel overrides the schedule that workers=1 picks
 (sequential = the reference's one-worker order, reproducible, one wavefront: small corpora; parallel = all documents of an
-epoch at once).  --synthetic-d2v skips training and builds a seeded stand-in model from the corpus counts."""
+epoch at once).  --synthetic-d2v skips training and builds a seeded stand-in model from the corpus counts.
+--related-tags K (off by default) also writes related-tags.csv: per dictionary term one line tag,rel1,rel2,... with its up to K most
+related tags (BM25Index.related: Jaccard over the documents that carry the tag, co-occurring in at least two of them)."""
 import argparse
 import copy
 import os
@@ -29,6 +31,7 @@ def main(arg_str: list) -> None:
     parser.add_argument('--epochs', type=int, default=TRAIN_EPOCHS)
     parser.add_argument('--d2v-mode', choices=['sequential', 'parallel'], default=None)
     parser.add_argument('--device', type=int, default=0)
+    parser.add_argument('--related-tags', type=int, default=0, metavar='K', help='also write related-tags.csv with K related tags per tag')
     args = parser.parse_args(arg_str)
     from hiptagsearch import synth
     from hiptagsearch.bm25 import gen_and_save_bm25_index
@@ -84,7 +87,17 @@ def main(arg_str: list) -> None:
             index = Similarity('doc2vec_index', None, model.vector_size, args.device, capacity=len(vecs))
         index.add_matrix(vecs)                                                       # :170-173 (ndarray docs: stored as given)
     index.save('doc2vec_index')                                                      # :175
-    gen_and_save_bm25_index(processed_docs_for_bm25, dictionary, args.device)        # :177
+    bm25 = gen_and_save_bm25_index(processed_docs_for_bm25, dictionary, args.device)  # :177
+    if args.related_tags > 0:
+        write_related_tags(bm25, dictionary.token2id, args.related_tags)
+
+
+def write_related_tags(bm25, token2id, k: int, path: str = 'related-tags.csv') -> None:
+    id2token = {i: t for t, i in token2id.items()}
+    ids, _, _, _ = bm25.related([((t,), ()) for t in range(bm25.vocab)], k, 'jaccard', 2)
+    with open(path, 'w', encoding='utf-8') as f:
+        for t in range(bm25.vocab):
+            f.write(','.join([id2token[t]] + [id2token[int(u)] for u in ids[t] if u >= 0]) + '\n')
 
 
 if __name__ == "__main__":

@@ -106,6 +106,8 @@ _SIGNATURES = {
     "hipts_bm25_set_idf": [c_void_p, c_void_p],
     "hipts_bm25_set_avgdl": [c_void_p, c_double],
     "hipts_bm25_score": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
+    "hipts_bm25_related": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p],
     "hipts_index_create": [c_int, c_int64, c_int, POINTER(c_void_p)],
     "hipts_index_destroy": [c_void_p],
     "hipts_index_add": [c_void_p, c_void_p, c_int64, c_int],

@@ -5,6 +5,7 @@
 The statistics pass and the scoring kernel live in libhip_tagsearch.so (csrc/query.hip).
 """
 import ctypes
+import itertools
 import pickle
 from typing import Dict, List, Optional, Sequence
 
@@ -12,6 +13,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import c_double, c_int32, c_int64, c_void_p
+
+
+RELATED_MEASURES = {"count": 0, "jaccard": 1, "lift": 2}      # HIPTS_RELATED_COUNT / _JACCARD / _LIFT
 
 
 def _csr_from_tokens(corpus: Sequence[Sequence[str]], token2id: Dict[str, int]):
@@ -97,6 +101,31 @@ class BM25Index:
         _lib.call("hipts_bm25_score", self._h, _lib.ptr(qt_a), _lib.ptr(qw_a), _lib.ptr(qp), nq, _lib.ptr(out),
                   _lib.memspace_of(out), _lib.current_stream_ptr())
         return out
+
+    def related(self, queries: Sequence, k: int, measure: str = "jaccard", min_count: int = 1):
+        """Related tags (hipts_bm25_related; the definition is in include/hip_tagsearch.h): `queries` is a sequence of
+        (include_ids, exclude_ids).  Returns ids int32 [nq, k], scores float64 [nq, k], counts int64 [nq, k] -- rows ranked by
+        (score descending, id ascending) and padded with (-1, -inf, 0) -- and matched int64 [nq], the documents each query matches."""
+        if measure not in RELATED_MEASURES:
+            raise ValueError("measure must be one of %s, not %r" % (", ".join(RELATED_MEASURES), measure))
+        nq = len(queries)
+        lists = []
+        for side in (0, 1):
+            ptr = np.zeros(nq + 1, dtype=np.int32)
+            ptr[1:] = np.cumsum(np.fromiter((len(q[side]) for q in queries), np.int64, nq))
+            flat = np.fromiter(itertools.chain.from_iterable(q[side] for q in queries), np.int64, int(ptr[-1]))
+            if flat.size and (flat.min() < -2 ** 31 or flat.max() >= 2 ** 31):
+                raise ValueError("term ids must fit int32")
+            lists.append((np.ascontiguousarray(flat if flat.size else [0], dtype=np.int32), ptr))
+        (inc, inc_ptr), (exc, exc_ptr) = lists
+        shape = (nq, max(int(k), 0))
+        ids, scores = np.empty(shape, np.int32), np.empty(shape, np.float64)
+        counts, matched = np.empty(shape, np.int64), np.empty(nq, np.int64)
+        if nq:
+            _lib.call("hipts_bm25_related", self._h, _lib.ptr(inc), _lib.ptr(inc_ptr), _lib.ptr(exc), _lib.ptr(exc_ptr), nq,
+                      RELATED_MEASURES[measure], c_int64(int(min_count)), int(k), _lib.ptr(ids), _lib.ptr(scores), _lib.ptr(counts),
+                      _lib.ptr(matched), _lib.current_stream_ptr())
+        return ids, scores, counts, matched
 
     def close(self):
         if self._h:

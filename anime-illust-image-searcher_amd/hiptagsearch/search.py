@@ -54,6 +54,22 @@ def _split_weight(tag: str):
     return ":".join(sp), None
 
 
+def parse_related_query(query: str, token2id: Dict[str, int]) -> Tuple[List[int], List[int]]:
+    """(include ids, exclude ids) of a related-tags query, in the grammar of the search box (_split_weight): a weight that starts with
+    '-' excludes its tag, every other term is included, the weight's value is ignored.  Tags are looked up as typed, like
+    parse_bm25_query (no parenthesis escaping); an unknown tag raises KeyError; ids are kept once, in order.  A query without any term
+    is the empty query, which matches every document."""
+    include: List[int] = []
+    exclude: List[int] = []
+    for term in query.split(" ") if query.strip() else []:
+        name, w = _split_weight(term)
+        side = exclude if w is not None and w.startswith("-") else include
+        t = token2id[name]
+        if t not in side:
+            side.append(t)
+    return include, exclude
+
+
 class SearchEngine:
     def __init__(self, model: Doc2VecInference, index: Similarity, token2id: Dict[str, int], bm25: BM25Index,
                  image_files_name_tags_arr: Sequence[str], search_mode: str = "normal", compat_rerank: bool = False):
@@ -120,6 +136,26 @@ class SearchEngine:
             else:
                 qw[self.token2id[name]] = 1
         return qw, required, exclude
+
+    # ---- related tags (no counterpart in the reference: its README sends the user to the tag file with grep) -------------------
+    def related_tags(self, query: str, topn: int = 20, measure: str = "jaccard", min_count: int = 1) -> List[Tuple[str, float, int]]:
+        """The tags that co-occur most with the documents `query` matches: (tag, score, count), best first.  `query` is parsed by
+        parse_related_query; counting, scoring and ranking are BM25Index.related."""
+        include, exclude = parse_related_query(query, self.token2id)
+        ids, scores, counts, _ = self.bm25.related([(include, exclude)], topn, measure, min_count)
+        id2token = self._id2token()
+        return [(id2token[int(t)], float(s), int(c)) for t, s, c in zip(ids[0], scores[0], counts[0]) if t >= 0]
+
+    def related_tags_table(self, k: int, measure: str = "jaccard", min_count: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """related_tags for every dictionary term at once: row t answers the one-tag query ([t], []).  ids int32 [V, k] and scores
+        float64 [V, k], rows padded with (-1, -inf).  One call; the library takes the queries in passes of 256."""
+        ids, scores, _, _ = self.bm25.related([((t,), ()) for t in range(self.bm25.vocab)], k, measure, min_count)
+        return ids, scores
+
+    def _id2token(self) -> Dict[int, str]:
+        if getattr(self, "_id2token_map", None) is None or len(self._id2token_map) != len(self.token2id):
+            self._id2token_map = {i: t for t, i in self.token2id.items()}
+        return self._id2token_map
 
     # ---- device scoring -------------------------------------------------------------------------
     def score_topk(self, query_weights: Sequence[Dict[int, float]], query_vectors: np.ndarray, k: int,
@@ -402,6 +438,13 @@ def find_similar_documents_batch(queries: Sequence[str], topn: int = 50) -> List
     if _engine is None:
         raise RuntimeError("no SearchEngine installed: call set_engine(load_engine()) first (webui.py:585 load_model)")
     return _engine.find_similar_documents_batch(queries, topn)
+
+
+def related_tags(query: str, topn: int = 20, measure: str = "jaccard", min_count: int = 1) -> List[Tuple[str, float, int]]:
+    """SearchEngine.related_tags on the installed engine."""
+    if _engine is None:
+        raise RuntimeError("no SearchEngine installed: call set_engine(load_engine()) first (webui.py:585 load_model)")
+    return _engine.related_tags(query, topn, measure, min_count)
 
 
 def load_engine(device: int = 0, d2v_model: str = "doc2vec_model", compat_rerank: bool = False) -> SearchEngine:

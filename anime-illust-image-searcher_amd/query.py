@@ -2,7 +2,10 @@
 """python query.py "1girl blue_eyes:+2 hat:-1" [--topn 50]     -- the webui.py query function
 (find_similar_documents, webui.py:345) without the Streamlit UI.
 python query.py --batch-file queries.txt [--topn 50]           -- one query per line, answered as one batch
-(find_similar_documents_batch); per query a "# query" header line, then the same lines."""
+(find_similar_documents_batch); per query a "# query" header line, then the same lines.
+python query.py --related "1girl hat:-1" [--topn 20] [--measure count|jaccard|lift] [--min-count N]
+-- the tags that co-occur most with the documents that carry 1girl and not hat (SearchEngine.related_tags): score<TAB>count<TAB>tag lines.
+Needs only doc2vec_dictionary and the BM25 pickles."""
 import argparse
 import os
 import sys
@@ -14,10 +17,19 @@ def main(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("query", nargs="?")
     ap.add_argument("--batch-file", help="file with one query per line (empty lines are skipped); replaces the positional query")
-    ap.add_argument("--topn", type=int, default=50)
+    ap.add_argument("--related", metavar="QUERY", help="list the tags related to this query instead of searching")
+    ap.add_argument("--measure", choices=["count", "jaccard", "lift"], default="jaccard", help="--related: how co-occurrence is scored")
+    ap.add_argument("--min-count", type=int, default=1, help="--related: drop tags that co-occur in fewer matching documents")
+    ap.add_argument("--topn", type=int, default=None, help="default 50; 20 with --related")
     ap.add_argument("--compat-rerank", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.related is not None:
+        if a.query is not None or a.batch_file is not None:
+            ap.error("--related replaces the query and --batch-file")
+        return related(a)
+    if a.topn is None:
+        a.topn = 50
     if (a.query is None) == (a.batch_file is None):
         ap.error("give either a query or --batch-file")
     from hiptagsearch import search
@@ -34,6 +46,16 @@ def main(argv):
             print("# %s" % queries[i])
         for doc_id, score in res:
             print("%.6f\t%s" % (score, eng.image_files_name_tags_arr[doc_id].split(",")[0]))
+
+
+def related(a):
+    import pickle
+    from hiptagsearch import search
+    from hiptagsearch.bm25 import load_bm25_index
+    token2id = pickle.load(open("doc2vec_dictionary", "rb")).token2id
+    eng = search.SearchEngine(None, None, token2id, load_bm25_index(a.device), [])
+    for tag, score, count in eng.related_tags(a.related, 20 if a.topn is None else a.topn, a.measure, a.min_count):
+        print("%.6f\t%d\t%s" % (score, count, tag))
 
 
 if __name__ == "__main__":

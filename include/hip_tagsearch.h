@@ -438,9 +438,34 @@ int hipts_bm25_set_avgdl(hipts_bm25_t* h, double avgdl);
  * required with weight-1000 (webui.py:154-170).  scores_out: float64 [nq][num_docs]. */
 int hipts_bm25_score(hipts_bm25_t* h, const int32_t* q_terms, const double* q_weights, const int32_t* q_ptr,
                      int nq, double* scores_out, int out_memspace, void* stream);
+/* Related tags: for each of nq queries, the terms that co-occur most with the documents the query matches (the reference has no
+ * such step; its README sends the user to the tag file with grep).  Query i includes inc_terms[inc_ptr[i] .. inc_ptr[i+1]) and
+ * excludes exc_terms[exc_ptr[i] .. exc_ptr[i+1]): distinct term ids, 0 .. 32 per list (a *_terms pointer may be NULL when its lists
+ * are all empty).
+ *   T(d)   the distinct term ids of document d, as hipts_bm25_export gives them in csr_term (tf is ignored)
+ *   M      { d : include is a subset of T(d) and exclude does not meet T(d) };  n = |M|.  Both lists empty: M is every document.
+ *          A term with df = 0 is legal in either list; a term in both lists gives n = 0.
+ *   c[u]   |{ d in M : u in T(d) }|, an exact integer
+ *   score  all operands converted from integers that are exact in a double, one rounding per operation in the order written:
+ *            HIPTS_RELATED_COUNT     (double)c
+ *            HIPTS_RELATED_JACCARD   (double)c / (double)(n + df[u] - c)             (the integer sum in int64)
+ *            HIPTS_RELATED_LIFT      ((double)c / (double)n) / ((double)df[u] / (double)D)
+ *   A term is a candidate iff c[u] >= max(min_count, 1), u is not included and u is not excluded; other terms are never scored.
+ *   Candidates rank by score descending, ties by ascending term id (the rule of hipts_topk).
+ * Outputs, host memory: ids_out int32 [nq][k], scores_out float64 [nq][k], counts_out int64 [nq][k] (c of the result), rows
+ * padded with (-1, -inf, 0); matched_out int64 [nq] = n.  HIPTS_ERR_INVALID: k outside [1, 1024], a term id outside [0, vocab),
+ * more than 32 terms in a list, an unknown measure.  Up to 256 queries share a device pass; more run in several. */
+#define HIPTS_RELATED_COUNT 0
+#define HIPTS_RELATED_JACCARD 1
+#define HIPTS_RELATED_LIFT 2
+int hipts_bm25_related(hipts_bm25_t* h, const int32_t* inc_terms, const int32_t* inc_ptr,
+                       const int32_t* exc_terms, const int32_t* exc_ptr, int nq,
+                       int measure, int64_t min_count, int k,
+                       int32_t* ids_out, double* scores_out, int64_t* counts_out,
+                       int64_t* matched_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Dense similarity index.   Replaces gensim Similarity / MatrixSimilarity as the reference
+ * Dense similarity index.  Replaces gensim Similarity / MatrixSimilarity as the reference
  * uses it: Similarity(prefix,[vec],num_features) / add_documents   genmodel.py:170-173,
  * gen_cfeatures.py:311-314;  index[query]                         webui.py:205,352;
  * vector_by_id / len                                               webui.py:306-309.

@@ -158,6 +158,9 @@ int hiptsdbg_attention2_stamps(unsigned long long* host, int n);
 int hiptsdbg_search1_last(hipts_bm25_t* h, uint32_t* candidates, uint32_t* took_candidate_path);
 /* measurement-only builds (-DHIPTS_X_TOPK_STAMPS=<workgroup>): the 16 wall-clock stamps (10 ns units) of the last batched hipts_topk launch */
 int hiptsdbg_topk_stamps(unsigned long long* host16);
+/* The last hipts_bm25_related call on this handle: the HIP-event time of its count launches (all passes) and how many work items
+ * (workgroups) took the LDS histogram arm and the direct global-atomics arm (tools/related_bench.py).  Any pointer may be NULL. */
+int hiptsdbg_related_last(const hipts_bm25_t* h, double* count_ms, int64_t* lds_items, int64_t* direct_items);
 
 #ifdef __cplusplus
 }
