@@ -149,7 +149,7 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
 // SK (round 4): the split-K tail of GemmArgs::sk_* -- work items past sk_first are (tile, K slice) pairs.  A separate instantiation, so
 // the default kernels' code is untouched.
 template <int EPI, int MR = 8, bool F16 = false, bool OP8 = false, bool SK = false, bool INT = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(HIPTS_INT_DEPTH == 3 ? 256 : 240))) void gemm_pp_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
+__global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gemm_pp_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
     static_assert(!INT || (EPI == EPI_RESID_XG && MR == 8 && !OP8 && !SK), "INT: the residual epilogue's interior form");
     static_assert(!OP8 || (F16 && MR == 8), "e4m3 operands: half 16-bit outputs, full tiles");
     static_assert(!SK || (!OP8 && MR == 8), "split-K: 16-bit operands, full tiles");
@@ -860,7 +860,7 @@ __global__ __launch_bounds__(256, 2) void gemm_s3_kernel(const GemmArgs a, int t
 // (lgkmcnt(0)) and its own loads of stage s+1 (vmcnt(6): stage s+2 stays in flight); after it slot
 // s % 3 is free for stage s+3 and stage s+1 is visible.  Every load has two steps to land.
 // LDS image: a 16-row x 32-k block is 1 KB of 64 B rows; the 16 B chunk c of row r is stored at chunk
-// c ^ ((r >> 2) & 3) (swizzle applied to the global source address, the LDS-DMA writes lane-linear),
+// c ^ Image64::swizzle(r) (gemm_epi.h; applied to the global source address, the LDS-DMA writes lane-linear),
 // which makes the 16 lanes of a ds_read_b128 phase (one k-chunk, rows 0..15) hit 16 different bank groups.
 // ---------------------------------------------------------------------------------------------
 constexpr int DW_BM = 256, DW_BN = 128, DW_BK = 32;
@@ -885,7 +885,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(const GemmArgs a, int t
     const bf16_t* src[6];
     int dst[6];
     {
-        const int r = lane >> 2, q = (lane & 3) ^ ((r >> 2) & 3);     // four lanes fetch one 64 B row segment
+        const int r = lane >> 2, q = (lane & 3) ^ Image64::swizzle(r);     // four lanes fetch one 64 B row segment
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int rb = wave * 4 + i;
@@ -903,7 +903,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(const GemmArgs a, int t
             dst[4 + i] = DW_A_BYTES + rb * 1024;
         }
     }
-    const int frag_off = (lane & 15) * 64 + (((lane >> 4) ^ (((lane & 15) >> 2) & 3)) * 16);
+    const int frag_off = (lane & 15) * 64 + (((lane >> 4) ^ Image64::swizzle(lane & 15)) * 16);
     auto issue = [&](int i, char* st) {
         glds16(src[i], st + dst[i]);
         src[i] += DW_BK;

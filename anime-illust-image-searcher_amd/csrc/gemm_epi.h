@@ -2,6 +2,17 @@
 // ping-pong loops; gemm4.hip: the 4-wave, one-wave-per-SIMD loop).  Included INSIDE `namespace hipts { namespace {` of each file:
 // every function is a forceinline device function of that translation unit.  An epilogue sees a wave-part of 16 MR rows x 64
 // columns (acc[MR][4] of 16 x 16 tiles) with its (wave_m, wave_n) coordinates in the 256 x 256 tile, whoever computed it.
+// Stated ONCE here (add to the shared piece, not a copy of it): RowImage<CHUNKS> -- the LDS row image of every staged store, where
+// a chunk is stored, the swizzle and the bank argument (Image128, Image64; no swizzle expression stands anywhere else);
+// row_sums / row_sums_to_red -- a wave's share of a row's (sum, sum of squares), add order included; ln_stat_pair -- the
+// (sum, sum of squares) -> (rstd, rstd * mean) finish; epi_bias -- the bias preamble of both entry points.
+// The entry points gemm_epilogue (arms: V^T direct, HEAD, RESID_LN, RESID_XG / XGI interior and general, the RESID / RESCALE /
+// ROWSTAT / LS read-modify-write, the plain stores) and gemm_epilogue_staged (V^T, SWIGLU, the row images of GELU / STAR / QK /
+// QK_ROPE) hold their arms as `if constexpr` branches.  An arm sees the launch's GemmArgs, the wave-part's acc[MR][4], (m0, n0,
+// wave_m, wave_n, lane), the bias in its accumulator layout (bias_v) and the entry point's optional arguments (LDS scratch /
+// image, the tile's finished row statistics st_lds, the staged per-column vectors colvec), and returns with its outputs stored.
+// Still written more than once, because stating it once changed spills or waits of the kernels (LABNOTES, "GEMM epilogues"): the
+// read-back of a 64-row pass, staged_store_2blocks beside its interior form, the stat_part finish (here, gemm.hip, gemm4.hip).
 
 constexpr int BM = 256, BN = 256, BK = 64;
 #ifndef HIPTS_STAGE_AHEAD
@@ -16,12 +27,6 @@ constexpr int BM = 256, BN = 256, BK = 64;
 #endif
 #ifndef HIPTS_STAGE_ORDER_OLD
 #define HIPTS_STAGE_ORDER_OLD 0       // 1: the previous staging order of the ping-pong loop (A/B builds)
-#endif
-#ifndef HIPTS_STAGED_INTERIOR
-#define HIPTS_STAGED_INTERIOR 1         // 0: the staged 16-bit epilogues store under per-lane predicates everywhere (A/B builds)
-#endif
-#ifndef HIPTS_INT_DEPTH
-#define HIPTS_INT_DEPTH 2
 #endif
 constexpr int TILE_BYTES = BM * BK * 2;          // 32 KiB
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;      // A + W
@@ -104,6 +109,15 @@ __device__ __forceinline__ f32x4 gelu_f4(f32x4 x, int tanh_form) {
     return x * (r + k4(0.5f));
 }
 
+// (rstd, rstd * mean) of a row from its (sum, sum of squares) over ln_dim columns: the one finish of a folded LayerNorm's statistics
+__device__ __forceinline__ float2 ln_stat_pair(const GemmArgs& a, float s1, float s2) {
+    const float inv = 1.0f / (float)a.ln_dim;
+    const float mean = s1 * inv;
+    const float var = fmaxf(s2 * inv - mean * mean, 0.f);
+    const float rstd = 1.0f / sqrtf(var + a.ln_eps);
+    return make_float2(rstd, rstd * mean);
+}
+
 // (rstd, rstd * mean) of row m for a folded LayerNorm: finished by a kernel (rowstat) or from the producer's per-tile partial
 // sums (stat_in; summed in index order, so the result does not depend on who reads it)
 __device__ __forceinline__ float2 row_stat(const GemmArgs& a, int m) {
@@ -126,11 +140,7 @@ __device__ __forceinline__ float2 row_stat(const GemmArgs& a, int m) {
             s1 += v.x;
             s2 += v.y;
         }
-        const float inv = 1.0f / (float)a.ln_dim;
-        const float mean = s1 * inv;
-        const float var = fmaxf(s2 * inv - mean * mean, 0.f);
-        const float rstd = 1.0f / sqrtf(var + a.ln_eps);
-        return make_float2(rstd, rstd * mean);
+        return ln_stat_pair(a, s1, s2);
     }
     return *reinterpret_cast<const float2*>(a.rowstat + 2 * (size_t)m);
 }
@@ -144,12 +154,7 @@ __device__ __forceinline__ void row_stat_request(const GemmArgs& a, int m, float
         pv[b] = b < a.stat_in_blocks ? *reinterpret_cast<const float2*>(a.stat_in + 2 * ((size_t)b * a.stat_in_stride + m)) : make_float2(0.f, 0.f);
 }
 __device__ __forceinline__ float2 row_stat_finish(const GemmArgs& a, const float2 (&pv)[4]) {
-    const float s1 = ((pv[0].x + pv[1].x) + pv[2].x) + pv[3].x, s2 = ((pv[0].y + pv[1].y) + pv[2].y) + pv[3].y;
-    const float inv = 1.0f / (float)a.ln_dim;
-    const float mean = s1 * inv;
-    const float var = fmaxf(s2 * inv - mean * mean, 0.f);
-    const float rstd = 1.0f / sqrtf(var + a.ln_eps);
-    return make_float2(rstd, rstd * mean);
+    return ln_stat_pair(a, ((pv[0].x + pv[1].x) + pv[2].x) + pv[3].x, ((pv[0].y + pv[1].y) + pv[2].y) + pv[3].y);
 }
 
 // HIPTS_EPI_PRIO (GemmArgs::epi_prio, A/B): the two waves of a SIMD take turns at s_setprio 1 from one epilogue step to the next.  Both are
@@ -213,16 +218,51 @@ __device__ __forceinline__ f32x4 star_relu4(f32x4 x, float s, float b, int kind 
     return r * r * s + b;
 }
 
-// Row-contiguous store of a wave's (16 MR) x 64 block of 16-bit values through a private 8 KB LDS image (the
-// mechanism of gemm_epilogue_staged, for epilogues that produce their values from a callback): lane layout
-// in = (row 16 i + lr, columns 16 j + 4 lq ..+3), out = 8 rows x 128 B per store instruction.
-template <int MR, bool F16, int P0 = 0, int P1 = 2, typename ValueOf>
+// The bias preamble of both epilogue entry points: what the caller loaded early (bias_pre), or the loads here
+template <int EPI>
+__device__ __forceinline__ void epi_bias(const GemmArgs& a, int n0, int wave_n, int lane, const f32x4* bias_pre, f32x4 (&bias_v)[4]) {
+    if (bias_pre) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bias_v[j] = bias_pre[j];
+    } else {
+        load_bias<EPI>(a, n0, wave_n, lane, bias_v);
+    }
+}
+
+// ---- The LDS row image of the staged stores.  After the main loop one stage of LDS is free, so a wave packs its output block into a
+// private image in its accumulator layout (lane = row lr of a 16-row block, 8 B or 4 B per lane and column block) and reads it back
+// row-contiguous: each global store instruction then writes whole lines instead of 16 scattered pieces.  An image row is CHUNKS
+// chunks of 16 B and logical chunk c of row `row` is stored at chunk c ^ swizzle(row):
+//   Image128 (8 chunks, 128 B = 64 16-bit columns), swizzle (row >> 1) & 7: rows alternate between the two 128 B halves of the 64
+//       banks and the XOR spreads the sixteen rows of a write (one column block, lanes lr = 0..15 per quarter) and the eight rows of
+//       a read (8 rows x 128 B per instruction) over all bank groups: both LDS passes are bank-conflict free;
+//   Image64 (4 chunks, 64 B: e4m3 rows of 64 columns, or 32 16-bit columns), swizzle (row >> 2) & 3: four rows fill the 64 banks,
+//       bank = 16 (row & 3) + 4 (chunk ^ swizzle) + (the lane's 4 B or 8 B inside the chunk): conflict-free 4 B writes, and 8 B writes
+//       per half wave; read back as 16 rows x 64 B per instruction.
+// The image is wave-private: no workgroup barrier, LDS operations of one wave execute in order.
+template <int CHUNKS>
+struct RowImage {
+    static_assert(CHUNKS == 8 || CHUNKS == 4, "128 B or 64 B rows");
+    static __device__ __forceinline__ int swizzle(int row) { return CHUNKS == 8 ? (row >> 1) & 7 : (row >> 2) & 3; }
+    // where logical chunk `chunk` of row `row` is stored
+    static __device__ __forceinline__ char* at(char* image, int row, int chunk) { return image + row * (CHUNKS * 16) + (chunk ^ swizzle(row)) * 16; }
+    // four 16-bit values of accumulator-layout lane quarter lq, 16-column block j: columns 16 j + 4 lq ..+3 of the row
+    static __device__ __forceinline__ void put4(char* image, int row, int j, int lq, bf16x4 v) {
+        *reinterpret_cast<bf16x4*>(at(image, row, j * 2 + (lq >> 1)) + (lq & 1) * 8) = v;
+    }
+};
+using Image128 = RowImage<8>;
+using Image64 = RowImage<4>;
+
+// Row-contiguous store of a wave's (16 MR) x 64 block of 16-bit values through a private 8 KB Image128, for epilogues that produce
+// their values from a callback: lane layout in = (row 16 i + lr, columns 16 j + 4 lq ..+3), out = 8 rows x 128 B per store instruction.
+template <int MR, bool F16, typename ValueOf>
 __device__ __forceinline__ void staged_store_rows(char* region, int lane, int mrow0, int M, bf16_t* out, int ld, int ncol0, int N,
                                                   ValueOf value_of) {
     const int lr = lane & 15, lq = lane >> 4, lc = lane & 7, lrow = lane >> 3;
     const bool nvl = ncol0 + lc * 8 < N;
 #pragma unroll
-    for (int pass = P0; pass < P1; ++pass) {
+    for (int pass = 0; pass < 2; ++pass) {
         if (pass) __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int ii = 0; ii < 4; ++ii) {
@@ -230,25 +270,20 @@ __device__ __forceinline__ void staged_store_rows(char* region, int lane, int mr
             if (i >= MR) continue;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int row = ii * 16 + lr;
-                const int pc = (j * 2 + (lq >> 1)) ^ ((row >> 1) & 7);
                 const f32x4 v = value_of(i, j);
-                *reinterpret_cast<bf16x4*>(region + row * 128 + pc * 16 + (lq & 1) * 8) = pack4<F16>(v[0], v[1], v[2], v[3]);
+                Image128::put4(region, ii * 16 + lr, j, lq, pack4<F16>(v[0], v[1], v[2], v[3]));
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (HIPTS_STAGED_INTERIOR && mrow0 + pass * 64 + 64 <= M && pass * 64 + 64 <= MR * 16 && ncol0 + 64 <= N) {
+        if (mrow0 + pass * 64 + 64 <= M && pass * 64 + 64 <= MR * 16 && ncol0 + 64 <= N) {
             // all 64 rows x 64 columns of this pass exist (wave-uniform: every tile but the last row / column of tiles): eight LDS reads,
             // then eight stores from one base address -- with the per-lane test each store is an exec-masked block with its own LDS read,
             // lgkmcnt(0) and 64-bit address arithmetic
             bf16_t* base = out + (size_t)(mrow0 + pass * 64 + lrow) * ld + ncol0 + lc * 8;
             uint4 v[8];
 #pragma unroll
-            for (int r8 = 0; r8 < 8; ++r8) {
-                const int row = r8 * 8 + lrow;
-                v[r8] = *reinterpret_cast<const uint4*>(region + row * 128 + ((lc ^ ((row >> 1) & 7)) * 16));
-            }
+            for (int r8 = 0; r8 < 8; ++r8) v[r8] = *reinterpret_cast<const uint4*>(Image128::at(region, r8 * 8 + lrow, lc));
 #pragma unroll
             for (int r8 = 0; r8 < 8; ++r8) *reinterpret_cast<uint4*>(base + (size_t)r8 * 8 * ld) = v[r8];
         } else {
@@ -256,7 +291,7 @@ __device__ __forceinline__ void staged_store_rows(char* region, int lane, int mr
             for (int r8 = 0; r8 < 8; ++r8) {
                 const int row = r8 * 8 + lrow;
                 const int m = mrow0 + pass * 64 + row;
-                const uint4 v = *reinterpret_cast<const uint4*>(region + row * 128 + ((lc ^ ((row >> 1) & 7)) * 16));
+                const uint4 v = *reinterpret_cast<const uint4*>(Image128::at(region, row, lc));
                 if (pass * 64 + row >= MR * 16 || m >= M || !nvl) continue;
                 *reinterpret_cast<uint4*>(out + (size_t)m * ld + ncol0 + lc * 8) = v;
             }
@@ -265,8 +300,7 @@ __device__ __forceinline__ void staged_store_rows(char* region, int lane, int mr
     }
 }
 
-// The same for e4m3 outputs: a (16 MR) x 64 block is 64 B per row; image rows of 64 B with the 16 B chunk XOR-swizzled by
-// (row >> 2) & 3 (conflict-free 4 B writes: bank = 16 (row & 3) + 4 (chunk ^ (row >> 2) & 3) + lq), read back as
+// The same for e4m3 outputs: a (16 MR) x 64 block is 64 B per row (Image64, 4 B per lane and column block), read back as
 // 16 rows x 64 B per store instruction.
 template <int MR, typename ValueOf>
 __device__ __forceinline__ void staged_store_rows8(char* region, int lane, int mrow0, int M, uint8_t* out, int ld, int ncol0, int N,
@@ -282,10 +316,8 @@ __device__ __forceinline__ void staged_store_rows8(char* region, int lane, int m
             if (i >= MR) continue;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int row = ii * 16 + lr;
-                const int pc = j ^ ((row >> 2) & 3);
                 const f32x4 v = value_of(i, j);
-                *reinterpret_cast<uint32_t*>(region + row * 64 + pc * 16 + lq * 4) = pack4_e4m3(v[0], v[1], v[2], v[3]);
+                *reinterpret_cast<uint32_t*>(Image64::at(region, ii * 16 + lr, j) + lq * 4) = pack4_e4m3(v[0], v[1], v[2], v[3]);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -294,7 +326,7 @@ __device__ __forceinline__ void staged_store_rows8(char* region, int lane, int m
         for (int r16 = 0; r16 < 4; ++r16) {
             const int row = r16 * 16 + lrow;
             const int m = mrow0 + pass * 64 + row;
-            const uint4 v = *reinterpret_cast<const uint4*>(region + row * 64 + ((lc ^ ((row >> 2) & 3)) * 16));
+            const uint4 v = *reinterpret_cast<const uint4*>(Image64::at(region, row, lc));
             if (pass * 64 + row >= MR * 16 || m >= M || !nvl) continue;
             *reinterpret_cast<uint4*>(out + (size_t)m * ld + ncol0 + lc * 16) = v;
         }
@@ -302,7 +334,7 @@ __device__ __forceinline__ void staged_store_rows8(char* region, int lane, int m
     }
 }
 
-// One or two 16-row blocks (32 rows x 64 columns) of 16-bit values through a 4 KB wave-private image: the per-block form of
+// One or two 16-row blocks (32 rows x 64 columns) of 16-bit values through a 4 KB wave-private Image128: the per-block form of
 // staged_store_rows for epilogues that finish their rows two blocks at a time (EPI_RESID_XG).
 template <bool F16, typename ValueOf>
 __device__ __forceinline__ void staged_store_2blocks(char* image, int lane, int mrow_first, int nblk, int M, bf16_t* out, int ld, int ncol0, int N,
@@ -314,10 +346,8 @@ __device__ __forceinline__ void staged_store_2blocks(char* image, int lane, int 
         if (u >= nblk) continue;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int row = u * 16 + lr;
-            const int pc = (j * 2 + (lq >> 1)) ^ ((row >> 1) & 7);
             const f32x4 v = value_of(u, j);
-            *reinterpret_cast<bf16x4*>(image + row * 128 + pc * 16 + (lq & 1) * 8) = pack4<F16>(v[0], v[1], v[2], v[3]);
+            Image128::put4(image, u * 16 + lr, j, lq, pack4<F16>(v[0], v[1], v[2], v[3]));
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -326,14 +356,15 @@ __device__ __forceinline__ void staged_store_2blocks(char* image, int lane, int 
     for (int r8 = 0; r8 < 4; ++r8) {
         const int row = r8 * 8 + lrow;
         const int m = mrow_first + row;
-        const uint4 v = *reinterpret_cast<const uint4*>(image + row * 128 + ((lc ^ ((row >> 1) & 7)) * 16));
+        const uint4 v = *reinterpret_cast<const uint4*>(Image128::at(image, row, lc));
         if (row < nblk * 16 && m < M && nvl) *reinterpret_cast<uint4*>(out + (size_t)m * ld + ncol0 + lc * 8) = v;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
 
-// staged_store_2blocks for a tile that lies inside the matrix: two full row blocks, nothing predicated (one basic block)
+// staged_store_2blocks for a tile that lies inside the matrix: two full row blocks, nothing predicated (one basic block).  (Kept as
+// a function of its own: as staged_store_2blocks<F16, INTERIOR> the general residual kernels came out with other spills, LABNOTES.)
 template <bool F16, typename ValueOf>
 __device__ __forceinline__ void staged_store_2blocks_interior(char* image, int lane, bf16_t* out_rows, int ld, ValueOf value_of) {
     const int lr = lane & 15, lq = lane >> 4, lc = lane & 7, lrow = lane >> 3;
@@ -341,26 +372,25 @@ __device__ __forceinline__ void staged_store_2blocks_interior(char* image, int l
     for (int u = 0; u < 2; ++u)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int row = u * 16 + lr;
-            const int pc = (j * 2 + (lq >> 1)) ^ ((row >> 1) & 7);
             const f32x4 v = value_of(u, j);
-            *reinterpret_cast<bf16x4*>(image + row * 128 + pc * 16 + (lq & 1) * 8) = pack4<F16>(v[0], v[1], v[2], v[3]);
+            Image128::put4(image, u * 16 + lr, j, lq, pack4<F16>(v[0], v[1], v[2], v[3]));
         }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int r8 = 0; r8 < 4; ++r8) {
         const int row = r8 * 8 + lrow;
-        const uint4 v = *reinterpret_cast<const uint4*>(image + row * 128 + ((lc ^ ((row >> 1) & 7)) * 16));
+        // (the chunk address spelled out, not Image128::at: through at() the interior kernels grouped their integer adds otherwise
+        // and gemm_pp_kernel<RESID_XG, 8, *, 0, 0, 1> lost one s_waitcnt)
+        const uint4 v = *reinterpret_cast<const uint4*>(image + row * 128 + ((lc ^ Image128::swizzle(row)) * 16));
         *reinterpret_cast<uint4*>(out_rows + (size_t)row * ld + lc * 8) = v;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
 
-// A (16 MR) x 32 block of 16-bit values (the SwiGLU product: half as many output columns as accumulator columns):
-// 64 B per row, the image geometry of staged_store_rows8 with 8 B per (row block, column block) -- lane (lr, lq) writes
-// columns 16 jj + 4 lq ..+3 of row 16 i + lr; bank = 16 (row & 3) + 4 (chunk ^ (row >> 2) & 3) + 2 (lq & 1) per half wave.
+// A (16 MR) x 32 block of 16-bit values (the SwiGLU product: half as many output columns as accumulator columns): 64 B per row,
+// Image64 with 8 B per lane and column block -- lane (lr, lq) writes columns 16 jj + 4 lq ..+3 of row 16 i + lr.
 template <int MR, bool F16, typename ValueOf>
 __device__ __forceinline__ void staged_store_half_rows(char* region, int lane, int mrow0, int M, bf16_t* out, int ld, int ocol0, int Nout,
                                                        ValueOf value_of) {
@@ -375,23 +405,18 @@ __device__ __forceinline__ void staged_store_half_rows(char* region, int lane, i
             if (i >= MR) continue;
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
-                const int row = ii * 16 + lr;
-                const int pc = (jj * 2 + (lq >> 1)) ^ ((row >> 2) & 3);
                 const f32x4 v = value_of(i, jj);
-                *reinterpret_cast<bf16x4*>(region + row * 64 + pc * 16 + (lq & 1) * 8) = pack4<F16>(v[0], v[1], v[2], v[3]);
+                Image64::put4(region, ii * 16 + lr, jj, lq, pack4<F16>(v[0], v[1], v[2], v[3]));
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (HIPTS_STAGED_INTERIOR && mrow0 + pass * 64 + 64 <= M && pass * 64 + 64 <= MR * 16 && ocol0 + 32 <= Nout) {
-            // the pass lies inside the matrix (wave-uniform): reads, then stores from one base address (see staged_store_rows)
+        if (mrow0 + pass * 64 + 64 <= M && pass * 64 + 64 <= MR * 16 && ocol0 + 32 <= Nout) {
+            // the pass lies inside the matrix (wave-uniform): reads, then stores from one base address (see read_back_pass)
             bf16_t* base = out + (size_t)(mrow0 + pass * 64 + lrow) * ld + ocol0 + lc * 8;
             uint4 v[4];
 #pragma unroll
-            for (int r16 = 0; r16 < 4; ++r16) {
-                const int row = r16 * 16 + lrow;
-                v[r16] = *reinterpret_cast<const uint4*>(region + row * 64 + ((lc ^ ((row >> 2) & 3)) * 16));
-            }
+            for (int r16 = 0; r16 < 4; ++r16) v[r16] = *reinterpret_cast<const uint4*>(Image64::at(region, r16 * 16 + lrow, lc));
 #pragma unroll
             for (int r16 = 0; r16 < 4; ++r16) *reinterpret_cast<uint4*>(base + (size_t)r16 * 16 * ld) = v[r16];
         } else {
@@ -399,13 +424,36 @@ __device__ __forceinline__ void staged_store_half_rows(char* region, int lane, i
             for (int r16 = 0; r16 < 4; ++r16) {
                 const int row = r16 * 16 + lrow;
                 const int m = mrow0 + pass * 64 + row;
-                const uint4 v = *reinterpret_cast<const uint4*>(region + row * 64 + ((lc ^ ((row >> 2) & 3)) * 16));
+                const uint4 v = *reinterpret_cast<const uint4*>(Image64::at(region, row, lc));
                 if (pass * 64 + row >= MR * 16 || m >= M || !nvl) continue;
                 *reinterpret_cast<uint4*>(out + (size_t)m * ld + ocol0 + lc * 8) = v;
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
+}
+
+// A wave's share of a row's (sum, sum of squares): over the lane's NB column blocks, then its four elements, then the four lane
+// quarters (xor 16, xor 32) -- every lane of a row ends with the pair.  The add order is part of the output bits.
+template <int NB>
+__device__ __forceinline__ float2 row_sums(const f32x4 (&blk)[4]) {
+    f32x4 t = blk[0], q = blk[0] * blk[0];
+#pragma unroll
+    for (int j = 1; j < NB; ++j) {
+        t = t + blk[j];
+        q = q + blk[j] * blk[j];
+    }
+    float s1 = (t[0] + t[1]) + (t[2] + t[3]), s2 = (q[0] + q[1]) + (q[2] + q[3]);
+    s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
+    s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
+    return make_float2(s1, s2);
+}
+// ... left in red[row][wave_n] ([256 rows][4 waves] of float2 in LDS), where the four waves of a row meet once the tile's epilogue
+// is through and thread t adds row t's four parts into stat_part
+template <int NB>
+__device__ __forceinline__ void row_sums_to_red(const f32x4 (&blk)[4], int lq, float2* red, int row, int wave_n) {
+    const float2 s = row_sums<NB>(blk);
+    if (lq == 0) red[row * 4 + wave_n] = s;
 }
 
 // Epilogue shared by both main-loop variants.  acc[i][j]: 16 x 16 tile (i: 16-row block of the
@@ -427,12 +475,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
     const int lr = lane & 15, lq = lane >> 4;
     const int ld = a.ld_out ? a.ld_out : a.N;
     f32x4 bias_v[4];
-    if (bias_pre) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bias_v[j] = bias_pre[j];
-    } else {
-        load_bias<EPI>(a, n0, wave_n, lane, bias_v);
-    }
+    epi_bias<EPI>(a, n0, wave_n, lane, bias_pre, bias_v);
     if constexpr (EPI == EPI_VT) {
         // natural order: lane = column n, registers = 4 consecutive rows (tokens)
         float bv[4];
@@ -605,10 +648,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
                 const size_t rb_step = a.x_blocked ? (size_t)(ld >> 4) * 256 : (size_t)16 * ld;
                 const int cb_step = a.x_blocked ? 256 : 16;
                 float* base = a.out_f32 + x_off(a, m0 + wave_m * 128, ncol0, ld);            // uniform
-                // HIPTS_INT_DEPTH (2 / 3): register sets of loads in flight.  With the stream in blocks the address path is no longer what a
-                // step waits for, so a third set (two steps ahead, 32 more registers: the instantiation is built for 256) was tried
-                constexpr int DEPTH = HIPTS_INT_DEPTH;
-                f32x4 xv[DEPTH][RB][4];
+                // two register sets of loads in flight (a third, two steps ahead: LABNOTES, "GEMM epilogues: retired switches")
+                f32x4 xv[2][RB][4];
                 auto request = [&](int buf, int i2) {
 #pragma unroll
                     for (int u = 0; u < RB; ++u)
@@ -617,16 +658,11 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
                             xv[buf][u][j] = *reinterpret_cast<const f32x4*>(base + (size_t)(i2 + u) * rb_step + lane_off + j * cb_step);
                 };
                 request(0, 0);
-                if constexpr (DEPTH == 3) request(1, RB);
 #pragma unroll
                 for (int i2 = 0; i2 < 8; i2 += RB) {
                     epi_turn(a, wave_m, i2 / RB);
-                    const int cur = (i2 / RB) % DEPTH;
-                    if constexpr (DEPTH == 3) {
-                        if (i2 + 2 * RB < 8) request((cur + 2) % 3, i2 + 2 * RB);
-                    } else {
-                        if (i2 + RB < 8) request(cur ^ 1, i2 + RB);
-                    }
+                    const int cur = (i2 / RB) % 2;
+                    if (i2 + RB < 8) request(cur ^ 1, i2 + RB);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int u = 0; u < RB; ++u) {
@@ -643,19 +679,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
                         }
                     }
 #pragma unroll
-                    for (int u = 0; u < RB; ++u) {
-                        const int i = i2 + u;
-                        f32x4 t = acc[i][0], q = acc[i][0] * acc[i][0];
-#pragma unroll
-                        for (int j = 1; j < 4; ++j) {
-                            t = t + acc[i][j];
-                            q = q + acc[i][j] * acc[i][j];
-                        }
-                        float s1 = (t[0] + t[1]) + (t[2] + t[3]), s2 = (q[0] + q[1]) + (q[2] + q[3]);
-                        s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
-                        s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
-                        if (lq == 0) red[(wave_m * 128 + i * 16 + lr) * 4 + wave_n] = make_float2(s1, s2);
-                    }
+                    for (int u = 0; u < RB; ++u) row_sums_to_red<4>(acc[i2 + u], lq, red, wave_m * 128 + (i2 + u) * 16 + lr, wave_n);
                     staged_store_2blocks_interior<F16>(image, lane, a.out_bf16 + (size_t)(m0 + wave_m * 128 + i2 * 16) * ld + ncol0, ld,
                                                        [&](int u, int j) { return acc[i2 + u][j] * cvec[j * 4 + lq]; });
                     __builtin_amdgcn_sched_barrier(0);      // the pair after next is not requested early (registers)
@@ -699,27 +723,17 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
                 if (!copy) continue;
                 if (a.stat_part) {
 #pragma unroll
-                    for (int u = 0; u < RB; ++u) {
-                        const int i = i2 + u;
-                        if (i >= MR) continue;
-                        f32x4 t = acc[i][0], q = acc[i][0] * acc[i][0];
-#pragma unroll
-                        for (int j = 1; j < 4; ++j) {
-                            t = t + acc[i][j];
-                            q = q + acc[i][j] * acc[i][j];
-                        }
-                        float s1 = (t[0] + t[1]) + (t[2] + t[3]), s2 = (q[0] + q[1]) + (q[2] + q[3]);
-                        s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
-                        s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
-                        if (lq == 0) red[(wave_m * (MR * 16) + i * 16 + lr) * 4 + wave_n] = make_float2(s1, s2);      // columns past N hold zeros
-                    }
+                    for (int u = 0; u < RB; ++u)
+                        if (i2 + u < MR) row_sums_to_red<4>(acc[i2 + u], lq, red, wave_m * (MR * 16) + (i2 + u) * 16 + lr, wave_n);      // columns past N hold zeros
                 }
                 staged_store_2blocks<F16>(image, lane, m0 + wave_m * (MR * 16) + i2 * 16, (MR - i2) < RB ? (MR - i2) : RB, a.M, a.out_bf16, ld, ncol0, a.N,
                                           [&](int u, int j) { return acc[i2 + u][j] * gv[j]; });
             }
             }       // !INT
             if (copy && a.stat_part && finish_stats) {
-                // the four waves that hold a row meet (uniform); red is written again only after the next tile's main loop
+                // the four waves that hold a row meet (uniform); red is written again only after the next tile's main loop.  (This block
+                // stands three times -- here, in gemm.hip's SWIGLU tail and in gemm4.hip: as one function it moved spills and waits in
+                // the kernels of this file's two sites, LABNOTES)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -876,12 +890,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
     }
 }
 
-// Half-precision epilogues through LDS.  After the main loop one stage of LDS is free, so every wave
-// packs its 16 MR x 64 output block, 64 rows at a time, into a private 8 KB LDS image and reads it back
-// row-contiguous: each global store instruction then writes whole 128 B lines (8 rows x 128 B) instead of
-// 16 scattered 32 B pieces.  Both LDS passes are bank-conflict free: the 16 B chunk of an image row is
-// XOR-swizzled with (row >> 1) & 7 and rows alternate between the two 128 B halves of the 64 banks.
-// Wave-private image: no workgroup barrier, LDS operations of one wave execute in order.
+// Half-precision epilogues through LDS: every wave packs its 16 MR x 64 output block, 64 rows at a time, into its private 8 KB
+// Image128 (`region`, in the LDS stage the main loop has left free) and reads it back row-contiguous (RowImage, read_back_pass).
+// The arms: V^T (the image's rows are the columns d), SWIGLU (the product as half rows), and the row images of GELU / STAR
+// (row-major out) and QK / QK_ROPE (the q | k | v layouts).
 template <int EPI, int MR, bool F16>
 __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& a, f32x4 (&acc)[MR][4], int m0, int n0, int wave_m, int wave_n,
                                                      int lane, char* region, const f32x4* bias_pre = nullptr, const float2* st_lds = nullptr,
@@ -890,12 +902,7 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& a, f32x4 (&
     // there and the caller adds them into ONE pair per (256-column tile, row)
     // st_lds: (rstd, rstd * mean) of the tile's rows m0 .. m0 + 255, finished from the producer's partials by the caller
     f32x4 bias_v[4];
-    if (bias_pre) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bias_v[j] = bias_pre[j];
-    } else {
-        load_bias<EPI>(a, n0, wave_n, lane, bias_v);
-    }
+    epi_bias<EPI>(a, n0, wave_n, lane, bias_pre, bias_v);
     static_assert(EPI == EPI_VT || EPI == EPI_GELU || EPI == EPI_STAR || EPI == EPI_QK || EPI == EPI_QK_ROPE || EPI == EPI_SWIGLU,
                   "staged epilogue: half-precision outputs only");
     constexpr bool IS_QK = EPI == EPI_QK || EPI == EPI_QK_ROPE;
@@ -937,9 +944,7 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& a, f32x4 (&
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const f32x4 c = acc[i][j] * sx + (bv[j] - sy * cu[j][0]);
-                    const int d = j * 16 + lr;
-                    const int pc = (ii * 2 + (lq >> 1)) ^ ((d >> 1) & 7);
-                    *reinterpret_cast<bf16x4*>(region + d * 128 + pc * 16 + (lq & 1) * 8) = pack4<F16>(c[0], c[1], c[2], c[3]);
+                    Image128::put4(region, j * 16 + lr, ii, lq, pack4<F16>(c[0], c[1], c[2], c[3]));      // image row = column d, the lane's four tokens its 8 B
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -951,7 +956,7 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& a, f32x4 (&
             for (int r8 = 0; r8 < 8; ++r8) {
                 const int d = r8 * 8 + lrow;
                 const int n = ncol0 + d;
-                const uint4 v = *reinterpret_cast<const uint4*>(region + d * 128 + ((lc ^ ((d >> 1) & 7)) * 16));
+                const uint4 v = *reinterpret_cast<const uint4*>(Image128::at(region, d, lc));
                 if (mv && n < a.N)
                     *reinterpret_cast<uint4*>(a.out_bf16 +
                                               ((((size_t)(b * a.heads + (n >> a.hd_log2))) << a.hd_log2) + (n & ((1 << a.hd_log2) - 1))) * a.tokens_pad + t) = v;
@@ -983,15 +988,13 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& a, f32x4 (&
                 if (a.stat_part) {
                     // this wave's share of the row statistics of the product (a LayerNorm over the hidden units follows):
                     // sum over the lane's 8 values, then over the four lane quarters
-                    const f32x4 t = acc[i][0] + acc[i][1], q = acc[i][0] * acc[i][0] + acc[i][1] * acc[i][1];
-                    float s1 = (t[0] + t[1]) + (t[2] + t[3]), s2 = (q[0] + q[1]) + (q[2] + q[3]);
-                    s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
-                    s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
+                    // (the sums before the branch: inside its two arms the shuffles were emitted twice)
+                    const float2 s = row_sums<2>(acc[i]);
                     const int m = mrow0 + i * 16 + lr;
                     if (red) {
-                        if (lq == 0) red[(mrow0 - m0 + i * 16 + lr) * 4 + wave_n] = ncol0 < a.N ? make_float2(s1, s2) : make_float2(0.f, 0.f);
+                        if (lq == 0) red[(mrow0 - m0 + i * 16 + lr) * 4 + wave_n] = ncol0 < a.N ? s : make_float2(0.f, 0.f);
                     } else if (lq == 0 && m < a.M && ncol0 < a.N)
-                        *reinterpret_cast<float2*>(a.stat_part + 2 * ((size_t)(ncol0 >> 6) * a.stat_stride + m)) = make_float2(s1, s2);
+                        *reinterpret_cast<float2*>(a.stat_part + 2 * ((size_t)(ncol0 >> 6) * a.stat_stride + m)) = s;
                 }
                 // the gamma of the LayerNorm that follows, applied to the stored operand (the statistics above are of the raw
                 // product): the next GEMM then keeps its own weights unchanged
@@ -1047,8 +1050,6 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& a, f32x4 (&
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int row = ii * 16 + lr;
-                    const int pc = (j * 2 + (lq >> 1)) ^ ((row >> 1) & 7);
                     f32x4 v = acc[i][j] * st.x + (bv[j] - cu[j] * st.y);
                     if constexpr (EPI == EPI_QK_ROPE) {
                         if (rok)
@@ -1064,22 +1065,19 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& a, f32x4 (&
                         o = pack4<F16>(gv[0], gv[1], gv[2], gv[3]);
                     } else
                         o = pack4<F16>(v[0] * sc, v[1] * sc, v[2] * sc, v[3] * sc);
-                    *reinterpret_cast<bf16x4*>(region + row * 128 + pc * 16 + (lq & 1) * 8) = o;
+                    Image128::put4(region, ii * 16 + lr, j, lq, o);
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
+            // The read-back (the pair of staged_store_rows: interior, then predicated).  It stays written out here and there: as one
+            // function taking the destination as a callable it moved registers, spills and waits in every kernel that uses it (LABNOTES).
             if constexpr (EPI == EPI_GELU || EPI == EPI_STAR) {
-                // all 64 rows x 64 columns of this pass exist (wave-uniform: every tile but the last row / column of tiles): eight LDS reads,
-                // then eight stores from one base address (see staged_store_rows)
-                if (HIPTS_STAGED_INTERIOR && mrow0 + pass * 64 + 64 <= a.M && pass * 64 + 64 <= MR * 16 && ncol0 + 64 <= a.N) {
+                if (mrow0 + pass * 64 + 64 <= a.M && pass * 64 + 64 <= MR * 16 && ncol0 + 64 <= a.N) {
                     bf16_t* base = a.out_bf16 + (size_t)(mrow0 + pass * 64 + lrow) * ld + ncol0 + lc * 8;
                     uint4 v[8];
 #pragma unroll
-                    for (int r8 = 0; r8 < 8; ++r8) {
-                        const int row = r8 * 8 + lrow;
-                        v[r8] = *reinterpret_cast<const uint4*>(region + row * 128 + ((lc ^ ((row >> 1) & 7)) * 16));
-                    }
+                    for (int r8 = 0; r8 < 8; ++r8) v[r8] = *reinterpret_cast<const uint4*>(Image128::at(region, r8 * 8 + lrow, lc));
 #pragma unroll
                     for (int r8 = 0; r8 < 8; ++r8) *reinterpret_cast<uint4*>(base + (size_t)r8 * 8 * ld) = v[r8];
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1088,13 +1086,12 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& a, f32x4 (&
             }
             if constexpr (IS_QK) {
                 // the same for the q | k | v layouts: the eight (image, token) addresses first, then reads, then stores
-                if (HIPTS_STAGED_INTERIOR && mrow0 + pass * 64 + 64 <= a.M && pass * 64 + 64 <= MR * 16 && ncol0 + 64 <= a.N) {
+                if (mrow0 + pass * 64 + 64 <= a.M && pass * 64 + 64 <= MR * 16 && ncol0 + 64 <= a.N) {
                     uint4 v[8];
                     size_t off[8];
 #pragma unroll
                     for (int r8 = 0; r8 < 8; ++r8) {
-                        const int row = r8 * 8 + lrow;
-                        v[r8] = *reinterpret_cast<const uint4*>(region + row * 128 + ((lc ^ ((row >> 1) & 7)) * 16));
+                        v[r8] = *reinterpret_cast<const uint4*>(Image128::at(region, r8 * 8 + lrow, lc));
                         off[r8] = ((((size_t)(qb * a.heads + head) * a.tokens_pad + qt)) << a.hd_log2) + hd_off;
                         qt += 8;
                         while (qt >= a.tokens) {
@@ -1112,7 +1109,7 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& a, f32x4 (&
             for (int r8 = 0; r8 < 8; ++r8) {
                 const int row = r8 * 8 + lrow;
                 const int m = mrow0 + pass * 64 + row;
-                const uint4 v = *reinterpret_cast<const uint4*>(region + row * 128 + ((lc ^ ((row >> 1) & 7)) * 16));
+                const uint4 v = *reinterpret_cast<const uint4*>(Image128::at(region, row, lc));
                 const int qb_now = qb, qt_now = qt;
                 if constexpr (IS_QK) {
                     qt += 8;

@@ -7,10 +7,24 @@ references of tests/gemm_epi_ref.py.  Per case (an arm of gemm_epi_ref.CASES x K
     fp32 output; (c) resid_rowmajor_out holds the bits the blocked stream would; (d) probs is the sigmoid of the kernel's logits; (e) two
     launches give identical bytes;
   * cross-arm invariance: the arm's outputs equal, bit for bit, those of the epilogue's general 256-row persistent arm on the rows and
-    columns they share -- batch invariance at kernel level.
-Inputs come from one master per (epilogue, operand type): |a| ~ 1, |w| ~ 0.05, folded LayerNorm rows with |mean| <= 0.5 sigma."""
+    columns they share -- batch invariance at kernel level;
+  * the launch's output BITS, pinned: one sha256 over every buffer the launch returns (x, rowmajor, probs, out16[0..2], stat_part, each whole,
+    guard and pad bytes included) must equal the digest in tests/golden/gemm_epi_bits.json under the case's id.  A refactor of the epilogues
+    ("same bits out") passes it unchanged: the plan is fixed for the device's CU count, split-K slabs are summed in slice order and the
+    arithmetic by source order (-ffp-contract=off), so the digests do not move with a rebuild.
+Inputs come from one master per (epilogue, operand type): |a| ~ 1, |w| ~ 0.05, folded LayerNorm rows with |mean| <= 0.5 sigma.
+
+A pull request that changes an epilogue's arithmetic ON PURPOSE (another summation order, another conversion, another plan for a case's
+shape) regenerates the digests on an MI355X, from the commit that holds the new arithmetic, and says so:
+
+    HIPTS_GEMM_EPI_BITS_REGEN=tests/golden/gemm_epi_bits.json python -m pytest tests/test_gpu_gemm_epi.py -m gpu
+
+(the variable names the file to write; every case then records its digest instead of comparing it).
+"""
 import ctypes
 import functools
+import hashlib
+import json
 import os
 import sys
 
@@ -23,6 +37,8 @@ import gemm_epi_ref as R  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 FILL = 0xFF
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_epi_bits.json")
+REGEN = os.environ.get("HIPTS_GEMM_EPI_BITS_REGEN")
 CHUNK = 2048            # rows of a float64 reference block
 
 
@@ -240,6 +256,31 @@ def bits_of(a):
     return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
+@functools.lru_cache(maxsize=None)
+def _golden():
+    with open(GOLDEN) as f:
+        return json.load(f)
+
+
+def check_bits(key, raw):
+    """the launch's buffers in OutT's order (x, rowmajor, probs, out16[0..2], stat_part), each whole, against the pinned digest"""
+    h = hashlib.sha256()
+    for name in ("x", "rowmajor", "probs", "o0", "o1", "o2", "stat"):
+        if raw.get(name) is not None:
+            h.update(raw[name].tobytes())
+    if REGEN:
+        rec = {}
+        if os.path.exists(REGEN):
+            with open(REGEN) as f:
+                rec = json.load(f)
+        rec[key] = h.hexdigest()
+        with open(REGEN, "w") as f:
+            json.dump(rec, f, indent=0, sort_keys=True)
+            f.write("\n")
+        return
+    assert h.hexdigest() == _golden()[key], "%s: the launch's output bits differ from tests/golden/gemm_epi_bits.json" % key
+
+
 def logical(raw, spec, name):
     return raw[name][spec[name][2]]
 
@@ -297,7 +338,7 @@ def _ids():
 
 def _default_environment():
     """the plan is asked with the 4-wave mask 0 and the default switches: the launch must run under the same"""
-    switches = [k for k in os.environ if k.startswith(("HIPTS_GEMM", "HIPTS_EPI_", "HIPTS_RESID_GENERAL"))]
+    switches = [k for k in os.environ if k.startswith(("HIPTS_GEMM", "HIPTS_EPI_", "HIPTS_RESID_GENERAL")) and k != "HIPTS_GEMM_EPI_BITS_REGEN"]
     assert switches == [], "the cases are for the default environment, the 4-wave loop (HIPTS_GEMM_Q4) off: %s" % switches
 
 
@@ -382,6 +423,8 @@ def test_epilogue_arm(case, K, blocks):
         assert np.array_equal(bits_of(np.ascontiguousarray(mine[:rows, :cols])), bits_of(np.ascontiguousarray(ref[name][:rows, :cols]))), \
             "%s differs from the general 256-row persistent arm on shared rows and columns" % name
 
+    check_bits("%s-K%d%s" % (R.key_name(R.case_key(case)), K, "-b%d" % blocks if blocks else ""), raw)
+
 
 def test_vt_unstaged_small_images():
     """tokens % 8 != 0 (the CAFormer test geometry's last stage: 4 tokens per image) takes EPI_VT's store path without the LDS image"""
@@ -396,6 +439,7 @@ def test_vt_unstaged_small_images():
     a64, w64 = m["a64"][:256, :128], m["w64"][:128, :128]
     q = R.reference(R.VT, a64 @ w64.T, np.abs(a64) @ np.abs(w64).T, v)["o0"]
     assert (np.abs(_from16(logical(raw, spec, "o0"), 1) - q.val) <= q.bound(128, "f16")).all()
+    check_bits("test_vt_unstaged_small_images-K128", raw)
 
 
 def _refused(case, K, blocks, **over):
