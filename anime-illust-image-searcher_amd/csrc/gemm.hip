@@ -243,11 +243,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
     }
 
     for (;;) {
+        // not cleared: the first product into a block in a work item takes C = 0 (ktile's FIRST); a pass of 32 MR v_mov per tile else
         f32x4 acc[MR][4];
-#pragma unroll
-        for (int i = 0; i < MR; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
         // This wave's eight staging slots of a K-tile (two per phase), as (global source pointer for
         // K-tile 1, LDS offset inside a stage).  Phase lists of 16 sub-tiles (8 rows x 128 B each), wave w
@@ -320,7 +317,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
         bf16x8 wf[2][4];
         i32x8 wf8[4], af8[4];
         unsigned xpf = 0;       // destination of the epilogue prefetch: stays allocated until the epilogue's own loads have been waited for
-        for (int t = 0; t < nt; ++t) {
+        // One K-tile.  FIRST (compile time; the item's first K-tile, peeled below -- a split-K slice's is K-tile kt0) : the phases that touch
+        // an accumulator block first -- 0 and 2 (kk == 0); with e4m3 operands every phase has a j half of its own -- multiply onto a literal
+        // zero.  0 + sum from an inline 0 and from a cleared register are the same bits.
+        auto ktile = [&](int t, auto first_tag) __attribute__((always_inline)) {
+            constexpr bool FIRST = decltype(first_tag)::value;
             const char* cur = smem + ((par + t) & 1) * STAGE_BYTES;
             char* nxt = smem + ((par + t + 1) & 1) * STAGE_BYTES;
             const bool more = t + 1 < nt;
@@ -436,10 +437,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
 #pragma unroll
                         for (int jj = 0; jj < 2; ++jj) {
                             const int j = 2 * kk + jj;
+                            const f32x4 c = FIRST ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[mh * 4 + i][j];
                             if constexpr (EPI == EPI_VT)
-                                acc[mh * 4 + i][j] = mfma_16x16x128_e4m3(af8[i], wf8[j], acc[mh * 4 + i][j], scale_1, scale_w);
+                                acc[mh * 4 + i][j] = mfma_16x16x128_e4m3(af8[i], wf8[j], c, scale_1, scale_w);
                             else
-                                acc[mh * 4 + i][j] = mfma_16x16x128_e4m3(wf8[j], af8[i], acc[mh * 4 + i][j], scale_w, scale_1);
+                                acc[mh * 4 + i][j] = mfma_16x16x128_e4m3(wf8[j], af8[i], c, scale_w, scale_1);
                         }
                 } else {
 #pragma unroll
@@ -454,10 +456,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
                     const int i = ij >> 2, j = ij & 3;
 #endif
                     if (mh * 4 + i >= MR) continue;
+                    const f32x4 c = (FIRST && kk == 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[mh * 4 + i][j];
                     if constexpr (EPI == EPI_VT)
-                        acc[mh * 4 + i][j] = mfma_16x16x32<F16>(af[i], wf[kk][j], acc[mh * 4 + i][j]);
+                        acc[mh * 4 + i][j] = mfma_16x16x32<F16>(af[i], wf[kk][j], c);
                     else
-                        acc[mh * 4 + i][j] = mfma_16x16x32<F16>(wf[kk][j], af[i], acc[mh * 4 + i][j]);
+                        acc[mh * 4 + i][j] = mfma_16x16x32<F16>(wf[kk][j], af[i], c);
                 }
                 }
                 __builtin_amdgcn_s_setprio(0);
@@ -465,7 +468,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
             }
-        }
+        };
+        ktile(0, std::true_type{});
+        for (int t = 1; t < nt; ++t) ktile(t, std::false_type{});
         if (wave_m == 0) __builtin_amdgcn_s_barrier();      // balance the stagger
         PPSTAMP(3);
         if (a.stamps && blockIdx.x == 8 && stamp_tile < 8 && lane == 0) a.stamps[wave * 64 + stamp_tile * 8 + 7] = wall_clock64();
@@ -473,12 +478,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
         // Every wave is past its last fragment read and no LDS-DMA is in flight.  Stage (par + nt) & 1 (last
         // read in K-tile nt - 2) receives K-tile 0 of this workgroup's next tile now, so that its HBM
         // latency is covered by the epilogue; the stage of the last K-tile is the epilogue's scratch.
+        // The epilogue's per-lane values (LDS image addresses, row offsets of the stream and of the 16-bit copy) are cheap functions of
+        // the lane number.  Computed from `lane` they are loop invariants: hipcc hoists them in front of the tile loop, they stay live through
+        // the main loop on top of accumulators and fragments, and the allocator spills them -- a scratch reload is a VMEM operation behind
+        // s_waitcnt vmcnt(0), a drain of every store in flight, in the epilogue's first turn.  From a copy the compiler cannot see through
+        // they are recomputed per tile (a few dozen VALU instructions) and die with the epilogue.
+        int elane = lane;
+        asm volatile("" : "+v"(elane));
         f32x4 bias_pre[4];
         if constexpr (INT) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) bias_pre[j] = f32x4{0.f, 0.f, 0.f, 0.f};      // INT reads bias (and gamma, col_u) from colvec
         } else {
-            load_bias<EPI>(a, n0, wave_n, lane, bias_pre);      // in flight while the next prologue is issued
+            load_bias<EPI>(a, n0, wave_n, elane, bias_pre);      // in flight while the next prologue is issued
         }
         constexpr bool FOLDABLE = EPI == EPI_VT || EPI == EPI_GELU || EPI == EPI_STAR || EPI == EPI_QK || EPI == EPI_QK_ROPE || EPI == EPI_SWIGLU ||
                                   EPI == EPI_RESID_ROWSTAT || EPI == EPI_RESID_XGI;
@@ -569,7 +581,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
                                                                      : ((a.ld_out ? a.ld_out : a.N) % 8 == 0);
             if (ok) {
                 float2* red = (EPI == EPI_SWIGLU && a.stat_part) ? sw_red : nullptr;
-                gemm_epilogue_staged<EPI, MR, F16>(a, acc, m0, n0, wave_m, wave_n, lane,
+                gemm_epilogue_staged<EPI, MR, F16>(a, acc, m0, n0, wave_m, wave_n, elane,
                                                    smem + ((par + nt + 1) & 1) * STAGE_BYTES + wave * 8192, bias_pre, fold_st ? st_table : nullptr, red);
                 staged = true;
                 if constexpr (EPI == EPI_SWIGLU) {
@@ -589,7 +601,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
             }
         }
         if (!staged)
-            gemm_epilogue<EPI, MR, F16, INT>(a, acc, m0, n0, wave_m, wave_n, lane, bias_pre, smem + ((par + nt + 1) & 1) * STAGE_BYTES,
+            gemm_epilogue<EPI, MR, F16, INT>(a, acc, m0, n0, wave_m, wave_n, elane, bias_pre, smem + ((par + nt + 1) & 1) * STAGE_BYTES,
                                              fold_st ? st_table : nullptr, INT ? colvec : nullptr);
         }       // run_epilogue
         if (a.epi_prio) __builtin_amdgcn_s_setprio(0);
@@ -910,11 +922,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(const GemmArgs a, int t
     };
     auto frag = [&](const char* base, int rb) { return *reinterpret_cast<const bf16x8*>(base + rb * 1024 + frag_off); };
 
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[8][4];        // not cleared: the first step's products take C = 0 (step's Z)
 
     const bool trace = a.stamps && a.trace && blockIdx.x < 4096;
     if (trace && tid == 0) {
@@ -942,14 +950,15 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(const GemmArgs a, int t
     unsigned long long wait_cyc = 0, bar_cyc = 0;
     const unsigned long long loop_t0 = a.stamps ? __builtin_readcyclecounter() : 0;
     const unsigned long long wall_t0 = a.stamps ? wall_clock64() : 0;
-    auto mm = [&](f32x4& c, const bf16x8& av, const bf16x8& wv) {
-        if constexpr (EPI == EPI_VT) c = mfma_16x16x32<F16>(av, wv, c);
-        else c = mfma_16x16x32<F16>(wv, av, c);
+    auto mm = [&](f32x4& c, const bf16x8& av, const bf16x8& wv, bool zero) {
+        const f32x4 c0 = zero ? f32x4{0.f, 0.f, 0.f, 0.f} : c;
+        if constexpr (EPI == EPI_VT) c = mfma_16x16x32<F16>(av, wv, c0);
+        else c = mfma_16x16x32<F16>(wv, av, c0);
     };
     // One step; H1/H2/H3 = stage st+1 / st+2 / st+3 exists (compile time: straight-line code, exact
-    // compiler-generated lgkmcnt), U = register set of this step.
-    auto step = [&](auto H1, auto H2, auto H3, auto U) {
-        constexpr bool has1 = decltype(H1)::value, has2 = decltype(H2)::value, has3 = decltype(H3)::value;
+    // compiler-generated lgkmcnt), U = register set of this step, Z = the tile's first step: its products take C = 0.
+    auto step = [&](auto H1, auto H2, auto H3, auto U, auto Z) __attribute__((always_inline)) {
+        constexpr bool has1 = decltype(H1)::value, has2 = decltype(H2)::value, has3 = decltype(H3)::value, first = decltype(Z)::value;
         constexpr int u = decltype(U)::value;
         const char* cur = smem + slot * DW_STAGE;
         const int slot1 = slot == 2 ? 0 : slot + 1;
@@ -959,7 +968,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(const GemmArgs a, int t
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                mm(acc[i][HIPTS_SNAKE_J(i, j)], alo[u][i], wfr[u][HIPTS_SNAKE_J(i, j)]);
+                mm(acc[i][HIPTS_SNAKE_J(i, j)], alo[u][i], wfr[u][HIPTS_SNAKE_J(i, j)], first);
                 if (i == 0) ahi[j] = frag(cur, wave_m * 8 + 4 + j);
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -980,7 +989,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(const GemmArgs a, int t
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                mm(acc[4 + i][HIPTS_SNAKE_J(i, j)], ahi[i], wfr[u][HIPTS_SNAKE_J(i, j)]);
+                mm(acc[4 + i][HIPTS_SNAKE_J(i, j)], ahi[i], wfr[u][HIPTS_SNAKE_J(i, j)], first);
                 const int idx = i * 4 + j;
                 if constexpr (has1) {
                     if (idx < 4) wfr[u ^ 1][idx] = frag(nx + DW_A_BYTES, wave_n * 4 + idx);
@@ -997,16 +1006,24 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(const GemmArgs a, int t
     using F = std::false_type;
     using U0 = std::integral_constant<int, 0>;
     using U1 = std::integral_constant<int, 1>;
-    for (int s = 0; s + 6 <= nt; s += 2) {      // nt is even (K % 64 == 0)
-        step(T{}, T{}, T{}, U0{});
-        step(T{}, T{}, T{}, U1{});
+    // nt is even (K % 64 == 0): (nt - 4) / 2 full pairs, the pair whose second step has no stage to request, the last pair; the first
+    // step of the tile is the first step of whichever of the three comes first
+    if (nt >= 6) {
+        step(T{}, T{}, T{}, U0{}, T{});
+        step(T{}, T{}, T{}, U1{}, F{});
+        for (int s = 2; s + 6 <= nt; s += 2) {
+            step(T{}, T{}, T{}, U0{}, F{});
+            step(T{}, T{}, T{}, U1{}, F{});
+        }
     }
     if (nt >= 4) {
-        step(T{}, T{}, T{}, U0{});
-        step(T{}, T{}, F{}, U1{});
+        if (nt == 4) step(T{}, T{}, T{}, U0{}, T{});
+        else step(T{}, T{}, T{}, U0{}, F{});
+        step(T{}, T{}, F{}, U1{}, F{});
     }
-    step(T{}, F{}, F{}, U0{});
-    step(F{}, F{}, F{}, U1{});
+    if (nt == 2) step(T{}, F{}, F{}, U0{}, T{});
+    else step(T{}, F{}, F{}, U0{}, F{});
+    step(F{}, F{}, F{}, U1{}, F{});
     if (trace && tid == 0) a.stamps[blockIdx.x * 8 + 3] = wall_clock64();
     if (a.stamps && !trace && blockIdx.x == 8 && lane == 0) {
         a.stamps[wave * 64 + 0] = __builtin_readcyclecounter() - loop_t0;
@@ -1063,6 +1080,43 @@ int gemm_plan_status(const GemmPlan& p, GemmEpilogue epi) {
     return HIPTS_OK;
 }
 
+// The gemm_pp_kernel instantiation of a launch; null where none is built.  launch_t launches what this returns and
+// hiptsdbg_gemm_kernel_resources describes it, so the registers and the scratch a test reads are those of the kernel that runs.
+using GemmKernel = void (*)(const GemmArgs, int, int);
+template <int EPI>
+GemmKernel pp_kernel(int mr, bool f16, bool op8, bool sk, bool interior) {
+    if (op8) {
+        if constexpr (EPI == EPI_STAR || EPI == EPI_RESID || EPI == EPI_RESCALE || EPI == EPI_RESID_LN || EPI == EPI_QK || EPI == EPI_VT || EPI == EPI_BIAS)
+            if (mr == 8 && f16 && !sk && !interior) return gemm_pp_kernel<EPI, 8, true, true>;
+        return nullptr;
+    }
+    if (sk) {
+        if constexpr (EPI == EPI_RESID || EPI == EPI_RESID_XG || EPI == EPI_RESID_XGI || EPI == EPI_RESID_ROWSTAT || EPI == EPI_HEAD)
+            if (mr == 8 && !interior) return f16 ? gemm_pp_kernel<EPI, 8, true, false, true> : gemm_pp_kernel<EPI, 8, false, false, true>;
+        return nullptr;
+    }
+    if (interior) {
+        if constexpr (EPI == EPI_RESID_XG)
+            if (mr == 8) return f16 ? gemm_pp_kernel<EPI, 8, true, false, false, true> : gemm_pp_kernel<EPI, 8, false, false, false, true>;
+        return nullptr;
+    }
+    if (f16) return mr == 6 ? gemm_pp_kernel<EPI, 6, true> : mr == 7 ? gemm_pp_kernel<EPI, 7, true> : mr == 8 ? gemm_pp_kernel<EPI, 8, true> : nullptr;
+    return mr == 7 ? gemm_pp_kernel<EPI, 7, false> : mr == 8 ? gemm_pp_kernel<EPI, 8, false> : nullptr;
+}
+
+template <int EPI>
+int kernel_resources_t(int mr, bool f16, bool op8, bool sk, bool interior, int* num_regs, int* scratch_bytes, int* static_lds) {
+    const GemmKernel k = pp_kernel<EPI>(mr, f16, op8, sk, interior);
+    HIPTS_REQUIRE(k != nullptr, "hiptsdbg_gemm_kernel_resources: no gemm_pp_kernel is built for epilogue %d, mr %d, f16 %d, op8 %d, sk %d, interior %d", EPI, mr,
+                  (int)f16, (int)op8, (int)sk, (int)interior);
+    hipFuncAttributes at;
+    HIPTS_HIP(hipFuncGetAttributes(&at, reinterpret_cast<const void*>(k)));
+    *num_regs = at.numRegs;
+    *scratch_bytes = (int)at.localSizeBytes;
+    *static_lds = (int)at.sharedSizeBytes;
+    return HIPTS_OK;
+}
+
 // validate (launch_gemm), plan (gemm_plan.h), launch: nothing is decided here.  The `if constexpr` guards name the epilogues an
 // instantiation is built for; the plan never asks for another.
 template <int EPI>
@@ -1083,7 +1137,7 @@ int launch_t(const GemmArgs& a, hipStream_t s) {
                           EPI == EPI_BIAS) {
                 static PerDevice once;
                 HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_pp_kernel<EPI, 8, true, true>));
-                go(gemm_pp_kernel<EPI, 8, true, true>);
+                go(pp_kernel<EPI>(8, true, true, false, false));
             }
             break;
         case HIPTSDBG_GEMM_DW: {
@@ -1127,8 +1181,7 @@ int launch_t(const GemmArgs& a, hipStream_t s) {
                 if (p.sk_slices >= 2) {     // the split-K tail
                     static PerDevice once;
                     HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_pp_kernel<EPI, 8, false, false, true>, gemm_pp_kernel<EPI, 8, true, false, true>));
-                    if (f16) go(gemm_pp_kernel<EPI, 8, true, false, true>);
-                    else go(gemm_pp_kernel<EPI, 8, false, false, true>);
+                    go(pp_kernel<EPI>(8, f16, false, true, false));
                     break;
                 }
             }
@@ -1136,19 +1189,16 @@ int launch_t(const GemmArgs& a, hipStream_t s) {
                 if (p.interior) {
                     static PerDevice once;
                     HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_pp_kernel<EPI, 8, false, false, false, true>, gemm_pp_kernel<EPI, 8, true, false, false, true>));
-                    if (f16) go(gemm_pp_kernel<EPI, 8, true, false, false, true>);
-                    else go(gemm_pp_kernel<EPI, 8, false, false, false, true>);
+                    go(pp_kernel<EPI>(8, f16, false, false, true));
                     break;
                 }
             }
             static PerDevice once;
             HIPTS_TRY(allow_dynamic_lds(once, dev, p.lds_bytes, gemm_pp_kernel<EPI, 8, false>, gemm_pp_kernel<EPI, 7, false>, gemm_pp_kernel<EPI, 8, true>,
                                         gemm_pp_kernel<EPI, 7, true>, gemm_pp_kernel<EPI, 6, true>));
-            if (f16 && p.mr == 6) go(gemm_pp_kernel<EPI, 6, true>);
-            else if (f16 && p.mr == 7) go(gemm_pp_kernel<EPI, 7, true>);
-            else if (f16) go(gemm_pp_kernel<EPI, 8, true>);
-            else if (p.mr == 7) go(gemm_pp_kernel<EPI, 7, false>);
-            else go(gemm_pp_kernel<EPI, 8, false>);
+            const GemmKernel k = pp_kernel<EPI>(p.mr, f16, false, false, false);
+            HIPTS_REQUIRE(k != nullptr, "gemm: no %d-row tiles are built for these operands", 32 * p.mr);
+            go(k);
         }
     }
     HIPTS_LAUNCH_CHECK();
@@ -1272,6 +1322,24 @@ extern "C" int hiptsdbg_gelu(const float* x_host, int n, int tanh_form, float* y
     HIPTS_LAUNCH_CHECK();
     HIPTS_HIP(hipMemcpy(y_host, y.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return HIPTS_OK;
+}
+
+// Development/test aid (not part of the public ABI): registers, scratch and static LDS of the gemm_pp_kernel instantiation the launcher
+// picks for (epilogue, tile height, operand type, e4m3, split-K, interior), as the loaded code object reports them.
+extern "C" int hiptsdbg_gemm_kernel_resources(int epi, int mr, int f16, int op8, int sk, int interior, int* num_regs, int* scratch_bytes, int* static_lds) {
+    using namespace hipts;
+    HIPTS_REQUIRE(num_regs && scratch_bytes && static_lds && epi >= EPI_PATCH && epi <= EPI_RESID_LS, "hiptsdbg_gemm_kernel_resources: bad argument");
+    HIPTS_TRY(use_device(0));
+#define HIPTS_RES_CASE(E) \
+    case E: return kernel_resources_t<E>(mr, f16 != 0, op8 != 0, sk != 0, interior != 0, num_regs, scratch_bytes, static_lds)
+    switch (epi) {
+        HIPTS_RES_CASE(EPI_PATCH); HIPTS_RES_CASE(EPI_QK); HIPTS_RES_CASE(EPI_VT); HIPTS_RES_CASE(EPI_RESID); HIPTS_RES_CASE(EPI_GELU);
+        HIPTS_RES_CASE(EPI_HEAD); HIPTS_RES_CASE(EPI_STAR); HIPTS_RES_CASE(EPI_RESCALE); HIPTS_RES_CASE(EPI_BIAS); HIPTS_RES_CASE(EPI_RESID_LN);
+        HIPTS_RES_CASE(EPI_QK_ROPE); HIPTS_RES_CASE(EPI_SWIGLU); HIPTS_RES_CASE(EPI_RESID_ROWSTAT); HIPTS_RES_CASE(EPI_RESID_XG);
+        HIPTS_RES_CASE(EPI_RESID_XGI); HIPTS_RES_CASE(EPI_RESID_LS);
+    }
+#undef HIPTS_RES_CASE
+    return set_error(HIPTS_ERR_INVALID, "hiptsdbg_gemm_kernel_resources: unknown epilogue");
 }
 
 // Development/test aid (not part of the public ABI), host only: the launcher's plan for a launch described by numbers

@@ -636,7 +636,14 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
             // load and per store -- 142 branches, the block's loads drained with s_waitcnt vmcnt(0) together with the stores of the
             // block before, four drains per tile (profiles/r04_c_resid_epilogue.txt).  Here the loop is one basic block: the next
             // pair's eight loads are requested BEFORE this pair's read-modify-write, statistics and staged 16-bit copy (two register
-            // sets; the waits are counted), and the stores never wait.  Same operations in the same order: the bits do not change.
+            // sets), and the stores never wait.  Same operations in the same order: the bits do not change.
+            // The waits as compiled: turns 2 and 3 count (vmcnt(21) ... vmcnt(12)); turn 0 opens with one s_waitcnt vmcnt(0) that is hipcc's,
+            // not the source's.  (It stays when the next tile's K-tile 0 is not requested in front of the epilogue and when this loop is one
+            // basic block; as far as we can tell hipcc, which does not see the inline-assembly waits that retire the main loop's LDS-DMA
+            // requests, makes its first wait for a load behind them a full one.)  So turn 0 also waits for turn 1's eight loads, requested
+            // right behind its own -- vmcnt retires in order: a few issue slots -- and turn 1 needs no wait.  Nothing here may be spilled: a
+            // scratch reload is a load with a vmcnt(0) of its own, behind the turn's stores; hence the caller's lane number that the
+            // compiler cannot hoist from (gemm_pp_kernel, `elane`).
             if constexpr (INT) {
                 static_assert(MR == 8, "interior epilogue: full tiles");
                 // the per-column vectors (gamma, bias, col_u) are read from LDS where they are used instead of living in 48 registers:

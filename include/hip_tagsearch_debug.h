@@ -83,6 +83,10 @@ typedef struct hiptsdbg_gemm_plan_t {
  * refuses returns its error (and out->error). */
 int hiptsdbg_gemm_plan(int epi, int M, int N, int K, int f16, int shared_chip, unsigned features, int ld_out, int dim, int cus,
                        unsigned q4_mask, hiptsdbg_gemm_plan_t* out);
+/* What the loaded code object says of the ping-pong GEMM kernel the launcher picks for (epilogue, mr = tile rows / 32, operand type,
+ * e4m3 operands, split-K, interior), from hipFuncGetAttributes: VGPRs per lane, bytes of scratch (private segment) per lane -- 0 means
+ * nothing is spilled --, bytes of static LDS.  A combination no kernel is built for is refused. */
+int hiptsdbg_gemm_kernel_resources(int epi, int mr, int f16, int op8, int sk, int interior, int* num_regs, int* scratch_bytes, int* static_lds);
 /* ONE production launch -- launch_gemm(epi, g, null stream): the plan is gemm_plan()'s for this process and device, nothing is forced --
  * on caller-supplied operands, every output copied back whole (csrc/gemm_dbg.hip; tests/test_gpu_gemm_epi.py).
  * Inputs (host): a [M][K] and w [N][K] as 16-bit patterns (bf16, or IEEE half with f16 = 1; the entry pads w with zero rows to a multiple
