@@ -73,8 +73,9 @@ __device__ __forceinline__ i32x8 read_frag8(const char* lds_tile, int rowblk, in
 // GELU of four values at once, in packed fp32 (v_pk_mul/fma/add_f32 process two floats per lane and issue slot -- the GELU epilogue
 // is VALU-bound: 128 values per lane, two waves per SIMD).  Every epilogue form calls this one function, so a value does not depend on
 // the path its tile took.
-__device__ __forceinline__ f32x4 gelu_f4(f32x4 x, int tanh_form) {
-    if (tanh_form) {
+template <bool TANH>
+__device__ __forceinline__ f32x4 gelu_f4(f32x4 x) {
+    if constexpr (TANH) {
         // torch gelu(approximate='tanh'): 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3).
         // 0.5 (1 + tanh(u)) = sigmoid(2u) = 1 / (1 + 2^(-2 u log2 e)): one v_exp_f32 + one v_rcp_f32 per value.
         // exponent of 2: -2 log2(e) sqrt(2/pi) (x + 0.044715 x^3) = x (c1 + c2 x^2), explicit fma (the file is built with -ffp-contract=off)
@@ -108,6 +109,8 @@ __device__ __forceinline__ f32x4 gelu_f4(f32x4 x, int tanh_form) {
     const f32x4 r = (xc * p) * rq;
     return x * (r + k4(0.5f));
 }
+// the form as a run-time argument (gelu_probe_kernel); the epilogues branch once per tile and call the form they need
+__device__ __forceinline__ f32x4 gelu_f4(f32x4 x, int tanh_form) { return tanh_form ? gelu_f4<true>(x) : gelu_f4<false>(x); }
 
 // (rstd, rstd * mean) of a row from its (sum, sum of squares) over ln_dim columns: the one finish of a folded LayerNorm's statistics
 __device__ __forceinline__ float2 ln_stat_pair(const GemmArgs& a, float s1, float s2) {
@@ -845,6 +848,26 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
                 return;
             }
         }
+        if constexpr (EPI == EPI_GELU) {
+            // the form (tanh: the ViT; erf: SwinV2, ConvNeXt) is the launch's: ONE uniform branch around the rows, each copy with its own
+            // form only.  gelu_f4 is the staged epilogue's function, so a value does not depend on the path
+            auto rows = [&](auto form) __attribute__((always_inline)) {
+#pragma unroll
+                for (int i = 0; i < MR; ++i) {
+                    const int m = m0 + wave_m * (MR * 16) + i * 16 + lr;
+                    if (m >= a.M) continue;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (!nv[j]) continue;
+                        const f32x4 gv = gelu_f4<decltype(form)::value>(acc[i][j] + bv[j]);
+                        *reinterpret_cast<bf16x4*>(a.out_bf16 + (size_t)m * ld + nc[j]) = pack4<F16>(gv[0], gv[1], gv[2], gv[3]);
+                    }
+                }
+            };
+            if (a.gelu_tanh) rows(std::true_type{});
+            else rows(std::false_type{});
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < MR; ++i) {
             const int m = m0 + wave_m * (MR * 16) + i * 16 + lr;
@@ -869,15 +892,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
                     const f32x4 v = star_relu4(acc[i][j] + bv[j], a.star_scale, a.star_bias, a.star_kind);
                     *reinterpret_cast<bf16x4*>(a.out_bf16 + (size_t)m * ld + nc[j]) = pack4<F16>(v[0], v[1], v[2], v[3]);
                 }
-            } else if constexpr (EPI == EPI_GELU) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (!nv[j]) continue;
-                    const f32x4 v = acc[i][j] + bv[j];
-                    const f32x4 gv = gelu_f4(v, a.gelu_tanh);           // the staged epilogue's function, so a value does not depend on the path
-                    const bf16x4 o = pack4<F16>(gv[0], gv[1], gv[2], gv[3]);
-                    *reinterpret_cast<bf16x4*>(a.out_bf16 + (size_t)m * ld + nc[j]) = o;
-                }
             } else if constexpr (EPI == EPI_QK) {
                 const int b = m / a.tokens, t = m - b * a.tokens;
 #pragma unroll
@@ -901,13 +915,26 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MR
 // Image128 (`region`, in the LDS stage the main loop has left free) and reads it back row-contiguous (RowImage, read_back_pass).
 // The arms: V^T (the image's rows are the columns d), SWIGLU (the product as half rows), and the row images of GELU / STAR
 // (row-major out) and QK / QK_ROPE (the q | k | v layouts).
-template <int EPI, int MR, bool F16>
+template <int EPI, int MR, bool F16, int FORM = -1>
 __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& a, f32x4 (&acc)[MR][4], int m0, int n0, int wave_m, int wave_n,
                                                      int lane, char* region, const f32x4* bias_pre = nullptr, const float2* st_lds = nullptr,
                                                      float2* red = nullptr) {
     // red (SWIGLU with stat_part, persistent loop): [256 rows][4 waves] in LDS -- the four waves of a row leave their partial row sums
     // there and the caller adds them into ONE pair per (256-column tile, row)
     // st_lds: (rstd, rstd * mean) of the tile's rows m0 .. m0 + 255, finished from the producer's partials by the caller
+    // FORM (EPI_GELU; callers leave it at -1): 1 the tanh form, 0 the erf form.  The form is the launch's (GemmArgs::gelu_tanh), so a
+    // tile takes ONE uniform branch here and runs a copy that holds its own form only, straight-line code between its f32x4 groups.
+    // With a branch per group the tile's epilogue was 32 basic blocks: the scheduler could not move a ds_write, a conversion or a
+    // transcendental's latency across them, and the row pair (rstd, rstd * mean) was copied into {s, s} register pairs for the packed
+    // multiplies of every group (138 moves per tile and wave) where it now feeds them through op_sel.
+    // (The same for EPI_QK -- copies for a tile that lies wholly in q, or in k or v, when dim % 256 == 0, k and v without the
+    // multiplication by 1.0f -- was tried and dropped: gemm_pp_kernel<QK, 8> went from 241 to 253 registers and 76 to 89 spilled
+    // scalars, and its peeled first K-tile changed; LABNOTES.)
+    if constexpr (EPI == EPI_GELU && FORM < 0) {
+        if (a.gelu_tanh) gemm_epilogue_staged<EPI, MR, F16, 1>(a, acc, m0, n0, wave_m, wave_n, lane, region, bias_pre, st_lds, red);
+        else gemm_epilogue_staged<EPI, MR, F16, 0>(a, acc, m0, n0, wave_m, wave_n, lane, region, bias_pre, st_lds, red);
+        return;
+    }
     f32x4 bias_v[4];
     epi_bias<EPI>(a, n0, wave_n, lane, bias_pre, bias_v);
     static_assert(EPI == EPI_VT || EPI == EPI_GELU || EPI == EPI_STAR || EPI == EPI_QK || EPI == EPI_QK_ROPE || EPI == EPI_SWIGLU,
@@ -1065,7 +1092,7 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmArgs& a, f32x4 (&
                     }
                     bf16x4 o;
                     if constexpr (EPI == EPI_GELU) {
-                        const f32x4 gv = gelu_f4(v, a.gelu_tanh);
+                        const f32x4 gv = gelu_f4<FORM == 1>(v);
                         o = pack4<F16>(gv[0], gv[1], gv[2], gv[3]);
                     } else if constexpr (EPI == EPI_STAR) {
                         const f32x4 gv = star_relu4(v, a.star_scale, a.star_bias, a.star_kind);
