@@ -36,8 +36,11 @@
 namespace hipts {
 namespace {
 
+// Waves per SIMD the 4-wave sequential kernel (MODE 1, NW = 4: the default geometry) is compiled for: 4 -> at most 128 registers, which the
+// half-operand body fills to the last one (128, nothing spilled; bf16 operands: 121); 3 (-DHIPTS_ATTN2_SEQ_WAVES=3, the A/B build) -> 138.
+// tests/test_gpu_attention_resources.py holds the default to 128 registers and no scratch.  The 8-wave geometry stays at 3.
 #ifndef HIPTS_ATTN2_SEQ_WAVES
-#define HIPTS_ATTN2_SEQ_WAVES 3          // waves per SIMD the sequential body (MODE 1) is compiled for: 4 -> 128 registers, 3 -> 168
+#define HIPTS_ATTN2_SEQ_WAVES 4
 #endif
 constexpr int KV = 64;                   // keys per tile
 constexpr int HD = 64;
@@ -119,13 +122,17 @@ __device__ __forceinline__ void load_q_frags(const bf16_t* q, int bh, int tokens
 // 16 scores of a 32-key block -> P = 2^(S - m_ref) (PRESUB: the accumulator started at -m_ref; bf16 operands: m_ref = 0, nothing to
 // subtract) as operand words w0 (keys crow(0 .. 7)) / w1 (crow(8 .. 15)), the row sum in two alternating partial sums.
 // (sacc by value: by reference the two-block geometry, QB = 2, came out with other registers and 256 instead of 80 B of scratch.)
-template <bool F16, bool PRESUB>
+// START: ls0 / ls1 come in undefined and START from the block's first two pairs.  The same bits as starting them at 0.f -- a pair is the
+// sum of two exp2 results, never -0 -- but hipcc has to keep a `0 + x` it is given (x = -0), one v_add_f32 per partial sum and block.
+template <bool F16, bool PRESUB, bool START = false>
 __device__ __forceinline__ void exp_sum_pack(const f32x16 sacc, const float m_ref, bf16x8& w0, bf16x8& w1, float& ls0, float& ls1) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const float p0 = __builtin_amdgcn_exp2f((F16 && !PRESUB) ? sacc[i] - m_ref : sacc[i]);
         const float p1 = __builtin_amdgcn_exp2f((F16 && !PRESUB) ? sacc[8 + i] - m_ref : sacc[8 + i]);
-        if (i & 1) ls1 += p0 + p1; else ls0 += p0 + p1;
+        if (START && i == 0) ls0 = p0 + p1;
+        else if (START && i == 1) ls1 = p0 + p1;
+        else if (i & 1) ls1 += p0 + p1; else ls0 += p0 + p1;
         w0[i] = to_op<F16>(p0);
         w1[i] = to_op<F16>(p1);
     }
@@ -355,6 +362,8 @@ __device__ __forceinline__ bool attn2_body(char* __restrict__ smem, const bf16_t
 // The same pass with the least state per wave (MODE 1): the two 32-key halves of a tile go S -> softmax -> P V one after the other, so a
 // wave holds one 32 x 32 score block instead of two plus a lagging P (about 100 registers instead of 150-160): four waves per SIMD, and
 // the overlap of one wave's softmax with another's MFMAs is left entirely to the hardware.  Ring: two K and two V slots (one tile ahead).
+// What the wave keeps across the tile loop is O, Q, the half-operand accumulator seed and the fragment addresses of slot 0: the DMA sources
+// are scalar bases plus one lane offset per operand, the ring slot is an immediate of the LDS reads (the walk at the end of the body).
 template <bool F16, int NW>
 __device__ __forceinline__ bool attn2_seq_body(char* __restrict__ smem, const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                const bf16_t* __restrict__ v, bf16_t* __restrict__ out, int heads, int tokens, int tokens_pad,
@@ -372,25 +381,36 @@ __device__ __forceinline__ bool attn2_seq_body(char* __restrict__ smem, const bf
 #ifdef HIPTS_X_STAMPS
     const bool stamp_on = blockIdx.x == HIPTS_X_STAMPS && wave == 0;
 #endif
-    unsigned kgo[PCS], vgo[PCS];                     // element offsets of this lane's DMA sources inside a tile
+    // LDS-DMA sources: a scalar base per piece (tile t of this (image, head), advanced by scalar adds) plus ONE 32-bit lane offset per
+    // operand -- piece wave + NW pc lies NW pc KiB behind piece `wave` in the tile as in the slot, and its rows, a multiple of 16 further
+    // on, swizzle the same.  No per-lane 64-bit pointers live across the tile loop, no vector address arithmetic inside it.
+    static_assert(PCS == 1 || (NW * 8) % 16 == 0, "the pieces of a wave must swizzle alike");
+    const int row0 = wave * 8 + (lane >> 3);
+    unsigned kgo = row0 * (HD * 2) + k_src_chunk(row0, lane) * 16;            // byte offsets of this lane's DMA sources inside a tile
+    unsigned vgo = row0 * (HD * 2) + v_src_chunk(row0, lane) * 16;
+    const char* kb = reinterpret_cast<const char*>(k + (size_t)bh * tokens_pad * HD);
+    const char* vb = reinterpret_cast<const char*>(v + (size_t)bh * tokens_pad * HD);
+    auto stage = [&](int t, int slot) __attribute__((always_inline)) {              // tile t -> ring slot `slot` (a constant where it is called)
+        const int sl = slot * TILE;
+        // bases and offsets opaque where they meet: left visible, hipcc hoists base + lane offset (or the offset's zero extension) out of
+        // the loop and the loads take 64-bit lane pointers again instead of the SGPR base + 32-bit VGPR offset form
+        asm("" : "+v"(kgo), "+v"(vgo));
 #pragma unroll
-    for (int pc = 0; pc < PCS; ++pc) {
-        const int row = (wave + NW * pc) * 8 + (lane >> 3);
-        kgo[pc] = row * HD + k_src_chunk(row, lane) * 8;
-        vgo[pc] = row * HD + v_src_chunk(row, lane) * 8;
-    }
-    const bf16_t* kb = k + (size_t)bh * tokens_pad * HD;
-    const bf16_t* vb = v + (size_t)bh * tokens_pad * HD;
-    auto stage = [&](int t) __attribute__((always_inline)) {
-        const int sl = (t % SNS) * TILE;
+        for (int pc = 0; pc < PCS; ++pc) {
+            const char* ks = kb + (size_t)t * TILE + NW * pc * 1024;
+            asm("" : "+s"(ks));
+            glds16(ks + kgo, smem + sl + (wave + NW * pc) * 1024);
+        }
 #pragma unroll
-        for (int pc = 0; pc < PCS; ++pc) glds16(kb + (size_t)t * (KV * HD) + kgo[pc], smem + sl + (wave + NW * pc) * 1024);
-#pragma unroll
-        for (int pc = 0; pc < PCS; ++pc) glds16(vb + (size_t)t * (KV * HD) + vgo[pc], smem + VB + sl + (wave + NW * pc) * 1024);
+        for (int pc = 0; pc < PCS; ++pc) {
+            const char* vs = vb + (size_t)t * TILE + NW * pc * 1024;
+            asm("" : "+s"(vs));
+            glds16(vs + vgo, smem + VB + sl + (wave + NW * pc) * 1024);
+        }
     };
     bf16x8 qf[4];
     load_q_frags(q, bh, tokens_pad, q0 + r, h, qf);
-    stage(0);
+    stage(0, 0);
     int ka[4], va[2];
     k_frag_addrs(r, h, 0, ka);
     v_frag_addrs(lane, h, VB, va);
@@ -439,8 +459,8 @@ __device__ __forceinline__ bool attn2_seq_body(char* __restrict__ smem, const bf
         constexpr bool FIRST = decltype(first_c)::value;
         constexpr bool PRESUB = F16 && !FIRST;
         if constexpr (F16 && FIRST) m_ref = ref_exponent<1>(&sacc);      // the reference: this row's maximum over the first 32 keys
-        float ls0 = 0.f, ls1 = 0.f;
-        exp_sum_pack<F16, PRESUB>(sacc, m_ref, w0, w1, ls0, ls1);
+        float ls0, ls1;
+        exp_sum_pack<F16, PRESUB, true>(sacc, m_ref, w0, w1, ls0, ls1);
         l_run += ls0 + ls1;
     };
     auto pv = [&](const bf16x8 (&vf)[2][2], const bf16x8& w0, const bf16x8& w1) __attribute__((always_inline)) {
@@ -450,17 +470,19 @@ __device__ __forceinline__ bool attn2_seq_body(char* __restrict__ smem, const bf
             o[blk] = mfma_32x32x16<F16>(vf[blk][1], w1, o[blk]);
         }
     };
-    auto step = [&](int t, auto first_c, auto last_c) __attribute__((always_inline)) {
+    // Tile t sits in ring slot `slot` = t % 2.  The walk below names the slot of the first and of the middle steps as a constant: the
+    // slot's offset is then part of the ds_read's immediate and ka / va are the address registers themselves.
+    auto step = [&](int t, int slot, auto first_c, auto last_c) __attribute__((always_inline)) {
         constexpr bool LAST = decltype(last_c)::value;
         HIPTS_STAMP(t * 16 + 0);
         wait_vm<0>();                                // tile t (requested one step ago) has landed for this wave ...
         HIPTS_STAMP(t * 16 + 5);
         __builtin_amdgcn_s_barrier();                // ... and for every wave; tile t - 1's slots are free
         HIPTS_STAMP(t * 16 + 6);
-        if (t + SNS - 1 < nkv) stage(t + SNS - 1);
+        if constexpr (!LAST) stage(t + 1, slot ^ 1);  // every step but the last has a next tile
         if (!active) return;
         HIPTS_STAMP(t * 16 + 1);
-        int sl = (t % SNS) * TILE;
+        const int sl = slot * TILE;
         const bool two = !(LAST && tail_keys <= 32);
         bf16x8 kf0[4], kf1[4], vf[2][2], w0, w1;
         f32x16 sacc;
@@ -491,11 +513,18 @@ __device__ __forceinline__ bool attn2_seq_body(char* __restrict__ smem, const bf
             HIPTS_STAMP(t * 16 + 12);
         }
     };
-    if (nkv == 1) step(0, T_{}, T_{});
+    static_assert(SNS == 2, "the walk names two slots");
+    if (nkv == 1) step(0, 0, T_{}, T_{});
     else {
-        step(0, T_{}, F_{});
-        for (int t = 1; t + 1 < nkv; ++t) step(t, F_{}, F_{});
-        step(nkv - 1, F_{}, T_{});
+        step(0, 0, T_{}, F_{});
+        if (nkv > 2)                                 // the middle tiles 1 .. nkv - 2, two by two: odd tiles in slot 1, even ones in slot 0
+            for (int t = 1;;) {
+                step(t, 1, F_{}, F_{});
+                if (++t + 1 >= nkv) break;
+                step(t, 0, F_{}, F_{});
+                if (++t + 1 >= nkv) break;
+            }
+        step(nkv - 1, (nkv - 1) & 1, F_{}, T_{});
     }
     if (!active) return false;
 
@@ -619,7 +648,7 @@ __device__ __forceinline__ void attn2_classic(char* __restrict__ smem, const bf1
 }
 
 template <bool F16, int QB, int NW, int MODE>
-__global__ __launch_bounds__(NW * 64, MODE == 1 ? HIPTS_ATTN2_SEQ_WAVES : 2) void attn2_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
+__global__ __launch_bounds__(NW * 64, MODE == 1 ? (NW == 4 ? HIPTS_ATTN2_SEQ_WAVES : 3) : 2) void attn2_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                         bf16_t* __restrict__ out, int heads, int tokens, int tokens_pad, int chunks, int out_stride,
                                                         int classic, int out_ld, int lo_off, float lo_scale) {
     // ALL of the kernel's LDS is this one array (ring + the fallback flag word): with a second LDS object in the kernel -- __syncthreads_or()
@@ -709,9 +738,14 @@ __global__ __launch_bounds__(256, 1) void attn3_kernel(const bf16_t* __restrict_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// probe != null (here and in launch_cfg): nothing is launched, *probe receives the function attributes of the kernel the launch would run
 template <bool F16>
 int launch_attn3(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int batch, int heads, int tokens, int tokens_pad, int ost, int classic,
-                 int out_ld, int lo_off, float lo_scale, hipStream_t s) {
+                 int out_ld, int lo_off, float lo_scale, hipStream_t s, hipFuncAttributes* probe) {
+    if (probe) {
+        HIPTS_HIP(hipFuncGetAttributes(probe, (const void*)attn3_kernel<F16>));
+        return HIPTS_OK;
+    }
     static PerDevice attr;
     int dev = 0;
     const int cus = current_device_cus(&dev);
@@ -736,7 +770,11 @@ int launch_attn3(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out,
 
 template <bool F16, int QB, int NW, int MODE>
 int launch_cfg(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int batch, int heads, int tokens, int tokens_pad, int ost,
-               int classic, int out_ld, int lo_off, float lo_scale, hipStream_t s) {
+               int classic, int out_ld, int lo_off, float lo_scale, hipStream_t s, hipFuncAttributes* probe) {
+    if (probe) {
+        HIPTS_HIP(hipFuncGetAttributes(probe, (const void*)attn2_kernel<F16, QB, NW, MODE>));
+        return HIPTS_OK;
+    }
     const int nb = (tokens + 32 * QB - 1) / (32 * QB);
     const int chunks = (nb + NW - 1) / NW;
     attn2_kernel<F16, QB, NW, MODE><<<batch * heads * chunks, NW * 64, 0, s>>>(q, k, v, out, heads, tokens, tokens_pad, chunks, ost, classic, out_ld, lo_off, lo_scale);
@@ -744,12 +782,9 @@ int launch_cfg(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, i
     return HIPTS_OK;
 }
 
-}  // namespace
-
-// q, k, v: [batch * heads][tokens_pad][64] 16-bit (q pre-scaled by head_dim^-0.5 log2 e; rows past `tokens` zero), out [batch * out_stride][heads * 64].
-// variant: 0 = default; 1: 4 waves x 64 rows, 2: 8 waves x 32 rows, 3: 4 waves x 32 rows (A/B, hiptsdbg_attention2_*).
-int launch_attention2(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int batch, int heads, int tokens, int tokens_pad, bool f16,
-                      hipStream_t s, int out_tokens_stride, int variant, int split_lo, float lo_scale) {
+// The one place that picks the kernel: launch_attention2 launches it, attention2_kernel_resources (probe != null) describes it.
+int attention2_dispatch(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int batch, int heads, int tokens, int tokens_pad, bool f16,
+                        hipStream_t s, int out_tokens_stride, int variant, int split_lo, float lo_scale, hipFuncAttributes* probe) {
     const int ost = out_tokens_stride > 0 ? out_tokens_stride : tokens;
     // split_lo: rows of `out` are [hi (heads * 64) | lo (heads * 64)] -- the output as a hi | lo pair of 16-bit halves
     const int out_ld = split_lo ? 2 * heads * HD : heads * HD, lo_off = split_lo ? heads * HD : 0;
@@ -758,11 +793,11 @@ int launch_attention2(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t*
     static const int env_variant = getenv("HIPTS_ATTN2") ? atoi(getenv("HIPTS_ATTN2")) : 0;
     if (variant == 0) variant = env_variant ? env_variant : 5;
 #define HIPTS_ATTN2_CASE(QB_, NW_, MODE_)                                                                                        \
-    return f16 ? launch_cfg<true, QB_, NW_, MODE_>(q, k, v, out, batch, heads, tokens, tokens_pad, ost, classic, out_ld, lo_off, lo_scale, s)                      \
-               : launch_cfg<false, QB_, NW_, MODE_>(q, k, v, out, batch, heads, tokens, tokens_pad, ost, classic, out_ld, lo_off, lo_scale, s)
+    return f16 ? launch_cfg<true, QB_, NW_, MODE_>(q, k, v, out, batch, heads, tokens, tokens_pad, ost, classic, out_ld, lo_off, lo_scale, s, probe)               \
+               : launch_cfg<false, QB_, NW_, MODE_>(q, k, v, out, batch, heads, tokens, tokens_pad, ost, classic, out_ld, lo_off, lo_scale, s, probe)
     if (variant == 6 && tokens_pad >= 2 * KV)
-        return f16 ? launch_attn3<true>(q, k, v, out, batch, heads, tokens, tokens_pad, ost, classic, out_ld, lo_off, lo_scale, s)
-                   : launch_attn3<false>(q, k, v, out, batch, heads, tokens, tokens_pad, ost, classic, out_ld, lo_off, lo_scale, s);
+        return f16 ? launch_attn3<true>(q, k, v, out, batch, heads, tokens, tokens_pad, ost, classic, out_ld, lo_off, lo_scale, s, probe)
+                   : launch_attn3<false>(q, k, v, out, batch, heads, tokens, tokens_pad, ost, classic, out_ld, lo_off, lo_scale, s, probe);
     if (variant == 6) variant = 5;
     switch (variant) {
         case 1: HIPTS_ATTN2_CASE(2, 4, 0);
@@ -772,6 +807,26 @@ int launch_attention2(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t*
         default: HIPTS_ATTN2_CASE(1, 4, 0);
     }
 #undef HIPTS_ATTN2_CASE
+}
+
+}  // namespace
+
+// q, k, v: [batch * heads][tokens_pad][64] 16-bit (q pre-scaled by head_dim^-0.5 log2 e; rows past `tokens` zero), out [batch * out_stride][heads * 64].
+// variant: 0 = default; 1: 4 waves x 64 rows, 2: 8 waves x 32 rows, 3: 4 waves x 32 rows (A/B, hiptsdbg_attention2_*).
+int launch_attention2(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int batch, int heads, int tokens, int tokens_pad, bool f16,
+                      hipStream_t s, int out_tokens_stride, int variant, int split_lo, float lo_scale) {
+    return attention2_dispatch(q, k, v, out, batch, heads, tokens, tokens_pad, f16, s, out_tokens_stride, variant, split_lo, lo_scale, nullptr);
+}
+
+// Registers per lane, bytes of scratch per lane and bytes of static LDS of the kernel launch_attention2 runs for (tokens_pad, operand type,
+// variant) in this process, from the loaded code object (hipFuncGetAttributes).
+int attention2_kernel_resources(int tokens_pad, bool f16, int variant, int* num_regs, int* scratch_bytes, int* static_lds) {
+    hipFuncAttributes at;
+    HIPTS_TRY(attention2_dispatch(nullptr, nullptr, nullptr, nullptr, 1, 1, tokens_pad, tokens_pad, f16, nullptr, 0, variant, 0, 1.0f, &at));
+    *num_regs = at.numRegs;
+    *scratch_bytes = (int)at.localSizeBytes;
+    *static_lds = (int)at.sharedSizeBytes;
+    return HIPTS_OK;
 }
 
 #ifdef HIPTS_X_STAMPS

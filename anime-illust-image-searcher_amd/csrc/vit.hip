@@ -1276,6 +1276,12 @@ extern "C" int hiptsdbg_attention2(const uint16_t* q, const uint16_t* k, const u
     return rc;
 }
 
+extern "C" int hiptsdbg_attention2_kernel_resources(int tokens_pad, int f16, int variant, int* num_regs, int* scratch_bytes, int* static_lds) {
+    HIPTS_REQUIRE(num_regs && scratch_bytes && static_lds && tokens_pad >= 64 && tokens_pad % 64 == 0, "hiptsdbg_attention2_kernel_resources: bad arguments");
+    HIPTS_TRY(use_device(0));
+    return attention2_kernel_resources(tokens_pad, f16 != 0, variant, num_regs, scratch_bytes, static_lds);
+}
+
 extern "C" int hiptsdbg_attention2_stamps(unsigned long long* host, int n) { return attention2_read_stamps(host, n); }
 
 // Development aid: copy one workspace buffer of the last forward to the host (tools/determinism.py).

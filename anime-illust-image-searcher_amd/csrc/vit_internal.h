@@ -320,6 +320,10 @@ inline float split_lo_scale(bool f16) {
     return f16 ? 64.0f : 1.0f;
 }
 
+// What the loaded code object says of the kernel launch_attention2 picks for (tokens_pad, operand type, variant): registers per lane,
+// bytes of scratch per lane (0: nothing is spilled), bytes of static LDS.  Nothing is launched.
+int attention2_kernel_resources(int tokens_pad, bool f16, int variant, int* num_regs, int* scratch_bytes, int* static_lds);
+
 int attention2_read_stamps(unsigned long long* host, int n);      // measurement-only builds (HIPTS_X_STAMPS)
 
 // swin_attn.hip: SwinV2 window attention, head_dim 32, window^2 <= 256 tokens: qkv float32 [batch * side^2][3 * 32 heads] (raster order, bias

@@ -153,6 +153,11 @@ int hiptsdbg_attention_time(const uint16_t* q, const uint16_t* k, const uint16_t
 int hiptsdbg_attention2(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out_host, int batch, int heads, int tokens, int tokens_pad,
                         int f16, int variant, int iters, double* avg_us);
 
+/* What the loaded code object says of the kernel that hiptsdbg_attention2 (launch_attention2) runs for (tokens_pad, operand type, variant)
+ * in this process, from hipFuncGetAttributes: VGPRs per lane, bytes of scratch (private segment) per lane -- 0 means nothing is spilled --,
+ * bytes of static LDS.  Nothing is launched. */
+int hiptsdbg_attention2_kernel_resources(int tokens_pad, int f16, int variant, int* num_regs, int* scratch_bytes, int* static_lds);
+
 /* Measurement-only builds of csrc/attn2.hip (-DHIPTS_X_STAMPS=<workgroup>): the cycle stamps of one wave (tools/attn2_check.py stamps);
  * HIPTS_ERR_STATE in an ordinary build. */
 int hiptsdbg_attention2_stamps(unsigned long long* host, int n);
