@@ -1276,6 +1276,36 @@ extern "C" int hiptsdbg_attention2(const uint16_t* q, const uint16_t* k, const u
     return rc;
 }
 
+// ONE production launch of launch_attention2 with its whole argument list (tests/test_gpu_attention_exact.py), modelled on
+// hiptsdbg_gemm_epilogue: out_host holds out_rows rows of out_ld = (split_lo ? 2 : 1) * heads * 64 16-bit values, at least batch * stride
+// of them (stride = out_tokens_stride, or tokens when that is 0) plus whatever guard rows the caller wants to watch.  The whole device
+// buffer is filled with byte 0xFF, the kernel launched once and the whole buffer copied back.
+extern "C" int hiptsdbg_attention2_launch(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out_host, long long out_rows, int batch,
+                                          int heads, int tokens, int tokens_pad, int f16, int out_tokens_stride, int variant, int split_lo) {
+    HIPTS_REQUIRE(q && k && v && out_host && batch >= 1 && heads >= 1 && tokens >= 1 && tokens_pad >= tokens, "hiptsdbg_attention2_launch: bad arguments");
+    HIPTS_REQUIRE(out_tokens_stride == 0 || out_tokens_stride >= tokens, "hiptsdbg_attention2_launch: out_tokens_stride %d below tokens %d",
+                  out_tokens_stride, tokens);
+    const long long stride = out_tokens_stride > 0 ? out_tokens_stride : tokens;
+    HIPTS_REQUIRE(out_rows >= (long long)batch * stride, "hiptsdbg_attention2_launch: %lld output rows, the launch covers %lld", out_rows,
+                  (long long)batch * stride);
+    HIPTS_TRY(use_device(0));
+    const size_t nqk = (size_t)batch * heads * tokens_pad * 64, nout = (size_t)out_rows * (split_lo ? 2 : 1) * heads * 64;
+    DevBuf dq, dk, dv, dout;
+    HIPTS_TRY(dq.alloc(nqk * 2));
+    HIPTS_TRY(dk.alloc(nqk * 2));
+    HIPTS_TRY(dv.alloc(nqk * 2));
+    HIPTS_TRY(dout.alloc(nout * 2));
+    HIPTS_TRY(upload(dq.p, q, nqk * 2));
+    HIPTS_TRY(upload(dk.p, k, nqk * 2));
+    HIPTS_TRY(upload(dv.p, v, nqk * 2));
+    HIPTS_HIP(hipMemset(dout.p, 0xFF, nout * 2));
+    HIPTS_TRY(launch_attention2(dq.as<bf16_t>(), dk.as<bf16_t>(), dv.as<bf16_t>(), dout.as<bf16_t>(), batch, heads, tokens, tokens_pad, f16 != 0, nullptr,
+                                out_tokens_stride, variant, split_lo ? 1 : 0, split_lo_scale(f16 != 0)));
+    HIPTS_HIP(hipDeviceSynchronize());
+    HIPTS_HIP(hipMemcpy(out_host, dout.p, nout * 2, hipMemcpyDeviceToHost));
+    return HIPTS_OK;
+}
+
 extern "C" int hiptsdbg_attention2_kernel_resources(int tokens_pad, int f16, int variant, int* num_regs, int* scratch_bytes, int* static_lds) {
     HIPTS_REQUIRE(num_regs && scratch_bytes && static_lds && tokens_pad >= 64 && tokens_pad % 64 == 0, "hiptsdbg_attention2_kernel_resources: bad arguments");
     HIPTS_TRY(use_device(0));

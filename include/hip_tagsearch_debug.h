@@ -153,6 +153,18 @@ int hiptsdbg_attention_time(const uint16_t* q, const uint16_t* k, const uint16_t
 int hiptsdbg_attention2(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out_host, int batch, int heads, int tokens, int tokens_pad,
                         int f16, int variant, int iters, double* avg_us);
 
+/* ONE production launch of the same kernel through launch_attention2 with its whole argument list (tests/test_gpu_attention_exact.py),
+ * modelled on hiptsdbg_gemm_epilogue.  q, k, v as above.  out_tokens_stride: rows an image owns in the output (0 = tokens; EVA02 passes its
+ * padded token count); variant as above (6: the persistent one-wave-per-SIMD kernel of csrc/attn3.h); split_lo != 0: rows are
+ * [hi | lo * lo_scale] (operand_f16 bit 4), lo_scale = split_lo_scale(f16) as the forwards pass it: 64 for IEEE half, 1 for bf16.
+ * out_host: out_rows rows of out_ld = (split_lo ? 2 : 1) * heads * 64 16-bit values, out_rows >= batch * stride (stride = out_tokens_stride
+ * or tokens) plus as many guard rows as the caller wants to watch.  Fill convention: the entry sets every byte of the device buffer to
+ * 0xFF, launches once and copies the whole buffer back.  0xFFFF is a NaN in both 16-bit types and never a legitimate output: a real row
+ * (image b, token t at row b * stride + t) that still holds it was not written; a gap row (t >= tokens) or guard row that no longer holds
+ * it was written by the kernel. */
+int hiptsdbg_attention2_launch(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out_host, long long out_rows, int batch, int heads,
+                               int tokens, int tokens_pad, int f16, int out_tokens_stride, int variant, int split_lo);
+
 /* What the loaded code object says of the kernel that hiptsdbg_attention2 (launch_attention2) runs for (tokens_pad, operand type, variant)
  * in this process, from hipFuncGetAttributes: VGPRs per lane, bytes of scratch (private segment) per lane -- 0 means nothing is spilled --,
  * bytes of static LDS.  Nothing is launched. */

@@ -3,7 +3,10 @@
 
 Tolerances: bound = the first GPU run's measured value x 1.25 (values in the comments below).  Conditions that are not tolerances: the
 labels selected on the trained-like checkpoint equal the oracle's on every image, u8 and f32 inputs give the same bits, batches give
-the same bits as single images, and the window attention is further from a -inf-masked oracle than its bound."""
+the same bits as single images, and the window attention is further from a -inf-masked oracle than its bound.
+
+The two exact-answer window tests (test_window_attention_counts_its_group, test_window_attention_places_every_token) are not measured:
+their inputs (tests/attention_exact.py) have a closed-form answer and their bounds follow from the 16-bit output type."""
 import ctypes
 import os
 import subprocess
@@ -102,6 +105,38 @@ def test_window_attention_matches_float64(window, shift, f16):
         err_inf = np.abs(got - want_inf).max()
         print("   against a -inf mask: %.3e" % err_inf)
         assert err_inf > ATT_MAX[f16]
+
+
+# Three windows per axis: interior windows and, shifted, all nine roll regions; 1, 2, 2, 7 and 8 key chunks of 32 (16: the launcher's limit)
+EXACT_WINDOWS = [(4, 12, 0), (4, 12, 2), (7, 21, 0), (7, 21, 3), (8, 24, 4), (14, 42, 7), (16, 48, 0), (16, 48, 8)]
+
+
+@pytest.mark.parametrize("f16", [1, 0])
+@pytest.mark.parametrize("window,side,shift", EXACT_WINDOWS)
+def test_window_attention_counts_its_group(window, side, shift, f16):
+    """Every cosine 1, no position bias: a token's output is the float64 mean of v over the tokens of its window that share its roll
+    region (tests/attention_exact.py, by roll, partition and region; checked against swinv2_ref.window_attention on the host).  Bound
+    ulp16(want) + 2^-16 max |v| from the output type: equal numerators, at most 256 float32 terms; a key across regions weighs e^-100."""
+    import attention_exact as ax
+    regions = swinv2_ref.raster_regions(side, window, shift).numpy()
+    q, k, v, ls, cpb, want = ax.window_counting(2, 2, side, window, shift, regions, f16)
+    got, _ = _window_attention_gpu(q, k, v, ls, cpb, side, window, shift, f16)
+    bad = ax.window_counting_bad(got, want, f16, float(np.abs(v).max()))
+    print("window %d side %d shift %d operand_f16 %d: max |d| %.3e" % (window, side, shift, f16, np.abs(got - want).max()))
+    assert not bad.any(), (int(bad.sum()), np.argwhere(bad)[0], np.abs(got - want).max())
+
+
+@pytest.mark.parametrize("f16", [1, 0])
+@pytest.mark.parametrize("window,side,shift", EXACT_WINDOWS)
+def test_window_attention_places_every_token(window, side, shift, f16):
+    """k[j] = the window-local index of j as two one-hot digits, q[i] = the code of the next token of i's (window, region) group: scores
+    100, 50 or 0, so o[i] = v[next(i)] within one spacing of the output type -- every query row and every key of every window placed."""
+    import attention_exact as ax
+    regions = swinv2_ref.raster_regions(side, window, shift).numpy()
+    q, k, v, ls, cpb, want = ax.window_placement(2, 2, side, window, shift, regions, f16)
+    got, _ = _window_attention_gpu(q, k, v, ls, cpb, side, window, shift, f16)
+    bad = ax.window_placement_bad(got, want, f16)
+    assert not bad.any(), (int(bad.sum()), np.argwhere(bad)[0], np.abs(got - want).max())
 
 
 def test_tiny_both_operand_modes_u8_and_f32():
