@@ -20,9 +20,16 @@
 //              of the component, whatever the interleaving); roots -> ranks by flag + scan; border rows take the smallest label among
 //              their core neighbours.  No workgroup waits for another one anywhere.
 // Compiled with -ffp-contract=off: diff = 1 - s stays one float32 subtraction.
+//
+// A second relation builds the same handle (hipts_radius_create_hamming): the Hamming distance of 128-bit image hashes (imghash.hip),
+//     j in N(i)  <=>  popcount(h_i[0] ^ h_j[0]) + popcount(h_i[1] ^ h_j[1]) <= T,
+// by hamming_pairs_kernel through the same pass 1 / scan / pass 2 / sort (radius_build); everything from the lists on is shared.
+// Its algorithmic work: rows^2 / 2 pairs per pass at nine vector instructions each (four XORs, four accumulating population counts,
+// one compare); bytes: 16 per row per block pair it takes part in, read as uniform loads, plus the lists.
 #include <algorithm>
 #include <vector>
 
+#include "../../include/hip_tagsearch_debug.h"
 #include "common.h"
 #include "rank_util.h"
 
@@ -31,6 +38,7 @@ using namespace hipts;
 struct hipts_radius {
     int device = 0;
     int64_t rows = 0, pairs = 0;
+    float pass_ms[3] = {0.f, 0.f, 0.f};                // pass 1, pass 2, row sort of the create call (hiptsdbg_radius_passes)
     DevBuf d_deg, d_ptr, d_ids;                        // int32 [rows], int64 [rows + 1], int32 [pairs]
     DevBuf ws_label, ws_flag, ws_rank, ws_out, ws_changed;      // dbscan: int32 [rows] x2, int64 [rows + 1], int32 [rows], int32
 };
@@ -308,6 +316,150 @@ __global__ __launch_bounds__(256) void radius_assign_kernel(const long long* __r
     out[i] = (int32_t)best;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The Hamming relation over 128-bit hashes (hipts_radius_create_hamming)
+// ---------------------------------------------------------------------------------------------
+constexpr int HAM_BLOCK = 256;           // rows per block = threads per workgroup: a lane per row of block I
+constexpr int HAM_UNROLL = 8;            // rows of block J per step: their 32 dwords are requested together
+constexpr int HAM_GRID_PER_CU = 32;      // workgroups per CU in the grid (8 fit at a time); the block pairs are walked grid-stride
+
+// j in N(i)  <=>  popcount(h_i ^ h_j) <= T over the four dwords.  Block pairs (I, J >= I), radius_pairs_kernel's convention: an
+// off-diagonal block credits both rows of a hit, the diagonal block is walked as the full square and credits the row side only.  A lane
+// keeps its own row of block I in registers and walks the rows of block J, whose dwords are the same for every lane: I and J are made
+// wave-uniform explicitly, so the loads are uniform ones that land in scalar registers -- four XORs against them, four population
+// counts that accumulate and one compare per pair.  Hits are rare: the ballots of HAM_UNROLL rows are ORed, and everything after that
+// runs only where the OR is non-zero.  FILL as in radius_pairs_kernel.  Rows at or beyond N take no part on either side.
+template <bool FILL>
+__global__ __launch_bounds__(HAM_BLOCK) void hamming_pairs_kernel(const uint32_t* __restrict__ words, int64_t N, int T, int64_t nblk, int64_t nwork,
+                                                                  int32_t* __restrict__ deg, const int64_t* __restrict__ ptr,
+                                                                  int32_t* __restrict__ cursor, int32_t* __restrict__ ids) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (int64_t p = blockIdx.x; p < nwork; p += gridDim.x) {
+        int64_t Id, Jd;
+        radius_decode(p, nblk, Id, Jd);
+        const int64_t I = __builtin_amdgcn_readfirstlane((int)Id), J = __builtin_amdgcn_readfirstlane((int)Jd);      // nblk < 2^23
+        const int64_t i = I * HAM_BLOCK + tid;
+        const bool iv = i < N;
+        const uint2* __restrict__ own = reinterpret_cast<const uint2*>(words) + 2 * (iv ? i : 0);      // a uint64 pointer: 8-byte aligned
+        const uint2 w0 = own[0], w1 = own[1];
+        const uint4 mine = make_uint4(w0.x, w0.y, w1.x, w1.y);
+        const int64_t j0 = J * HAM_BLOCK;
+        const int jn = (int)(N - j0 < HAM_BLOCK ? N - j0 : HAM_BLOCK);      // >= 1
+        const bool diag = I == J;
+        const uint32_t* __restrict__ other = words + 4 * j0;
+        const int tl = iv ? T : -1;                              // a lane without a row is nobody's neighbour, without a branch
+        auto hit_mask = [&](uint32_t o0, uint32_t o1, uint32_t o2, uint32_t o3) -> uint64_t {       // the lanes whose row is a neighbour of row o
+            int d = __popc(mine.x ^ o0);
+            d += __popc(mine.y ^ o1);
+            d += __popc(mine.z ^ o2);
+            d += __popc(mine.w ^ o3);
+            return __ballot(d <= tl);
+        };
+        int count = 0;                                           // pass 1: this lane's own row
+        auto credit = [&](int j, uint64_t m) {                   // m != 0, uniform
+            const bool on = (m >> lane) & 1;
+            const int64_t jr = j0 + j;
+            if (!FILL) {
+                count += on ? 1 : 0;
+                if (!diag && lane == 0) atomicAdd(&deg[jr], __popcll(m));
+            } else {
+                if (on) {
+                    const int k = atomicAdd(&cursor[i], 1);
+                    if (k < deg[i]) ids[ptr[i] + k] = (int32_t)jr;
+                }
+                if (!diag) {
+                    int base = 0;
+                    if (lane == 0) base = atomicAdd(&cursor[jr], __popcll(m));
+                    base = __builtin_amdgcn_readfirstlane(base);
+                    if (on) {
+                        const int k = base + __popcll(m & (((uint64_t)1 << lane) - 1));
+                        if (k < deg[jr]) ids[ptr[jr] + k] = (int32_t)i;
+                    }
+                }
+            }
+        };
+        int j = 0;
+        for (; j + HAM_UNROLL <= jn; j += HAM_UNROLL) {
+            uint32_t o[4 * HAM_UNROLL];
+#pragma unroll
+            for (int k = 0; k < 4 * HAM_UNROLL; ++k) o[k] = other[4 * j + k];
+            uint64_t m[HAM_UNROLL], any = 0;
+#pragma unroll
+            for (int u = 0; u < HAM_UNROLL; ++u) {
+                m[u] = hit_mask(o[4 * u], o[4 * u + 1], o[4 * u + 2], o[4 * u + 3]);
+                any |= m[u];
+            }
+            if (any == 0) continue;                              // uniform
+#pragma unroll
+            for (int u = 0; u < HAM_UNROLL; ++u)
+                if (m[u]) credit(j + u, m[u]);
+        }
+        for (; j < jn; ++j) {                                    // the ragged last block
+            const uint32_t* __restrict__ o = other + 4 * j;
+            const uint64_t m = hit_mask(o[0], o[1], o[2], o[3]);
+            if (m) credit(j, m);
+        }
+        if (!FILL && count) atomicAdd(&deg[i], count);
+    }
+}
+
+// The pass 1 / scan / pass 2 / sort protocol both relations share.  launch(fill, deg, ptr, cursor, ids) enqueues the relation's pair
+// kernel on `s`; `who` and `where` word the refusal ("<who>: <count> neighbour pairs <where>, max_pairs allows <max_pairs>").
+template <typename Launch>
+int radius_build(const char* who, const char* where, int device, int64_t N, int64_t max_pairs, hipStream_t s, hipts_radius_t** out, Launch launch) {
+    if (max_pairs == 0) {                        // the library's default: the ids may take half of what is free now
+        size_t free_b = 0, total_b = 0;
+        HIPTS_HIP(hipMemGetInfo(&free_b, &total_b));
+        max_pairs = (int64_t)(free_b / 2 / 4);
+    }
+    hipts_radius* h = new hipts_radius();
+    h->device = device;
+    h->rows = N;
+    DevBuf cursor;
+    hipEvent_t ev[5] = {};                       // around pass 1, around pass 2, after the sort
+    auto run = [&]() -> int {
+        for (auto& e : ev) HIPTS_HIP(hipEventCreate(&e));
+        HIPTS_TRY(h->d_deg.alloc((size_t)N * 4));
+        HIPTS_TRY(h->d_ptr.alloc((size_t)(N + 1) * 8));
+        HIPTS_HIP(hipMemsetAsync(h->d_deg.p, 0, (size_t)N * 4, s));
+        HIPTS_HIP(hipEventRecord(ev[0], s));
+        launch(false, h->d_deg.as<int32_t>(), nullptr, nullptr, nullptr);
+        HIPTS_LAUNCH_CHECK();
+        HIPTS_HIP(hipEventRecord(ev[1], s));
+        radius_scan_kernel<<<1, 1024, 0, s>>>(h->d_deg.as<int32_t>(), N, h->d_ptr.as<long long>());
+        HIPTS_LAUNCH_CHECK();
+        long long total = 0;
+        HIPTS_HIP(hipMemcpyAsync(&total, h->d_ptr.as<long long>() + N, 8, hipMemcpyDeviceToHost, s));
+        HIPTS_HIP(hipStreamSynchronize(s));
+        HIPTS_REQUIRE(total <= max_pairs, "%s: %lld neighbour pairs %s, max_pairs allows %lld", who, total, where, (long long)max_pairs);
+        h->pairs = total;
+        HIPTS_TRY(h->d_ids.alloc((size_t)total * 4));
+        HIPTS_TRY(cursor.alloc((size_t)N * 4));
+        HIPTS_HIP(hipMemsetAsync(cursor.p, 0, (size_t)N * 4, s));
+        HIPTS_HIP(hipEventRecord(ev[2], s));
+        launch(true, h->d_deg.as<int32_t>(), h->d_ptr.as<int64_t>(), cursor.as<int32_t>(), h->d_ids.as<int32_t>());
+        HIPTS_LAUNCH_CHECK();
+        HIPTS_HIP(hipEventRecord(ev[3], s));
+        radius_sort_rows_kernel<<<(int)N, RAD_SORT_THREADS, 0, s>>>(h->d_ptr.as<long long>(), h->d_ids.as<int32_t>());
+        HIPTS_LAUNCH_CHECK();
+        HIPTS_HIP(hipEventRecord(ev[4], s));
+        HIPTS_HIP(hipStreamSynchronize(s));
+        HIPTS_HIP(hipEventElapsedTime(&h->pass_ms[0], ev[0], ev[1]));
+        HIPTS_HIP(hipEventElapsedTime(&h->pass_ms[1], ev[2], ev[3]));
+        HIPTS_HIP(hipEventElapsedTime(&h->pass_ms[2], ev[3], ev[4]));
+        return HIPTS_OK;
+    };
+    const int st = run();
+    for (auto& e : ev)
+        if (e) (void)hipEventDestroy(e);
+    if (st != HIPTS_OK) {
+        delete h;
+        return st;
+    }
+    *out = h;
+    return HIPTS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -325,49 +477,39 @@ int hipts_radius_create(hipts_index_t* features, float threshold, int64_t max_pa
     HIPTS_REQUIRE(N < ((int64_t)1 << 31), "hipts_radius_create: %lld rows, the limit is 2^31 - 1", (long long)N);
     HIPTS_TRY(use_device(device));
     hipStream_t s = (hipStream_t)stream;
-    if (max_pairs == 0) {                        // the library's default: the ids may take half of what is free now
-        size_t free_b = 0, total_b = 0;
-        HIPTS_HIP(hipMemGetInfo(&free_b, &total_b));
-        max_pairs = (int64_t)(free_b / 2 / 4);
-    }
     const int64_t nblk = (N + RAD_BLOCK - 1) / RAD_BLOCK, nwork = nblk * (nblk + 1) / 2;
     const int grid = (int)std::min<int64_t>(nwork, (int64_t)1 << 22);
-    hipts_radius* h = new hipts_radius();
-    h->device = device;
-    h->rows = N;
-    DevBuf cursor;
-    auto run = [&]() -> int {
-        HIPTS_TRY(h->d_deg.alloc((size_t)N * 4));
-        HIPTS_TRY(h->d_ptr.alloc((size_t)(N + 1) * 8));
-        HIPTS_HIP(hipMemsetAsync(h->d_deg.p, 0, (size_t)N * 4, s));
-        radius_pairs_kernel<false><<<grid, 512, 0, s>>>(tiled, N, dim, threshold, nblk, nwork, h->d_deg.as<int32_t>(), nullptr, nullptr, nullptr);
-        HIPTS_LAUNCH_CHECK();
-        radius_scan_kernel<<<1, 1024, 0, s>>>(h->d_deg.as<int32_t>(), N, h->d_ptr.as<long long>());
-        HIPTS_LAUNCH_CHECK();
-        long long total = 0;
-        HIPTS_HIP(hipMemcpyAsync(&total, h->d_ptr.as<long long>() + N, 8, hipMemcpyDeviceToHost, s));
-        HIPTS_HIP(hipStreamSynchronize(s));
-        HIPTS_REQUIRE(total <= max_pairs, "hipts_radius_create: %lld neighbour pairs under the threshold, max_pairs allows %lld", total,
-                      (long long)max_pairs);
-        h->pairs = total;
-        HIPTS_TRY(h->d_ids.alloc((size_t)total * 4));
-        HIPTS_TRY(cursor.alloc((size_t)N * 4));
-        HIPTS_HIP(hipMemsetAsync(cursor.p, 0, (size_t)N * 4, s));
-        radius_pairs_kernel<true><<<grid, 512, 0, s>>>(tiled, N, dim, threshold, nblk, nwork, h->d_deg.as<int32_t>(), h->d_ptr.as<int64_t>(),
-                                                        cursor.as<int32_t>(), h->d_ids.as<int32_t>());
-        HIPTS_LAUNCH_CHECK();
-        radius_sort_rows_kernel<<<(int)N, RAD_SORT_THREADS, 0, s>>>(h->d_ptr.as<long long>(), h->d_ids.as<int32_t>());
-        HIPTS_LAUNCH_CHECK();
-        HIPTS_HIP(hipStreamSynchronize(s));
-        return HIPTS_OK;
-    };
-    const int st = run();
-    if (st != HIPTS_OK) {
-        delete h;
-        return st;
+    return radius_build("hipts_radius_create", "under the threshold", device, N, max_pairs, s, out,
+                        [&](bool fill, int32_t* deg, const int64_t* ptr, int32_t* cursor, int32_t* ids) {
+                            if (fill) radius_pairs_kernel<true><<<grid, 512, 0, s>>>(tiled, N, dim, threshold, nblk, nwork, deg, ptr, cursor, ids);
+                            else radius_pairs_kernel<false><<<grid, 512, 0, s>>>(tiled, N, dim, threshold, nblk, nwork, deg, ptr, cursor, ids);
+                        });
+}
+
+int hipts_radius_create_hamming(const uint64_t* hashes, int hashes_memspace, int64_t rows, int max_distance, int64_t max_pairs, int device,
+                                void* stream, hipts_radius_t** out) {
+    HIPTS_REQUIRE(out, "hipts_radius_create_hamming: null output");
+    *out = nullptr;
+    HIPTS_REQUIRE(max_distance >= 0 && max_distance <= 128, "hipts_radius_create_hamming: max_distance must be in [0, 128], got %d", max_distance);
+    HIPTS_REQUIRE(rows > 0, "hipts_radius_create_hamming: empty input");
+    HIPTS_REQUIRE(hashes && max_pairs >= 0, "hipts_radius_create_hamming: bad arguments");
+    HIPTS_REQUIRE(rows < ((int64_t)1 << 31), "hipts_radius_create_hamming: %lld rows, the limit is 2^31 - 1", (long long)rows);
+    HIPTS_TRY(use_device(device));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf copy;                                 // host hashes: a device copy that lives as long as this call (which ends synchronised)
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(hashes);
+    if (hashes_memspace != HIPTS_DEVICE) {
+        HIPTS_TRY(copy.alloc((size_t)rows * 16));
+        HIPTS_HIP(hipMemcpyAsync(copy.p, hashes, (size_t)rows * 16, hipMemcpyHostToDevice, s));
+        words = copy.as<uint32_t>();
     }
-    *out = h;
-    return HIPTS_OK;
+    const int64_t nblk = (rows + HAM_BLOCK - 1) / HAM_BLOCK, nwork = nblk * (nblk + 1) / 2;
+    const int grid = (int)std::min<int64_t>(nwork, (int64_t)HAM_GRID_PER_CU * current_device_cus());
+    return radius_build("hipts_radius_create_hamming", "within the distance", device, rows, max_pairs, s, out,
+                        [&](bool fill, int32_t* deg, const int64_t* ptr, int32_t* cursor, int32_t* ids) {
+                            if (fill) hamming_pairs_kernel<true><<<grid, HAM_BLOCK, 0, s>>>(words, rows, max_distance, nblk, nwork, deg, ptr, cursor, ids);
+                            else hamming_pairs_kernel<false><<<grid, HAM_BLOCK, 0, s>>>(words, rows, max_distance, nblk, nwork, deg, ptr, cursor, ids);
+                        });
 }
 
 int hipts_radius_destroy(hipts_radius_t* h) {
@@ -382,6 +524,14 @@ int hipts_radius_info(const hipts_radius_t* h, int64_t* rows, int64_t* pairs) {
     HIPTS_REQUIRE(h, "hipts_radius_info: null handle");
     if (rows) *rows = h->rows;
     if (pairs) *pairs = h->pairs;
+    return HIPTS_OK;
+}
+
+int hiptsdbg_radius_passes(const hipts_radius_t* h, double* pass1_ms, double* pass2_ms, double* sort_ms) {
+    HIPTS_REQUIRE(h, "null handle");
+    if (pass1_ms) *pass1_ms = h->pass_ms[0];
+    if (pass2_ms) *pass2_ms = h->pass_ms[1];
+    if (sort_ms) *sort_ms = h->pass_ms[2];
     return HIPTS_OK;
 }
 

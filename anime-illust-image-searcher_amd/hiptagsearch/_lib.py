@@ -148,6 +148,8 @@ _SIGNATURES = {
     "hipts_radius_info": [c_void_p, POINTER(c_int64), POINTER(c_int64)],
     "hipts_radius_read": [c_void_p, c_void_p, c_void_p],
     "hipts_radius_dbscan": [c_void_p, c_int, c_void_p, POINTER(c_int64), POINTER(c_int32)],
+    "hipts_image_hash_u8": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p],
+    "hipts_radius_create_hamming": [c_void_p, c_int, c_int64, c_int, c_int64, c_int, c_void_p, POINTER(c_void_p)],
     "hipts_rerank_finish": [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "hipts_query_profile_enable": [c_void_p, c_int],
     "hipts_query_profile_read": [c_void_p, c_int, POINTER(c_double), POINTER(c_int64), POINTER(c_double)],

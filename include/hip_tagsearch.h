@@ -595,6 +595,37 @@ int hipts_radius_read(hipts_radius_t* h, int64_t* ptr_out, int32_t* ids_out);
 int hipts_radius_dbscan(hipts_radius_t* h, int min_samples, int32_t* labels_out, int64_t* num_clusters, int32_t* sweeps_out);
 
 /* ------------------------------------------------------------------------------------------
+ * Near-duplicate images: a 128-bit gradient hash of the model-input tensor, and the all-pairs Hamming relation
+ * over such hashes as a hipts_radius_t.   Beyond the reference: "which FILES hold the same picture?" (a re-save at
+ * another size, a JPEG of a PNG, a second download).  Everything is integer arithmetic: every result is exact.
+ *
+ * hipts_image_hash_u8.  images: uint8 [batch][size][size][3] (host or device memory, the layout of *_forward_u8);
+ * hashes_out: uint64 [batch][2] (host or device memory).  size in [9, 1024], batch >= 1; anything else is
+ * HIPTS_ERR_INVALID.  All work is ordered on `stream`; the call synchronises only when hashes_out is host memory (keep
+ * pinned host images unchanged until the stream has passed this point).  The definition:
+ *   grey      per pixel, Pillow's convert("L"):  g = (19595 R + 38470 G + 7471 B + 0x8000) >> 16
+ *   grids     a grid of Rr rows x Cc columns has the boundaries floor(k * size / Rr) and floor(k * size / Cc);
+ *             sum(r, c) is the integer sum of g over a cell, area(r, c) its pixel count.  Cells have unequal areas
+ *             whenever 9 does not divide size (at 448 the column bounds are 0, 49, 99, 149, 199, 248, 298, 348, 398, 448)
+ *   brighter  cell b is brighter than cell a when  sum(b) * area(a) > sum(a) * area(b)  in 64-bit integers: the
+ *             means compared exactly, without a division or a float
+ *   word 0    horizontal, grid 8 x 9: bit 8 r + c (r, c in 0..7) is set when cell (r, c + 1) is brighter than cell (r, c)
+ *   word 1    vertical, grid 9 x 8: bit 8 r + c is set when cell (r + 1, c) is brighter than cell (r, c)
+ * The comparison is strict, so a flat region sets no bits.
+ *
+ * hipts_radius_create_hamming.  hashes: uint64 [rows][2] (host or device memory).  Relation:
+ *   j in N(i)  <=>  popcount(h_i[0] ^ h_j[0]) + popcount(h_i[1] ^ h_j[1]) <= max_distance
+ * for all pairs, j == i included; max_distance in [0, 128], 1 <= rows < 2^31 (an empty input is refused).  The result
+ * is an ordinary hipts_radius_t -- info, read, dbscan and destroy work on it unchanged -- built by the two passes of
+ * hipts_radius_create (degrees, then ids, rows sorted ascending: the same bytes run to run); max_pairs as there:
+ * exceeded after the first pass the call fails with HIPTS_ERR_INVALID and a message naming the count, 0 stands for half
+ * of the free device memory.  Synchronises `stream`.  The handle does not refer to `hashes` afterwards. */
+int hipts_image_hash_u8(const uint8_t* images, int images_memspace, int batch, int size, uint64_t* hashes_out, int out_memspace,
+                        int device, void* stream);
+int hipts_radius_create_hamming(const uint64_t* hashes, int hashes_memspace, int64_t rows, int max_distance, int64_t max_pairs,
+                                int device, void* stream, hipts_radius_t** out);
+
+/* ------------------------------------------------------------------------------------------
  * Normal-mode rerank, finishing stage for a batch.  Replaces the host list code of
  * webui.py:210-240 after the second ranking: division by the maximum, the top ten pinned at 1.0,
  * removal of their duplicates, the gap filter (webui.py:63-80) and the cut to topn.

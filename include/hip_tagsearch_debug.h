@@ -182,6 +182,10 @@ int hiptsdbg_topk_stamps(unsigned long long* host16);
 /* The last hipts_bm25_related call on this handle: the HIP-event time of its count launches (all passes) and how many work items
  * (workgroups) took the LDS histogram arm and the direct global-atomics arm (tools/related_bench.py).  Any pointer may be NULL. */
 int hiptsdbg_related_last(const hipts_bm25_t* h, double* count_ms, int64_t* lds_items, int64_t* direct_items);
+/* The create call that built this handle (hipts_radius_create or hipts_radius_create_hamming): the HIP-event times of its pass 1
+ * (the pair kernel counting degrees), of its pass 2 (the pair kernel filling the ids) and of the row sort (tools/dedup_bench.py).
+ * Any pointer may be NULL. */
+int hiptsdbg_radius_passes(const hipts_radius_t* h, double* pass1_ms, double* pass2_ms, double* sort_ms);
 
 #ifdef __cplusplus
 }
