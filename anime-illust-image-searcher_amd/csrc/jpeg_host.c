@@ -14,7 +14,10 @@
  * range of real data the two differ.  Per block and coefficient column the sum of |coefficient x quantiser| is held to COLSUM_LIMIT:
  * below it no 16-bit lane of either pass can wrap or saturate (pass 1 scales a column by at most 4 sqrt 8 / 2 = 5.66, pass 2 adds two such
  * values), so 16-bit and 32-bit arithmetic agree; an 8 x 8 block of 8-bit samples cannot exceed sqrt 8 x 1024 = 2896 (Parseval).  A block
- * above the limit sends the file to Pillow. */
+ * above the limit sends the file to Pillow.
+ *
+ * The other direction, hipts_jpeg_entropy_encode (further down), is the host half of the hybrid ENCODE: coefficient blocks -> the
+ * baseline file libjpeg writes for them. */
 #include <emmintrin.h> /* SSE2: part of the x86-64 baseline */
 #include <string.h>
 
@@ -644,6 +647,238 @@ int hipts_jpeg_entropy_decode(const uint8_t* data, int64_t n, void* slot, int64_
         }
         pos += len;
     }
+}
+
+/* ---- the host half of the hybrid JPEG ENCODE: a slot of quantised coefficient blocks (written by csrc/jpegenc.hip, or by the decoder
+ * above) -> the baseline file libjpeg writes for them with its defaults, which is what PIL.Image.save(..., "JPEG", quality=Q) produces:
+ * SOI, APP0 (JFIF 1.1, no density, no thumbnail), DQT 0, DQT 1, SOF0 (4:2:0), the four Annex K Huffman tables, one interleaved scan, EOI
+ * (jcmarker.c write_file_header / write_frame_header / write_scan_header; jchuff.c encode_one_block).  4:2:0 with three components only. */
+
+/* T.81 Annex K.3: the typical Huffman tables (jstdhuff.c) */
+static const uint8_t STD_DC_LUMA_BITS[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+static const uint8_t STD_DC_CHROMA_BITS[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+static const uint8_t STD_DC_VALS[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+static const uint8_t STD_AC_LUMA_BITS[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
+static const uint8_t STD_AC_LUMA_VALS[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+    0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+    0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+    0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+    0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+    0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+    0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+    0xfa};
+static const uint8_t STD_AC_CHROMA_BITS[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+static const uint8_t STD_AC_CHROMA_VALS[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+    0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+    0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+    0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+    0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+    0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+    0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+    0xfa};
+
+typedef struct {
+    uint16_t code[256];
+    uint8_t size[256]; /* 0: the table has no code for the symbol */
+} EncHuff;
+
+/* T.81 Annex C again, symbol -> code */
+static void enc_build(EncHuff* e, const uint8_t* counts, const uint8_t* symbols) {
+    int code = 0, p = 0;
+    memset(e, 0, sizeof(*e));
+    for (int l = 1; l <= 16; ++l) {
+        for (int i = 0; i < counts[l - 1]; ++i, ++p, ++code) {
+            e->code[symbols[p]] = (uint16_t)code;
+            e->size[symbols[p]] = (uint8_t)l;
+        }
+        code <<= 1;
+    }
+}
+
+/* the output: nothing is ever stored at or past `end`; `overflow` remembers that something did not fit */
+typedef struct {
+    uint8_t* p;
+    uint8_t* end;
+    uint64_t acc; /* the low `nbits` bits are pending, oldest highest */
+    int nbits;
+    int overflow;
+} BitWriter;
+
+static inline void put_byte(BitWriter* w, unsigned b) {
+    if (w->p < w->end) *w->p++ = (uint8_t)b;
+    else w->overflow = 1;
+}
+
+static void put_bytes(BitWriter* w, const uint8_t* src, int n) {
+    for (int i = 0; i < n; ++i) put_byte(w, src[i]);
+}
+
+static inline void put_be16(BitWriter* w, unsigned v) {
+    put_byte(w, v >> 8);
+    put_byte(w, v & 255u);
+}
+
+/* n <= 27 bits (a code of up to 16 and up to 11 magnitude bits).  Whole groups of four bytes leave at once when none of them is 0xFF
+ * (the common case); otherwise byte by byte with the stuffed zero (T.81 F.1.2.3) */
+static inline void put_bits(BitWriter* w, uint32_t bits, int n) {
+    w->acc = (w->acc << n) | bits;
+    w->nbits += n;
+    if (w->nbits < 32) return;
+    const uint32_t v = (uint32_t)(w->acc >> (w->nbits - 32));
+    w->nbits -= 32;
+    const uint32_t x = ~v;
+    if (!((x - 0x01010101u) & ~x & 0x80808080u) && w->end - w->p >= 4) {
+        const uint32_t be = __builtin_bswap32(v);
+        memcpy(w->p, &be, 4);
+        w->p += 4;
+        return;
+    }
+    for (int s = 24; s >= 0; s -= 8) {
+        const unsigned b = (v >> s) & 255u;
+        put_byte(w, b);
+        if (b == 0xFF) put_byte(w, 0);
+    }
+}
+
+/* the pending bits, padded with ones to a whole byte (jchuff.c flush_bits) */
+static void flush_bits(BitWriter* w) {
+    if (w->nbits & 7) {
+        const int pad = 8 - (w->nbits & 7);
+        w->acc = (w->acc << pad) | ((1u << pad) - 1u);
+        w->nbits += pad;
+    }
+    while (w->nbits > 0) {
+        const unsigned b = (unsigned)(w->acc >> (w->nbits - 8)) & 255u;
+        w->nbits -= 8;
+        put_byte(w, b);
+        if (b == 0xFF) put_byte(w, 0);
+    }
+}
+
+static inline int bit_length(unsigned v) { return v ? 32 - __builtin_clz(v) : 0; }
+
+static void put_dht(BitWriter* w, int tc_th, const uint8_t* counts, const uint8_t* symbols) {
+    int nsym = 0;
+    for (int i = 0; i < 16; ++i) nsym += counts[i];
+    put_be16(w, 0xFFC4);
+    put_be16(w, (unsigned)(2 + 1 + 16 + nsym));
+    put_byte(w, (unsigned)tc_th);
+    put_bytes(w, counts, 16);
+    put_bytes(w, symbols, nsym);
+}
+
+/* one block (jchuff.c encode_one_block); returns 0 if a value has no code */
+static inline int encode_block(BitWriter* w, const int16_t* blk, int* pred, const EncHuff* hdc, const EncHuff* hac) {
+    {
+        if (blk[0] < -2047 || blk[0] > 2047) return 0;
+        const int diff = blk[0] - *pred;
+        *pred = blk[0];
+        const int nb = bit_length((unsigned)(diff < 0 ? -diff : diff));
+        if (nb > 11) return 0;
+        const uint32_t mag = (uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << nb) - 1u);
+        put_bits(w, ((uint32_t)hdc->code[nb] << nb) | mag, hdc->size[nb] + nb);
+    }
+    int run = 0;
+    for (int k = 1; k < 64; ++k) {
+        const int v = blk[ZIGZAG[k]];
+        if (v == 0) {
+            ++run;
+            continue;
+        }
+        while (run > 15) {
+            put_bits(w, hac->code[0xF0], hac->size[0xF0]);
+            run -= 16;
+        }
+        const int nb = bit_length((unsigned)(v < 0 ? -v : v));
+        if (nb > 10) return 0;
+        const int sym = (run << 4) | nb;
+        const uint32_t mag = (uint32_t)(v < 0 ? v - 1 : v) & ((1u << nb) - 1u);
+        put_bits(w, ((uint32_t)hac->code[sym] << nb) | mag, hac->size[sym] + nb);
+        run = 0;
+    }
+    if (run > 0) put_bits(w, hac->code[0], hac->size[0]);
+    return 1;
+}
+
+/* Slot -> file.  0: *nbytes bytes of file_out hold the file.  JH_UNSUPPORTED: not a 4:2:0 three-component slot, or tables a baseline
+ * file with these markers cannot carry.  JH_CORRUPT: the header contradicts itself or slot_bytes, or a coefficient has no code (beyond 11
+ * bits of DC difference / 10 bits of AC magnitude: no 8-bit image produces one).  JH_TOO_SMALL: the file does not fit in `capacity`
+ * bytes.  Whatever the status, nothing is stored at or beyond file_out + capacity; on an error *nbytes is 0. */
+int hipts_jpeg_entropy_encode(const void* slot, int64_t slot_bytes, uint8_t* file_out, int64_t capacity, int64_t* nbytes) {
+    if (nbytes) *nbytes = 0;
+    if (!slot || !file_out || !nbytes || capacity < 0 || slot_bytes < HIPTS_JPEG_HEADER_BYTES) return JH_TOO_SMALL;
+    hipts_jpeg_header hd;
+    memcpy(&hd, slot, sizeof(hd));
+    if (hd.magic != HIPTS_JPEG_MAGIC || hd.kind != 1) return JH_CORRUPT;
+    if (hd.ncomp != 3 || hd.hmax != 2 || hd.vmax != 2) return JH_UNSUPPORTED;
+    if (hd.comp[0].h != 2 || hd.comp[0].v != 2 || hd.comp[1].h != 1 || hd.comp[1].v != 1 || hd.comp[2].h != 1 || hd.comp[2].v != 1)
+        return JH_UNSUPPORTED;
+    if (hd.width < 1 || hd.height < 1 || hd.width > 65535 || hd.height > 65535) return JH_CORRUPT;
+    if (hd.total_bytes < HIPTS_JPEG_HEADER_BYTES || hd.total_bytes > slot_bytes) return JH_CORRUPT;
+    const int mcux = (hd.width + 15) / 16, mcuy = (hd.height + 15) / 16;
+    const int64_t ncoef = (slot_bytes - HIPTS_JPEG_HEADER_BYTES) / 2;
+    for (int c = 0; c < 3; ++c) {
+        const hipts_jpeg_component* k = &hd.comp[c];
+        if (k->blocks_w != mcux * k->h || k->blocks_h != mcuy * k->v) return JH_CORRUPT;
+        if (k->offset < 0 || (int64_t)k->offset + (int64_t)k->blocks_w * k->blocks_h * 64 > ncoef) return JH_CORRUPT;
+        for (int i = 0; i < 64; ++i)
+            if (hd.quant[c][i] < 1 || hd.quant[c][i] > 255) return JH_UNSUPPORTED; /* 8-bit DQT entries */
+    }
+    if (memcmp(hd.quant[1], hd.quant[2], sizeof(hd.quant[1])) != 0) return JH_UNSUPPORTED; /* Cb and Cr share table 1 */
+
+    BitWriter w = {file_out, file_out + capacity, 0, 0, 0};
+    static const uint8_t APP0[18] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    put_be16(&w, 0xFFD8);
+    put_bytes(&w, APP0, 18);
+    for (int t = 0; t < 2; ++t) {
+        put_be16(&w, 0xFFDB);
+        put_be16(&w, 67);
+        put_byte(&w, (unsigned)t);
+        for (int i = 0; i < 64; ++i) put_byte(&w, hd.quant[t][ZIGZAG[i]]);
+    }
+    put_be16(&w, 0xFFC0);
+    put_be16(&w, 17);
+    put_byte(&w, 8);
+    put_be16(&w, (unsigned)hd.height);
+    put_be16(&w, (unsigned)hd.width);
+    put_byte(&w, 3);
+    static const uint8_t FRAME[9] = {1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1};
+    put_bytes(&w, FRAME, 9);
+    put_dht(&w, 0x00, STD_DC_LUMA_BITS, STD_DC_VALS);
+    put_dht(&w, 0x10, STD_AC_LUMA_BITS, STD_AC_LUMA_VALS);
+    put_dht(&w, 0x01, STD_DC_CHROMA_BITS, STD_DC_VALS);
+    put_dht(&w, 0x11, STD_AC_CHROMA_BITS, STD_AC_CHROMA_VALS);
+    static const uint8_t SCAN[14] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
+    put_bytes(&w, SCAN, 14);
+    if (w.overflow) return JH_TOO_SMALL;
+
+    EncHuff dc[2], ac[2];
+    enc_build(&dc[0], STD_DC_LUMA_BITS, STD_DC_VALS);
+    enc_build(&dc[1], STD_DC_CHROMA_BITS, STD_DC_VALS);
+    enc_build(&ac[0], STD_AC_LUMA_BITS, STD_AC_LUMA_VALS);
+    enc_build(&ac[1], STD_AC_CHROMA_BITS, STD_AC_CHROMA_VALS);
+    const char* coef = (const char*)slot + HIPTS_JPEG_HEADER_BYTES;
+    int pred[3] = {0, 0, 0};
+    for (int my = 0; my < mcuy; ++my) {
+        for (int mx = 0; mx < mcux; ++mx)
+            for (int c = 0; c < 3; ++c) {
+                const hipts_jpeg_component* k = &hd.comp[c];
+                for (int v = 0; v < k->v; ++v)
+                    for (int h = 0; h < k->h; ++h) {
+                        int16_t blk[64]; /* (the slot need not be aligned for int16) */
+                        memcpy(blk, coef + 2 * (k->offset + ((int64_t)(my * k->v + v) * k->blocks_w + (mx * k->h + h)) * 64), sizeof(blk));
+                        if (!encode_block(&w, blk, &pred[c], &dc[c > 0], &ac[c > 0])) return JH_CORRUPT;
+                    }
+            }
+        if (w.overflow) return JH_TOO_SMALL; /* (checked per MCU row: a file that cannot fit is not coded to its end) */
+    }
+    flush_bits(&w);
+    put_be16(&w, 0xFFD9);
+    if (w.overflow) return JH_TOO_SMALL;
+    *nbytes = w.p - file_out;
+    return JH_OK;
 }
 
 /* Size of the slot a width x height image needs at most (4:4:4: three full planes of int16, padded to whole MCUs of 16 x 16). */

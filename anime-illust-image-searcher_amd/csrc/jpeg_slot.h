@@ -10,6 +10,9 @@
 // A slot is a ring-buffer slot of hiptagsearch/pipeline.py: this header, then int16 coefficient blocks.  What the reference does at this
 // point is PIL's Image.open(...).load() (tagging.py:234-252, gen_cfeatures.py:285-295): the device half reproduces libjpeg-turbo's output
 // byte for byte (tests/test_gpu_jpeg.py compares with Pillow).
+//
+// The hybrid ENCODE (thumbnails and contact sheets) goes the other way through the same slot: jpegenc.hip writes it, header included, for
+// a 4:2:0 image, and jpeg_host.c's hipts_jpeg_entropy_encode turns it into the file libjpeg would write.
 #pragma once
 #include <stdint.h>
 

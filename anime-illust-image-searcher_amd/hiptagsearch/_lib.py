@@ -129,6 +129,8 @@ _SIGNATURES = {
     "hipts_jpeg_batch_u8": [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
     "hipts_png_decode_rgb": [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_void_p],
     "hipts_decode_batch_u8": [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
+    "hipts_jpeg_encode_batch_u8": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int64, c_int, c_void_p],
+    "hipts_jpeg_entropy_encode": [c_void_p, c_int64, c_void_p, c_int64, POINTER(c_int64)],
     "hipts_ccip_metric": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p],
     "hipts_comm_unique_id": [c_void_p, c_size_t],
     "hipts_comm_create": [c_void_p, c_size_t, c_int, c_int, c_int, POINTER(c_void_p)],

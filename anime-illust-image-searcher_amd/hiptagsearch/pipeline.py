@@ -101,6 +101,9 @@ def load_jpeg_host_lib():
     lib.hipts_jpeg_entropy_decode.restype = ctypes.c_int
     lib.hipts_jpeg_slot_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.hipts_jpeg_slot_bytes.restype = ctypes.c_int64
+    # the other direction (hiptagsearch/thumbs.py): coefficient slot -> file
+    lib.hipts_jpeg_entropy_encode.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    lib.hipts_jpeg_entropy_encode.restype = ctypes.c_int
     return lib
 
 

@@ -608,9 +608,13 @@ class Predictor:
 
     # ---- tagging.py:276-359
     def process_directory(self, dir_path: str, added_date: Optional[datetime.date] = None, batch_size: int = BATCH_SIZE,
-                          workers: int = 0, shards: Optional[str] = None) -> None:
+                          workers: int = 0, shards: Optional[str] = None, thumbnails=None) -> None:
         """workers > 0: decode in that many processes (pipeline.DecodePool) instead of the reference's 8 threads;
-        shards: tag the pre-decoded shards of pipeline.write_shards in that directory instead of walking dir_path."""
+        shards: tag the pre-decoded shards of pipeline.write_shards in that directory instead of walking dir_path;
+        thumbnails: a hiptagsearch.thumbs.ThumbnailWriter that gets every batch of model-input images before its forward is launched
+        (pipeline path only: workers > 0 or shards, not compat); closed here."""
+        if thumbnails is not None and not ((workers > 0 or shards) and not self.compat):
+            raise ValueError("thumbnails are written on the pipeline path only: workers > 0 or shards, and not compat")
         file_list = [] if shards else self.list_files_recursive(dir_path)
         print(f'{len(file_list)} files found')
         if added_date is not None:
@@ -666,6 +670,8 @@ class Predictor:
             step = 0
             try:
                 for kept, images in source:
+                    if thumbnails is not None:
+                        thumbnails.add(kept, images)
                     on_device = hasattr(images, "is_cuda") and images.is_cuda and len(images) <= self.max_batch
                     if on_device:
                         # the forward is only LAUNCHED here (outputs stay on the device): the next iteration launches the next one at once,
@@ -698,6 +704,8 @@ class Predictor:
                 sys.setswitchinterval(old_switch)
                 if pool is not None:
                     pool.close()
+                if thumbnails is not None:
+                    thumbnails.close()
             self.f.close()
             return
         batches = [file_list[i:i + batch_size] for i in range(0, len(file_list), batch_size)]

@@ -5,7 +5,10 @@ python query.py --batch-file queries.txt [--topn 50]           -- one query per 
 (find_similar_documents_batch); per query a "# query" header line, then the same lines.
 python query.py --related "1girl hat:-1" [--topn 20] [--measure count|jaccard|lift] [--min-count N]
 -- the tags that co-occur most with the documents that carry 1girl and not hat (SearchEngine.related_tags): score<TAB>count<TAB>tag lines.
-Needs only doc2vec_dictionary and the BM25 pickles."""
+Needs only doc2vec_dictionary and the BM25 pickles.
+python query.py QUERY --contact-sheet FILE --thumbnails DIR [--columns 8]
+-- also writes the ranked results as ONE JPEG, in result order, from the thumbnail cache DIR (make_thumbnails.py, tagging.py --thumbnails);
+a result without a thumbnail leaves its cell white."""
 import argparse
 import os
 import sys
@@ -23,7 +26,12 @@ def main(argv):
     ap.add_argument("--topn", type=int, default=None, help="default 50; 20 with --related")
     ap.add_argument("--compat-rerank", action="store_true")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--contact-sheet", metavar="FILE", help="write the results of the (single) query as one JPEG of thumbnails; needs --thumbnails")
+    ap.add_argument("--thumbnails", metavar="DIR", help="the thumbnail cache (the directory that holds thumbnails.csv)")
+    ap.add_argument("--columns", type=int, default=8, help="--contact-sheet: thumbnails per row (default 8)")
     a = ap.parse_args(argv)
+    if a.contact_sheet is not None and (a.thumbnails is None or a.query is None or a.related is not None or a.columns < 1):
+        ap.error("--contact-sheet needs a single query, --thumbnails DIR and --columns >= 1")
     if a.related is not None:
         if a.query is not None or a.batch_file is not None:
             ap.error("--related replaces the query and --batch-file")
@@ -46,6 +54,29 @@ def main(argv):
             print("# %s" % queries[i])
         for doc_id, score in res:
             print("%.6f\t%s" % (score, eng.image_files_name_tags_arr[doc_id].split(",")[0]))
+    if a.contact_sheet is not None:
+        write_contact_sheet([eng.image_files_name_tags_arr[doc_id].split(",")[0] for doc_id, _ in results[0]], a.thumbnails, a.contact_sheet,
+                            a.columns, a.device)
+
+
+def write_contact_sheet(paths, thumb_dir, out_file, columns=8, device=0):
+    """the thumbnails of `paths`, in order, as one JPEG of quality 85; the cell size is the cache's (read from the first thumbnail found)"""
+    import io
+    from PIL import Image
+    from hiptagsearch import thumbs
+    index = thumbs.read_index(thumb_dir)
+    found = [index.get(p) for p in paths]
+    size, quality = 256, 85
+    for f in found:
+        if f and os.path.exists(f):
+            with open(f, "rb") as fh:
+                im = Image.open(io.BytesIO(fh.read()))
+            size = im.size[0]
+            break
+    data = thumbs.contact_sheet(found, columns, size, quality, device)
+    with open(out_file, "wb") as f:
+        f.write(data)
+    print("%d of %d results have a thumbnail -> %s" % (sum(1 for f in found if f and os.path.exists(f)), len(found), out_file))
 
 
 def related(a):

@@ -7,6 +7,8 @@ selected_tags.csv for a real wd tagger; without them the seeded synthetic stand-
 throughput for the 1e-3 logit tolerance on flat / padded pictures (operand_f16 bit 4).
 Input pipeline (hiptagsearch/pipeline.py): --workers N decodes in N processes through shared memory; --write-shards DIR
 decodes the corpus once into packed uint8 shards and --shards DIR tags from them (utility/make_tensor_files.py's idea).
+--thumbnails DIR (with --workers N or --shards, single process): a JPEG thumbnail of every tagged image in the same pass, made from the
+model input and encoded on the device (hiptagsearch/thumbs.py); the tag file is the same with and without.
 
 Multi-GPU (one process per GPU, RCCL all-gather of fixed-width tag rows restores file order):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 tagging.py --dir D
@@ -51,7 +53,21 @@ def main(arg_str: list) -> None:
                         help='attention output handed to the output projection as a hi | lo pair of 16-bit halves (operand_f16 |= 16): logits of '
                              'flat / padded pictures within 1e-3 of the fp32 reference at a trained checkpoint\'s scale, about 5 %% fewer images/s')
     parser.add_argument('--device', type=int, default=0)
+    parser.add_argument('--thumbnails', default=None, metavar='DIR',
+                        help='with --workers N or --shards: also write a JPEG thumbnail of every tagged image (made from the model input, '
+                             'encoded on the device) into DIR, listed in DIR/thumbnails.csv')
+    parser.add_argument('--thumb-size', type=int, default=256, help='thumbnail edge: a multiple of 16 in 64..512 (default 256)')
+    parser.add_argument('--thumb-quality', type=int, default=85, help='JPEG quality of the thumbnails, 1..100 (default 85)')
     args = parser.parse_args(arg_str)
+    if args.thumbnails:
+        if args.compat or args.synthetic or int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            parser.error('--thumbnails works on the single-process pipeline path: not with --compat, --synthetic or under torch.distributed.run')
+        if not (args.workers > 0 or args.shards) or args.write_shards:
+            parser.error('--thumbnails needs the pipeline path: --workers N or --shards')
+        if args.thumb_size % 16 != 0 or not 64 <= args.thumb_size <= 512:
+            parser.error('--thumb-size must be a multiple of 16 in 64..512')
+        if not 1 <= args.thumb_quality <= 100:
+            parser.error('--thumb-quality must be in 1..100')
     if args.precise and args.model.startswith('convnext'):
         parser.error('--precise is an attention-output option (ViT, EVA02): the ConvNeXt tagger has no attention')
     if args.precise and args.model.startswith('swinv2'):
@@ -90,7 +106,12 @@ def main(arg_str: list) -> None:
                                             workers=args.workers, shards=args.shards, synthetic=args.synthetic)
         hdist.finish(dist)
         return
-    predictor.process_directory(args.dir[0], after_date, batch_size=10 if args.compat else args.batch, workers=args.workers, shards=args.shards)
+    thumbnails = None
+    if args.thumbnails:
+        from hiptagsearch.thumbs import ThumbnailWriter
+        thumbnails = ThumbnailWriter(args.thumbnails, args.thumb_size, args.thumb_quality, device)
+    predictor.process_directory(args.dir[0], after_date, batch_size=10 if args.compat else args.batch, workers=args.workers, shards=args.shards,
+                                thumbnails=thumbnails)
 
 
 if __name__ == "__main__":

@@ -351,6 +351,28 @@ int hipts_png_decode_rgb(const void* slot, int64_t slot_bytes, uint8_t* rgb_out,
 int hipts_decode_batch_u8(const uint8_t* slots, int64_t slot_stride, const int32_t* kinds, const int32_t* hw, int n, int pad_square,
                           uint8_t* dst_device, int size, int filter, int device, void* stream);
 
+/* ---- Hybrid JPEG encode: the decode's mirror image, for thumbnails and contact sheets (hiptagsearch/thumbs.py).  Goes past the
+ * reference, which shows a result by opening every full-size original per page view (webui.py display_images).  The bar is the file
+ * PIL.Image.save(..., "JPEG", quality=Q) writes -- libjpeg-turbo with its defaults: 4:2:0, baseline tables, the standard Huffman tables --
+ * byte for byte.  The per-pixel / per-block half (jccolor.c's RGB -> YCbCr, h2v2_downsample, jfdctint.c's accurate integer forward DCT,
+ * quantisation, libjpeg's edge replication and filler blocks) runs on the device; the serial half (Huffman coding) on the host.
+ *
+ * hipts_jpeg_encode_batch_u8: images uint8 [n][height][width][3] RGB (host or device memory) -> n slots (hipts_jpeg_header of
+ * csrc/jpeg_slot.h with quant[] filled in + int16 blocks, planar per component, natural order, planes padded to whole MCUs: what
+ * hipts_jpeg_entropy_decode writes for a 4:2:0 file, and what hipts_jpeg_decode_rgb reads), slot i at slots_out + i * slot_stride in host
+ * or device memory; slot_stride >= hipts_jpeg_slot_bytes(width, height).  Device slots that are 16-byte aligned (slots_out and
+ * slot_stride) are written in place, any others through a staging buffer and one copy per slot.  The bytes of a stride beyond a slot's
+ * total_bytes are left alone.  16 <= height, width <= 8192; 1 <= quality <= 100; 1 <= n <= 65535.  Ordered on `stream`, not
+ * synchronised: host memory on either side must stay put until the stream has passed this point. */
+int hipts_jpeg_encode_batch_u8(const uint8_t* images, int images_memspace, int n, int height, int width, int quality, uint8_t* slots_out,
+                               int out_memspace, int64_t slot_stride, int device, void* stream);
+
+/* HOST ONLY (also exported by libhipts_jpeg_host.so): a 4:2:0 three-component slot -> the file.  SOI, APP0 (JFIF 1.1, density units 0,
+ * 1:1, no thumbnail), DQT 0, DQT 1, SOF0, the four Annex K tables (DC0, AC0, DC1, AC1), one interleaved scan, EOI; no restart markers.
+ * Returns 0 and the file's length in *nbytes; 1: not such a slot; 2: the file does not fit in `capacity` bytes; 3: the header contradicts
+ * itself or slot_bytes, or a coefficient lies outside the 11-bit category range.  Never writes at or beyond file_out + capacity. */
+int hipts_jpeg_entropy_encode(const void* slot, int64_t slot_bytes, uint8_t* file_out, int64_t capacity, int64_t* nbytes);
+
 /* The synthetic image corpus of the benchmark configurations (BASELINE.json configs[3]: "1M synthetic images sharded
  * 8xMI355X"), generated on the device with no host I/O: images first_index .. first_index + count - 1 of the corpus `seed`, uint8
  * [count][image_size][image_size][3], every byte a counter-hash of (seed, GLOBAL image index, byte offset) -- so a rank produces its own
