@@ -711,4 +711,24 @@ int hiptsdbg_dwconv7_stamps(unsigned long long* host, int n) {
     return HIPTS_OK;
 }
 
+// Debug / test entry: stem_im2col_u8_kernel once, launched as the forward launches it, into an a0 of a0_bytes filled with `fill` and copied
+// back whole (tests/test_gpu_rows.py compares it with the generic gather of csrc/rows_dbg.hip).
+int hiptsdbg_ccip_stem_u8(const uint8_t* images, const float* lut, int batch, int S, int f16, int fill, uint16_t* a0, uint64_t a0_bytes) {
+    HIPTS_REQUIRE(images && lut && a0 && batch >= 1 && batch <= 64 && S >= 4 && S <= 1024 && S % 4 == 0, "hiptsdbg_ccip_stem_u8: bad argument");
+    const int H0 = S / 4, xtiles = ceil_div(H0, 64);
+    HIPTS_REQUIRE(a0_bytes >= (uint64_t)batch * H0 * H0 * STEM_K * 2, "hiptsdbg_ccip_stem_u8: a0 has %llu bytes, the launch's extent is %llu",
+                  (unsigned long long)a0_bytes, (unsigned long long)batch * H0 * H0 * STEM_K * 2);
+    HIPTS_TRY(use_device(0));
+    DevBuf img, lutd, ad;
+    HIPTS_TRY(img.alloc((size_t)batch * S * S * 3));
+    HIPTS_TRY(upload(img.p, images, (size_t)batch * S * S * 3));
+    HIPTS_TRY(upload_f32(lutd, lut, 3 * 256));
+    HIPTS_TRY(ad.alloc(a0_bytes));
+    HIPTS_HIP(hipMemset(ad.p, fill & 0xff, a0_bytes));
+    HIPTS_LAUNCH_F16(f16 != 0, stem_im2col_u8_kernel, batch * H0 * xtiles, 256, 0, nullptr, img.as<uint8_t>(), lutd.as<float>(), ad.as<bf16_t>(), S, H0, xtiles);
+    HIPTS_HIP(hipDeviceSynchronize());
+    HIPTS_HIP(hipMemcpy(a0, ad.p, a0_bytes, hipMemcpyDeviceToHost));
+    return HIPTS_OK;
+}
+
 }  // extern "C"

@@ -1314,6 +1314,26 @@ extern "C" int hiptsdbg_attention2_kernel_resources(int tokens_pad, int f16, int
 
 extern "C" int hiptsdbg_attention2_stamps(unsigned long long* host, int n) { return attention2_read_stamps(host, n); }
 
+// patchify_u8_p16_kernel once, launched as the forward launches it, into an a0 of a0_bytes filled with `fill` and copied back whole
+// (tests/test_gpu_rows.py compares it with patchify_u8_kernel at P = 16 through csrc/rows_dbg.hip).
+extern "C" int hiptsdbg_vit_patchify_u8_p16(const uint8_t* images, int batch, int grid, int f16, int fill, uint16_t* a0, uint64_t a0_bytes) {
+    HIPTS_REQUIRE(images && a0 && batch >= 1 && batch <= 64 && grid >= 1 && grid <= 64, "hiptsdbg_vit_patchify_u8_p16: bad argument");
+    const int S = 16 * grid, xgroups = (grid + 15) / 16;
+    const uint64_t need = (uint64_t)batch * grid * grid * 768 * 2;
+    HIPTS_REQUIRE(a0_bytes >= need, "hiptsdbg_vit_patchify_u8_p16: a0 has %llu bytes, the launch's extent is %llu", (unsigned long long)a0_bytes,
+                  (unsigned long long)need);
+    HIPTS_TRY(use_device(0));
+    DevBuf img, ad;
+    HIPTS_TRY(img.alloc((size_t)batch * S * S * 3));
+    HIPTS_TRY(upload(img.p, images, (size_t)batch * S * S * 3));
+    HIPTS_TRY(ad.alloc(a0_bytes));
+    HIPTS_HIP(hipMemset(ad.p, fill & 0xff, a0_bytes));
+    HIPTS_LAUNCH_F16(f16 != 0, patchify_u8_p16_kernel, batch * grid * xgroups, 256, 0, nullptr, img.as<uint8_t>(), ad.as<bf16_t>(), S, grid, xgroups);
+    HIPTS_HIP(hipDeviceSynchronize());
+    HIPTS_HIP(hipMemcpy(a0, ad.p, a0_bytes, hipMemcpyDeviceToHost));
+    return HIPTS_OK;
+}
+
 // Development aid: copy one workspace buffer of the last forward to the host (tools/determinism.py).
 extern "C" int hiptsdbg_vit_dump(hipts_vit_t* h, const char* name, void* out_host, size_t max_bytes, size_t* bytes) {
     HIPTS_REQUIRE(h && name && out_host && bytes, "null argument");

@@ -131,6 +131,68 @@ typedef struct hiptsdbg_gemm_out_t {
     uint64_t x_bytes, rowmajor_bytes, probs_bytes, out16_bytes[3], stat_part_bytes;
 } hiptsdbg_gemm_out_t;
 int hiptsdbg_gemm_epilogue(const hiptsdbg_gemm_case_t* in, hiptsdbg_gemm_out_t* out);
+/* The row kernels of csrc/row_ln.h and csrc/patch_rows.h, ONE launch each on caller-supplied operands (csrc/rows_dbg.hip;
+ * tests/test_gpu_rows.py), modelled on hiptsdbg_gemm_epilogue: the caller sizes every output buffer, the entry refuses one smaller than
+ * the launch's extent, fills each whole device buffer with the byte `fill`, launches once and copies every buffer back whole.  A buffer
+ * the launch does not use may still be given: it comes back holding `fill`.
+ *
+ * hiptsdbg_row_ln: row_ln_kernel<f16, source, affine, sink>(rows, D, eps).  Only the tuples a forward launches are built; any other is
+ * refused (HIPTS_ERR_INVALID), as are D % 4 != 0, D outside [4, 1024], a blocked layout with rows % 16 != 0 or D % 16 != 0, and
+ * SINK_PATCH2X2 with an odd H or rows % (H * H) != 0.
+ *   (SRC_F32, AFF_GAMMA_OPT_BETA, SINK_16)                vit.hip, launch_layernorm (b may be null)
+ *   (SRC_F32_BLOCKED, AFF_GAMMA_ADD_ZERO, SINK_16)        ccip.hip
+ *   (SRC_F32_INPLACE, AFF_GAMMA_PLAIN, SINK_BACK)         ccip.hip; blk = 0 / 1
+ *   (SRC_F32, AFF_GAMMA_BETA, SINK_F32_AND_16)            convnext.hip, swinv2.hip: in place
+ *   (SRC_F32, AFF_GAMMA_BETA, SINK_PATCH2X2)              convnext.hip
+ *   (SRC_16_BIAS, AFF_GAMMA_BETA, SINK_16)                convnext.hip
+ *   (SRC_F32, AFF_GAMMA_BETA, SINK_ADD_HILO)              swinv2.hip
+ *   (SRC_F32, AFF_GAMMA_BETA, SINK_F32)                   swinv2.hip
+ * in: the source rows [rows][D], float32 (the blocked layout [m / 16][n / 16][m % 16][n % 16] for SRC_F32_BLOCKED) or 16-bit patterns
+ * (SRC_16_BIAS, with bias [D]); null for the in-place tuples (SRC_F32_INPLACE, SINK_F32_AND_16), whose rows are x_init.  g, b: [D].
+ * out->f32: the float32 buffer the sink writes (SINK_F32: y; SINK_F32_AND_16, SINK_BACK, SINK_ADD_HILO: the stream x); x_init
+ * (x_init_bytes <= f32_bytes) is copied over its start after the fill.  out->o16: the 16-bit buffer (SINK_16: [rows][D]; SINK_F32_AND_16:
+ * the copy; SINK_PATCH2X2: [rows / 4][4 D]; SINK_ADD_HILO: [rows][hi(D) | lo(D)]). */
+enum { HIPTSDBG_SRC_F32 = 0, HIPTSDBG_SRC_F32_BLOCKED = 1, HIPTSDBG_SRC_F32_INPLACE = 2, HIPTSDBG_SRC_16_BIAS = 3 };
+enum { HIPTSDBG_AFF_GAMMA_BETA = 0, HIPTSDBG_AFF_GAMMA_OPT_BETA = 1, HIPTSDBG_AFF_GAMMA_ADD_ZERO = 2, HIPTSDBG_AFF_GAMMA_PLAIN = 3 };
+enum { HIPTSDBG_SINK_16 = 0, HIPTSDBG_SINK_E4M3 = 1, HIPTSDBG_SINK_F32 = 2, HIPTSDBG_SINK_F32_AND_16 = 3, HIPTSDBG_SINK_PATCH2X2 = 4,
+       HIPTSDBG_SINK_ADD_HILO = 5, HIPTSDBG_SINK_BACK = 6 };
+typedef struct hiptsdbg_row_ln_case_t {
+    int32_t src, affine, sink, f16, blk, H, D, fill;
+    int64_t rows;
+    float eps;
+    const void* in;
+    uint64_t in_bytes;
+    const float* bias;
+    const float* g;
+    const float* b;
+    const float* x_init;
+    uint64_t x_init_bytes;
+} hiptsdbg_row_ln_case_t;
+typedef struct hiptsdbg_rows_out_t {
+    void* f32;
+    void* o16;
+    uint64_t f32_bytes, o16_bytes;
+} hiptsdbg_rows_out_t;
+int hiptsdbg_row_ln(const hiptsdbg_row_ln_case_t* in, hiptsdbg_rows_out_t* out);
+/* pool_ln_kernel once: out[b] = LN((sum over the T rows of x[b]) / count) for x float32 [batch][T][C] (blk != 0: each image's rows in the
+ * blocked layout; T % 16 == 0 and C % 16 == 0 then), g, b [C]; 1 <= C <= 1024.  hilo == 0: the PooledF32 sink, out float32 [batch][C];
+ * otherwise PooledHiLo, out 16-bit patterns [batch][hi(C) | lo(C)].  out_bytes >= 4 batch C either way. */
+int hiptsdbg_pool_ln(const float* x, uint64_t x_bytes, const float* g, const float* b, int batch, int T, int C, int count, int blk, float eps,
+                     int hilo, int f16, int fill, void* out, uint64_t out_bytes);
+/* patch_gather_kernel once with a (pixel, window) tuple a forward launches -- (PIX_U8_AFFINE, WIN_PATCH), (PIX_U8_TABLE, WIN_4X4),
+ * (PIX_F32_FLIP, WIN_PATCH), (PIX_F32_FLIP, WIN_4X4), (PIX_F32, WIN_7X7) -- or, with PIX_U8_RAW and WIN_PATCH, patchify_u8_kernel.
+ * images: uint8 [batch][S][S][3] or float32 [batch][3][S][S]; lut: float32 [3][256] (PIX_U8_TABLE).  WIN_PATCH: P x P patches, S % P == 0,
+ * rows of 2 KH (KH >= 3 P P; PIX_U8_RAW: rows of 3 P P, KH unused); the others: S % 4 == 0, S / 4 tokens a side, rows of 128 / 320.
+ * a0: 16-bit patterns, a0_bytes >= the rows of the launch. */
+enum { HIPTSDBG_PIX_U8_AFFINE = 0, HIPTSDBG_PIX_U8_TABLE = 1, HIPTSDBG_PIX_F32_FLIP = 2, HIPTSDBG_PIX_F32 = 3, HIPTSDBG_PIX_U8_RAW = 4 };
+enum { HIPTSDBG_WIN_PATCH = 0, HIPTSDBG_WIN_4X4 = 1, HIPTSDBG_WIN_7X7 = 2 };
+int hiptsdbg_patch_gather(int pixel, int window, int f16, const void* images, uint64_t image_bytes, const float* lut, int batch, int S, int P,
+                          int KH, int fill, uint16_t* a0, uint64_t a0_bytes);
+/* The two LDS-tiled uint8 stems, file-local to their forwards, once each into a guarded a0 as above: stem_im2col_u8_kernel (csrc/ccip.hip;
+ * images [batch][S][S][3], S % 4 == 0, lut [3][256]; rows of 320) and patchify_u8_p16_kernel (csrc/vit.hip; images of side 16 grid; rows
+ * of 768). */
+int hiptsdbg_ccip_stem_u8(const uint8_t* images, const float* lut, int batch, int S, int f16, int fill, uint16_t* a0, uint64_t a0_bytes);
+int hiptsdbg_vit_patchify_u8_p16(const uint8_t* images, int batch, int grid, int f16, int fill, uint16_t* a0, uint64_t a0_bytes);
 /* out_host float32 [M][N] = A W^T for bf16 bit patterns a_bf16 [M][K], w_bf16 [N][K] (plain epilogue). */
 int hiptsdbg_gemm_run(int M, int N, int K, const uint16_t* a_bf16, const uint16_t* w_bf16, float* out_host);
 /* The e4m3 operand path: a_f32 / w_f32 are quantised by the library (per-tensor power-of-two weight scale returned in
