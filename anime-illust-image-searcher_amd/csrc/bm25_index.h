@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "common.h"
+#include "prof.h"
 #include "../../include/hip_tagsearch_debug.h"
 
 using hipts::DevBuf;
@@ -51,9 +52,5 @@ struct hipts_bm25 {
     int64_t rel_items[2] = {0, 0};             // work items of the last call: LDS histogram arm, direct arm
     // per-kernel HIP-event timing (hipts_query_profile_*): events on the stream each kernel is launched on
     bool prof = false;
-    struct ProfRec { int cat; hipEvent_t a, b; double bytes; };
-    std::vector<ProfRec> prof_recs;
-    std::vector<hipEvent_t> prof_pool;
-    double prof_ms[HIPTS_QUERY_PROF_CATEGORIES] = {0}, prof_bytes[HIPTS_QUERY_PROF_CATEGORIES] = {0};
-    int64_t prof_n[HIPTS_QUERY_PROF_CATEGORIES] = {0};
+    hipts::EventProfile<HIPTS_QUERY_PROF_CATEGORIES> ep;
 };

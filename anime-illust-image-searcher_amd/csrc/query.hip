@@ -22,6 +22,7 @@
 
 #include "bm25_index.h"
 #include "common.h"
+#include "query_plan.h"
 #include "rank_util.h"
 #include "topk.h"
 #include "../../include/hip_tagsearch_debug.h"
@@ -353,7 +354,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // the 32 lanes of a half-wave read 512 contiguous bytes per load.  With the plain row-major matrix every lane
 // walks its own 1200 B row -- 32 different cache lines per load instruction, each revisited four times -- and the
 // kernel ran at 2 TB/s of algorithmic traffic (61 us per pass over 100k x 300); K % 4 != 0 keeps that path.
-constexpr int SIM_THREADS = 512;     // 8 waves share one LDS query tile: 3 workgroups = 6 dependent MFMA chains per SIMD
 template <bool TILED>
 __global__ __launch_bounds__(SIM_THREADS) void sim_mfma_kernel(const float* __restrict__ index, int64_t D, int K, int64_t ld,
                                                        const float* __restrict__ q, int nq, float* __restrict__ out,
@@ -624,12 +624,8 @@ __global__ __launch_bounds__(256) void retile_kernel(const float* __restrict__ r
 // Algorithmic bytes per query: D * dim * 4 (index) + nnz * 8 + D * 12 (CSR) + D * (8 + 4) * 2 + D * 8 * 2 (scores, final).
 // =============================================================================================
 constexpr int S1_MAX_TERMS = 16;
-constexpr int S1_MAX_DIM = 768;
-constexpr int S1_THREADS = 128;
 constexpr int S1_SLOTS = 256;
-constexpr int S1_MIN_DOCS = 8192;
 constexpr int S1_LDS_TERMS = 6144;   // term ids of one workgroup's 128 documents staged in LDS (48 per document)
-constexpr int S1_GROUPS = 4096;      // at most this many document groups (a group = 64 * gw consecutive documents, one wave of search1_combine_kernel)
 
 struct Search1Query {            // passed by value: 3.3 KB of the 4 KB kernel-argument segment
     int32_t nt, dim;
@@ -1023,7 +1019,6 @@ __global__ __launch_bounds__(256) void search1_combine_kernel(const double* __re
     if ((lane & (gl - 1)) == 0) wmax[group * (64 / gl) + lane / gl] = (unsigned long long)order_key(m);      // a group past the last document stores the image of -inf
 }
 
-constexpr int S1_COLLECT_THREADS = 1024;
 struct S1HandOn {                // LDS of one workgroup of search1_collect_kernel / search1_finish_kernel
     uint32_t hist[4096];
     int scan[17];
@@ -1146,37 +1141,48 @@ static_assert(QP_COUNT == HIPTS_QUERY_PROF_CATEGORIES, "category count");
 const char* const kQueryProfNames[QP_COUNT] = {"bm25_postings_kernel", "sim_mfma_kernel", "rowmax_kernel<float>", "combine_kernel", "topk_kernel",
                                                "search1_score_kernel", "search1_combine_kernel", "search1_collect_kernel | search1_finish_kernel", "topk_kernel<candidates>"};
 
-struct QueryProfScope {
-    hipts_bm25* h;
-    hipStream_t s;
-    hipts_bm25::ProfRec r{};
-    bool on;
-    QueryProfScope(hipts_bm25* h_, hipStream_t s_, int cat, double bytes) : h(h_), s(s_), on(h_ && h_->prof) {
-        if (!on) return;
-        auto get = [&]() {
-            hipEvent_t e = nullptr;
-            if (!h->prof_pool.empty()) {
-                e = h->prof_pool.back();
-                h->prof_pool.pop_back();
-            } else if (hipEventCreate(&e) != hipSuccess) {
-                e = nullptr;
-            }
-            return e;
-        };
-        r.cat = cat;
-        r.bytes = bytes;
-        r.a = get();
-        r.b = get();
-        if (r.a) (void)hipEventRecord(r.a, s);
-    }
-    ~QueryProfScope() {
-        if (!on) return;
-        if (r.b) (void)hipEventRecord(r.b, s);
-        h->prof_recs.push_back(r);
-    }
+struct QueryProfScope : EventProfile<QP_COUNT>::Scope {
+    QueryProfScope(hipts_bm25* h, hipStream_t s, int cat, double bytes) : Scope(h && h->prof ? &h->ep : nullptr, s, cat, 0.0, bytes) {}
 };
 
+// rows of kk results each (ids hi, scores hv) as rows of k >= kk: the places past kk hold id -1, score -inf
+void pad_topk_rows(const int32_t* hi, const double* hv, int nq, int kk, int k, int32_t* ids_out, double* vals_out) {
+    if (kk == k) {
+        memcpy(ids_out, hi, (size_t)nq * k * 4);
+        memcpy(vals_out, hv, (size_t)nq * k * 8);
+        return;
+    }
+    for (int q = 0; q < nq; ++q)
+        for (int i = 0; i < k; ++i) {
+            ids_out[(size_t)q * k + i] = i < kk ? hi[(size_t)q * kk + i] : -1;
+            vals_out[(size_t)q * k + i] = i < kk ? hv[(size_t)q * kk + i] : -INFINITY;
+        }
+}
+
+static_assert(S1_STATE_BYTES == sizeof(Search1State) && S1_WITNESS_BYTES == sizeof(Search1Witness), "search1_plan lays these out");
 }  // namespace
+
+const QueryKnobs& hipts::query_knobs() {
+    static const QueryKnobs knobs = [] {
+        auto is = [](const char* name, const char* value) { const char* e = getenv(name); return e && strcmp(e, value) == 0; };
+        auto zero = [](const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; };
+        QueryKnobs k;
+        k.sim_tiled = !is("HIPTS_SIM", "rows");
+        k.sim_wide = !zero("HIPTS_SIM_WIDE");
+        k.sim_parts = !zero("HIPTS_SIM_PARTS");
+        k.bm25_scan = is("HIPTS_BM25", "scan");
+        k.bm25_parts = getenv("HIPTS_BM25_PARTS") ? atoi(getenv("HIPTS_BM25_PARTS")) : 0;
+        k.search1 = !is("HIPTS_SEARCH1", "0");
+        k.s1_finish = !zero("HIPTS_SEARCH1_FINISH");
+        k.s1_d2h = is("HIPTS_SEARCH1_D2H", "1");
+        k.s1_flag = !is("HIPTS_SEARCH1_FLAG", "0");
+        k.s1_pipe = !zero("HIPTS_S1_PIPE");
+        k.fused_topk = !zero("HIPTS_SEARCH_FUSED_TOPK");
+        k.overlap = getenv("HIPTS_SEARCH_OVERLAP") && atoi(getenv("HIPTS_SEARCH_OVERLAP")) != 0;
+        return k;
+    }();
+    return knobs;
+}
 
 // =============================================================================================
 // Dense index handle
@@ -1192,40 +1198,10 @@ struct hipts_index {
 
 namespace {
 
-// topk_kernel's score source for plain rows, [nq][n]
-TopkScores plain_rows(const double* v) {
-    TopkScores sc;
-    sc.v = v;
-    return sc;
-}
-
-// HIPTS_SIM_PARTS=0: the batched search takes the index products' row maxima with rowmax_kernel again (A/B; default: from the accumulators)
-bool sim_parts_enabled() {
-    static const bool on = !(getenv("HIPTS_SIM_PARTS") && atoi(getenv("HIPTS_SIM_PARTS")) == 0);
-    return on;
-}
-bool sim_wide_enabled() {
-    static const bool on = !(getenv("HIPTS_SIM_WIDE") && atoi(getenv("HIPTS_SIM_WIDE")) == 0) && !(getenv("HIPTS_SIM") && strcmp(getenv("HIPTS_SIM"), "rows") == 0);
-    return on;
-}
-// passes over the index that launch_sim makes for nq queries (the profile's algorithmic bytes)
-int sim_index_passes(bool tiled, int K, int nq) {
-    if (!(tiled && sim_wide_enabled() && K % 4 == 0)) return (nq + 31) / 32;
-    int passes = 0, done = 0;
-    while (nq - done > 32) {
-        done += std::min(256, nq - done);
-        ++passes;
-    }
-    return passes + (done < nq ? 1 : 0);
-}
-
-// parts / parts_grid (optional): when every query goes through the wide kernel, its per-workgroup row maxima are left in parts
-// ([query group of 256][SIMW_MAX_GRID][256] floats) and *parts_grid says how many workgroups wrote; *parts_grid = 0 otherwise (the caller
-// then runs rowmax_kernel over the stored products as before).
-constexpr int SIMW_MAX_GRID = 256;
-int launch_sim(const float* index, const float* tiled, int64_t D, int K, const float* q_dev, int nq, float* out_dev, int64_t out_ld,
-               hipStream_t s, float* parts = nullptr, int* parts_grid = nullptr) {
-    if (parts_grid) *parts_grid = 0;
+// The launches of sim_plan() (query_plan.h).  p.parts_grid > 0: the wide kernel's per-workgroup row maxima are left in parts ([query group
+// of 256][SIM_PARTS_MAX_GRID][256] floats, p.parts_bytes); otherwise the caller runs rowmax_kernel over the stored products.
+int launch_sim(const SimPlan& p, const float* index, const float* tiled, int64_t D, int K, const float* q_dev, int nq, float* out_dev,
+               int64_t out_ld, hipStream_t s, float* parts = nullptr) {
     const size_t lds = (size_t)K * 32 * sizeof(float);
     HIPTS_REQUIRE(lds <= 160 * 1024, "index dim %d too large for the query tile in LDS", K);
     static PerDevice attr_set;
@@ -1239,48 +1215,22 @@ int launch_sim(const float* index, const float* tiled, int64_t D, int K, const f
             attr_set.mark(dev);
         }
     }
-    static const bool use_tiled = !(getenv("HIPTS_SIM") && strcmp(getenv("HIPTS_SIM"), "rows") == 0);
-    const int64_t ntiles = (D + 31) / 32;
-    constexpr int WPB = SIM_THREADS / 64;
-    int grid = (int)std::min<int64_t>((ntiles + WPB - 1) / WPB, 256 * 4);
-    if (grid < 1) grid = 1;
-    // more than 32 queries over the tile-major copy: one pass per 256 queries (HIPTS_SIM_WIDE=0: the 32-query passes, for A/B)
-    const bool use_wide = sim_wide_enabled();
-    int q_done = 0;
-    if (tiled && use_tiled && use_wide && K % 4 == 0) {
-        // up to one workgroup per CU; a small index still fills them: the kernel splits the tiles it has across the query blocks
-        auto grid_for = [&](int nqb) { return (int)std::max<int64_t>(1, std::min<int64_t>((ntiles * nqb + 7) / 8, SIMW_MAX_GRID)); };
-        // the row maxima come out of the accumulators when no query is left for the 32-query kernel below and the groups share a grid
-        bool want_parts = parts && parts_grid && nq > 32;
-        if (want_parts) {
-            int rem = nq, g0 = -1;
-            while (rem > 32) {
-                const int n = std::min(256, rem), g = grid_for(n <= 64 ? 2 : n <= 128 ? 4 : 8);
-                if (g0 >= 0 && g != g0) want_parts = false;
-                g0 = g;
-                rem -= n;
-            }
-            if (rem > 0) want_parts = false;
-        }
-        while (nq - q_done > 32) {
-            const int n = std::min(256, nq - q_done);
-            const float4* t4 = reinterpret_cast<const float4*>(tiled);
-            const float* qp = q_dev + (int64_t)q_done * K;
-            float* op = out_dev + (int64_t)q_done * out_ld;
-            float* pm = want_parts ? parts + (int64_t)(q_done / 256) * SIMW_MAX_GRID * 256 : nullptr;
-            const int nqb = n <= 64 ? 2 : n <= 128 ? 4 : 8;
-            if (nqb == 2) sim_mfma_wide_kernel<2><<<grid_for(2), 512, 0, s>>>(t4, D, K, qp, n, op, out_ld, pm);
-            else if (nqb == 4) sim_mfma_wide_kernel<4><<<grid_for(4), 512, 0, s>>>(t4, D, K, qp, n, op, out_ld, pm);
-            else sim_mfma_wide_kernel<8><<<grid_for(8), 512, 0, s>>>(t4, D, K, qp, n, op, out_ld, pm);
-            HIPTS_LAUNCH_CHECK();
-            if (want_parts) *parts_grid = grid_for(nqb);
-            q_done += n;
-        }
+    HIPTS_REQUIRE(p.parts_grid == 0 || parts, "launch_sim: the plan wants a buffer for the row maxima");
+    const float4* t4 = reinterpret_cast<const float4*>(tiled);
+    for (int i = 0; i < p.wide_passes; ++i) {
+        const SimPass w = sim_wide_pass(p, i);
+        float* pm = p.parts_grid > 0 ? parts + (int64_t)i * SIM_PARTS_GROUP_FLOATS : nullptr;
+        const float* qp = q_dev + (int64_t)w.q0 * K;
+        float* op = out_dev + (int64_t)w.q0 * out_ld;
+        if (w.nqb == 2) sim_mfma_wide_kernel<2><<<w.grid, 512, 0, s>>>(t4, D, K, qp, w.n, op, out_ld, pm);
+        else if (w.nqb == 4) sim_mfma_wide_kernel<4><<<w.grid, 512, 0, s>>>(t4, D, K, qp, w.n, op, out_ld, pm);
+        else sim_mfma_wide_kernel<8><<<w.grid, 512, 0, s>>>(t4, D, K, qp, w.n, op, out_ld, pm);
+        HIPTS_LAUNCH_CHECK();
     }
-    for (int q0 = q_done; q0 < nq; q0 += 32) {
-        const int n = std::min(32, nq - q0);
-        if (tiled && use_tiled) sim_mfma_kernel<true><<<grid, SIM_THREADS, lds, s>>>(tiled, D, K, K, q_dev + (int64_t)q0 * K, n, out_dev + (int64_t)q0 * out_ld, out_ld);
-        else sim_mfma_kernel<false><<<grid, SIM_THREADS, lds, s>>>(index, D, K, K, q_dev + (int64_t)q0 * K, n, out_dev + (int64_t)q0 * out_ld, out_ld);
+    for (int i = 0; i < p.tail_passes; ++i) {
+        const int q0 = p.tail_q0 + i * 32, n = std::min(32, nq - q0);
+        if (p.tail_tiled) sim_mfma_kernel<true><<<p.tail_grid, SIM_THREADS, lds, s>>>(tiled, D, K, K, q_dev + (int64_t)q0 * K, n, out_dev + (int64_t)q0 * out_ld, out_ld);
+        else sim_mfma_kernel<false><<<p.tail_grid, SIM_THREADS, lds, s>>>(index, D, K, K, q_dev + (int64_t)q0 * K, n, out_dev + (int64_t)q0 * out_ld, out_ld);
         HIPTS_LAUNCH_CHECK();
     }
     return HIPTS_OK;
@@ -1288,26 +1238,22 @@ int launch_sim(const float* index, const float* tiled, int64_t D, int K, const f
 
 int launch_bm25(hipts_bm25* h, const int32_t* qt_dev, const double* qw_dev, const int32_t* qp_dev, int nq, double* out_dev,
                 hipStream_t s, double* max_out = nullptr) {
-    static const bool scan = getenv("HIPTS_BM25") && strcmp(getenv("HIPTS_BM25"), "scan") == 0;   // A/B: document-major scan
-    // HIPTS_BM25_PARTS: workgroups per query of the sliced kernel (1 = the one-workgroup-per-query kernel; default: enough to put ~1024 on the chip)
-    static const int parts_env = getenv("HIPTS_BM25_PARTS") ? atoi(getenv("HIPTS_BM25_PARTS")) : 0;
-    if (!scan && h->slice_docs > 0 && parts_env != 1) {
-        int parts = parts_env;
-        if (parts != 2 && parts != 4 && parts != 8) parts = nq >= 256 ? 4 : 8;
+    const Bm25Plan plan = bm25_plan(nq, h->slice_docs, query_knobs());
+    if (plan.kernel == Bm25Plan::SLICED) {
         HIPTS_TRY(h->ws_mark.reserve((size_t)nq * h->D));
-        if (max_out) HIPTS_TRY(h->ws_maxpart.reserve((size_t)nq * parts * 8));
-        bm25_postings_sliced_kernel<<<dim3(nq, parts), 512, 0, s>>>(h->d_tslice.as<int64_t>(), h->d_tdoc.as<int32_t>(), h->d_ttf.as<int32_t>(),
+        if (max_out) HIPTS_TRY(h->ws_maxpart.reserve((size_t)nq * plan.parts * 8));
+        bm25_postings_sliced_kernel<<<dim3(nq, plan.parts), 512, 0, s>>>(h->d_tslice.as<int64_t>(), h->d_tdoc.as<int32_t>(), h->d_ttf.as<int32_t>(),
                                                                      h->d_dl.as<int32_t>(), h->d_idf.as<double>(), h->V, h->avgdl, h->D, h->slice_docs,
-                                                                     BM25_SLICES / parts, qt_dev, qw_dev, qp_dev, out_dev, h->ws_mark.as<uint8_t>(),
+                                                                     BM25_SLICES / plan.parts, qt_dev, qw_dev, qp_dev, out_dev, h->ws_mark.as<uint8_t>(),
                                                                      max_out ? h->ws_maxpart.as<double>() : nullptr);
         HIPTS_LAUNCH_CHECK();
         if (max_out) {
-            bm25_max_reduce_kernel<<<ceil_div(nq, 256), 256, 0, s>>>(h->ws_maxpart.as<double>(), parts, max_out, nq);
+            bm25_max_reduce_kernel<<<ceil_div(nq, 256), 256, 0, s>>>(h->ws_maxpart.as<double>(), plan.parts, max_out, nq);
             HIPTS_LAUNCH_CHECK();
         }
         return HIPTS_OK;
     }
-    if (!scan) {
+    if (plan.kernel == Bm25Plan::POSTINGS) {
         HIPTS_TRY(h->ws_mark.reserve((size_t)nq * h->D));
         bm25_postings_kernel<<<nq, 1024, 0, s>>>(h->d_tptr.as<int64_t>(), h->d_tdoc.as<int32_t>(), h->d_ttf.as<int32_t>(),
                                                  h->d_dl.as<int32_t>(), h->d_idf.as<double>(), h->V, h->avgdl, h->D, qt_dev, qw_dev,
@@ -1327,24 +1273,31 @@ int launch_bm25(hipts_bm25* h, const int32_t* qt_dev, const double* qw_dev, cons
     return HIPTS_OK;
 }
 
+// The packed queries of a batch (query_pack): fills the host image `hin`; returns where its parts lie once it is copied to `dev`
+struct PackedQueries { const int32_t* qt; const double* qw; const int32_t* qp; const float* qvec; };
+PackedQueries pack_queries(const QueryPack& pk, char* hin, const void* dev, const int32_t* q_terms, const double* q_weights, const int32_t* q_ptr,
+                           const float* q_vectors, int nt, int nq, int dim) {
+    if (nt) {
+        memcpy(hin, q_terms, (size_t)nt * 4);
+        memcpy(hin + pk.off_w, q_weights, (size_t)nt * 8);
+    }
+    memcpy(hin + pk.off_p, q_ptr, (size_t)(nq + 1) * 4);
+    if (dim) memcpy(hin + pk.off_v, q_vectors, (size_t)nq * dim * 4);
+    const char* d = static_cast<const char*>(dev);
+    return PackedQueries{reinterpret_cast<const int32_t*>(d), reinterpret_cast<const double*>(d + pk.off_w), reinterpret_cast<const int32_t*>(d + pk.off_p),
+                         reinterpret_cast<const float*>(d + pk.off_v)};
+}
+
 // stage the CSR query description in the handle's workspace; returns device pointers
-int stage_queries(hipts_bm25* h, const int32_t* q_terms, const double* q_weights, const int32_t* q_ptr, int nq,
-                  const int32_t** qt, const double** qw, const int32_t** qp, hipStream_t s) {
+int stage_queries(hipts_bm25* h, const int32_t* q_terms, const double* q_weights, const int32_t* q_ptr, int nq, PackedQueries* q, hipStream_t s) {
     const int nt = q_ptr[nq];
     HIPTS_REQUIRE(q_ptr[0] == 0 && nt >= 0, "q_ptr must start at 0 and be non-decreasing");
-    const size_t off_w = ((size_t)nt * 4 + 15) / 16 * 16;
-    const size_t off_p = off_w + (size_t)nt * 8;
-    const size_t total = off_p + (size_t)(nq + 1) * 4;
-    HIPTS_TRY(h->ws_q.reserve(total));
-    std::vector<char> host(total, 0);
-    memcpy(host.data(), q_terms, (size_t)nt * 4);
-    memcpy(host.data() + off_w, q_weights, (size_t)nt * 8);
-    memcpy(host.data() + off_p, q_ptr, (size_t)(nq + 1) * 4);
-    HIPTS_HIP(hipMemcpyAsync(h->ws_q.p, host.data(), total, hipMemcpyHostToDevice, s));
+    const QueryPack pack = query_pack(nt, nq, 0);
+    HIPTS_TRY(h->ws_q.reserve(pack.bytes));
+    std::vector<char> host(pack.bytes, 0);
+    *q = pack_queries(pack, host.data(), h->ws_q.p, q_terms, q_weights, q_ptr, nullptr, nt, nq, 0);
+    HIPTS_HIP(hipMemcpyAsync(h->ws_q.p, host.data(), pack.bytes, hipMemcpyHostToDevice, s));
     HIPTS_HIP(hipStreamSynchronize(s));   // `host` goes out of scope
-    *qt = h->ws_q.as<int32_t>();
-    *qw = reinterpret_cast<const double*>(h->ws_q.as<char>() + off_w);
-    *qp = reinterpret_cast<const int32_t*>(h->ws_q.as<char>() + off_p);
     return HIPTS_OK;
 }
 
@@ -1364,121 +1317,73 @@ int search_one(hipts_bm25* bm25, hipts_index* index, const int32_t* q_terms, con
     memcpy(Q.q, q_vector, (size_t)index->dim * 4);
     HIPTS_TRY(bm25->ws_scores.reserve((size_t)D * 8));
     HIPTS_TRY(bm25->ws_sims.reserve((size_t)D * 4));
-    double* final_dev = final_out_device;
-    if (!final_dev) {
-        HIPTS_TRY(bm25->ws_final.reserve((size_t)D * 8));
-        final_dev = bm25->ws_final.as<double>();
-    }
-    const int64_t waves = (D + 63) / 64;
-    const int gw = (int)((waves + S1_GROUPS - 1) / S1_GROUPS);                   // 64 * gw documents per group
-    const int blocks2 = (int)((waves + (int64_t)gw * 4 - 1) / ((int64_t)gw * 4));
-    const int blocks3 = ceil_div(D, S1_COLLECT_THREADS);
-    const int kk = (int)std::min<int64_t>(k, D);
-    // lanes per group: 64 unless that leaves fewer than 2.5 k groups (then the k-th largest group maximum bounds little: with fewer
-    // groups than k every finite score is a candidate); down to 4.  G groups give about G * -ln(1 - k / G) candidates.
-    int gl = 64;
-    while (gw == 1 && gl > 4 && D / gl < (int64_t)kk * 5 / 2) gl >>= 1;
-    const int groups = blocks2 * 4 * (64 / gl);
-    // candidate slots per collect workgroup (1024 documents): four times the expected share of ~1.7 k candidates, 64 .. 1024
-    int bcap = S1_BLOCK_CAP;
-    while (bcap < 1024 && (int64_t)bcap * D < (int64_t)4 * 1024 * 17 * kk / 10) bcap <<= 1;
-    // workspace: state | group maxima u64[groups] | per-workgroup counts u32[blocks3] | flags u32[blocks3] | keys u64[blocks3][CAP] | ids u32[blocks3][CAP]
-    const size_t off_wmax = (sizeof(Search1State) + 15) / 16 * 16;
-    const size_t off_bcnt = off_wmax + (size_t)groups * 8;
-    const size_t off_bflag = off_bcnt + (size_t)blocks3 * 4;
-    const size_t off_bkey = (off_bflag + (size_t)blocks3 * 4 + 15) / 16 * 16;
-    const size_t off_bid = off_bkey + (size_t)blocks3 * bcap * 8;
-    // combine + collect in one launch (search1_finish_kernel) when a group is exactly one wave of the score kernel: its threshold comes from
-    // the score kernel's witness records (HIPTS_SEARCH1_FINISH=0: the two kernels, for A/B)
-    static const bool allow_finish = !(getenv("HIPTS_SEARCH1_FINISH") && atoi(getenv("HIPTS_SEARCH1_FINISH")) == 0);
-    const bool finish = allow_finish && gl == 64 && gw == 1;
-    const size_t off_wit = (off_bid + (size_t)blocks3 * bcap * 4 + 31) / 32 * 32;
-    const size_t ws_bytes = off_wit + (finish ? (size_t)ceil_div(D, S1_THREADS) * (S1_THREADS / 64) * sizeof(Search1Witness) : 0);
-    if (bm25->s1_state.bytes < ws_bytes) {
-        HIPTS_TRY(bm25->s1_state.alloc(ws_bytes));
+    if (!final_out_device) HIPTS_TRY(bm25->ws_final.reserve((size_t)D * 8));
+    double* final_dev = final_out_device ? final_out_device : bm25->ws_final.as<double>();
+    const QueryKnobs& knobs = query_knobs();
+    const Search1Plan P = search1_plan(D, k, knobs);
+    const int kk = P.kk, blocks3 = P.blocks3;
+    if (bm25->s1_state.bytes < P.ws_bytes) {
+        HIPTS_TRY(bm25->s1_state.alloc(P.ws_bytes));
         bm25->s1_dirty = true;
     }
     char* ws = bm25->s1_state.as<char>();
     Search1State* st = reinterpret_cast<Search1State*>(ws);
     if (bm25->s1_dirty) HIPTS_HIP(hipMemsetAsync(st, 0, sizeof(Search1State), s));
     bm25->s1_dirty = true;                    // until the last kernel (which clears the maxima slots) has been enqueued
-    unsigned long long* wmax = reinterpret_cast<unsigned long long*>(ws + off_wmax);
-    uint32_t* bcnt = reinterpret_cast<uint32_t*>(ws + off_bcnt);
-    uint32_t* bflag = reinterpret_cast<uint32_t*>(ws + off_bflag);
-    unsigned long long* bkey = reinterpret_cast<unsigned long long*>(ws + off_bkey);
-    uint32_t* bid = reinterpret_cast<uint32_t*>(ws + off_bid);
-    Search1Witness* wit = finish ? reinterpret_cast<Search1Witness*>(ws + off_wit) : nullptr;
-    const size_t out_bytes = (size_t)kk * 12;
-    HIPTS_TRY(bm25->pin_out.reserve(out_bytes + 192));
+    unsigned long long* wmax = reinterpret_cast<unsigned long long*>(ws + P.off_wmax);
+    uint32_t* bcnt = reinterpret_cast<uint32_t*>(ws + P.off_bcnt);
+    uint32_t* bflag = reinterpret_cast<uint32_t*>(ws + P.off_bflag);
+    unsigned long long* bkey = reinterpret_cast<unsigned long long*>(ws + P.off_bkey);
+    uint32_t* bid = reinterpret_cast<uint32_t*>(ws + P.off_bid);
+    Search1Witness* wit = P.finish ? reinterpret_cast<Search1Witness*>(ws + P.off_wit) : nullptr;
+    HIPTS_TRY(bm25->pin_out.reserve(P.out_bytes + 192));
     double* hv = bm25->pin_out.as<double>();                  // pinned + mapped: the last kernel stores the results here
     int32_t* hi = reinterpret_cast<int32_t*>(hv + kk);
-    static const bool via_copy = getenv("HIPTS_SEARCH1_D2H") && strcmp(getenv("HIPTS_SEARCH1_D2H"), "1") == 0;     // A/B: device buffer + copy
-    static const bool allow_flag = !(getenv("HIPTS_SEARCH1_FLAG") && strcmp(getenv("HIPTS_SEARCH1_FLAG"), "0") == 0);   // A/B: completion by stream synchronise
-    const bool use_flag = allow_flag && !via_copy && !bm25->prof;
-    uint32_t* flag = reinterpret_cast<uint32_t*>(bm25->pin_out.as<char>() + ((out_bytes + 63) / 64 * 64));       // its own cache line behind the results
+    const bool via_copy = knobs.s1_d2h, use_flag = knobs.s1_flag && !via_copy && !bm25->prof;
+    uint32_t* flag = reinterpret_cast<uint32_t*>(bm25->pin_out.as<char>() + P.off_flag);       // its own cache line behind the results
     if (++bm25->s1_seq == 0) bm25->s1_seq = 1;
     const uint32_t seq = bm25->s1_seq;
     if (use_flag) __atomic_store_n(flag, 0u, __ATOMIC_RELAXED);          // (fresh pinned memory is not zeroed)
-    double* ov = hv;
-    int32_t* oi = hi;
-    if (via_copy) {
-        HIPTS_TRY(bm25->ws_out.reserve(out_bytes + 64));
-        ov = bm25->ws_out.as<double>();
-        oi = reinterpret_cast<int32_t*>(ov + kk);
-    }
+    if (via_copy) HIPTS_TRY(bm25->ws_out.reserve(P.out_bytes + 64));
+    double* ov = via_copy ? bm25->ws_out.as<double>() : hv;            // where the last kernel stores: scores, then ids
+    int32_t* oi = reinterpret_cast<int32_t*>(ov + kk);
     {
         QueryProfScope ps(bm25, s, QP_S1_SCORE, (double)D * index->dim * 4.0 + (double)bm25->nnz * 8.0 + (double)D * (8 + 4 + 8 + 4));
-        static const bool pipe = !(getenv("HIPTS_S1_PIPE") && atoi(getenv("HIPTS_S1_PIPE")) == 0);      // A/B: the sequential form
-        if (pipe)
-            search1_score_kernel<true><<<ceil_div(D, S1_THREADS), S1_THREADS, 0, s>>>(Q, index->tiled.as<float4>(), D, bm25->d_ptr.as<int64_t>(),
-                                                                                  bm25->d_term.as<int32_t>(), bm25->d_tf.as<int32_t>(),
-                                                                                  bm25->d_dl.as<int32_t>(), bm25->d_idf.as<double>(), bm25->V, bm25->avgdl,
-                                                                                  bm25->ws_scores.as<double>(), bm25->ws_sims.as<float>(), st, wit);
-        else
-            search1_score_kernel<false><<<ceil_div(D, S1_THREADS), S1_THREADS, 0, s>>>(Q, index->tiled.as<float4>(), D, bm25->d_ptr.as<int64_t>(),
-                                                                                   bm25->d_term.as<int32_t>(), bm25->d_tf.as<int32_t>(),
-                                                                                   bm25->d_dl.as<int32_t>(), bm25->d_idf.as<double>(), bm25->V, bm25->avgdl,
-                                                                                   bm25->ws_scores.as<double>(), bm25->ws_sims.as<float>(), st, wit);
+        auto* score = knobs.s1_pipe ? search1_score_kernel<true> : search1_score_kernel<false>;       // HIPTS_S1_PIPE=0: the sequential form
+        score<<<P.grid_score, S1_THREADS, 0, s>>>(Q, index->tiled.as<float4>(), D, bm25->d_ptr.as<int64_t>(), bm25->d_term.as<int32_t>(),
+                                                  bm25->d_tf.as<int32_t>(), bm25->d_dl.as<int32_t>(), bm25->d_idf.as<double>(), bm25->V, bm25->avgdl,
+                                                  bm25->ws_scores.as<double>(), bm25->ws_sims.as<float>(), st, wit);
         HIPTS_LAUNCH_CHECK();
     }
-    if (finish) {
-        QueryProfScope ps(bm25, s, QP_S1_COLLECT, (double)D * 20.0 + (double)blocks3 * (double)waves * 32.0);
+    if (P.finish) {
+        QueryProfScope ps(bm25, s, QP_S1_COLLECT, (double)D * 20.0 + (double)blocks3 * (double)P.waves * 32.0);
         search1_finish_kernel<<<blocks3, S1_COLLECT_THREADS, 0, s>>>(bm25->ws_scores.as<double>(), bm25->ws_sims.as<float>(), D, kk, w_bm25, (float)w_sim,
-                                                                     final_dev, st, wit, (int)waves, bcnt, bflag, bkey, bid, bcap);
+                                                                     final_dev, st, wit, (int)P.waves, bcnt, bflag, bkey, bid, P.bcap);
         HIPTS_LAUNCH_CHECK();
     } else {
         {
             QueryProfScope ps(bm25, s, QP_S1_COMBINE, (double)D * 20.0);
-            search1_combine_kernel<<<blocks2, 256, 0, s>>>(bm25->ws_scores.as<double>(), bm25->ws_sims.as<float>(), D, w_bm25, (float)w_sim, final_dev,
-                                                           st, wmax, gw, gl);
+            search1_combine_kernel<<<P.blocks2, 256, 0, s>>>(bm25->ws_scores.as<double>(), bm25->ws_sims.as<float>(), D, w_bm25, (float)w_sim, final_dev,
+                                                           st, wmax, P.gw, P.gl);
             HIPTS_LAUNCH_CHECK();
         }
         {
             QueryProfScope ps(bm25, s, QP_S1_COLLECT, (double)D * 8.0);
-            search1_collect_kernel<<<blocks3, S1_COLLECT_THREADS, 0, s>>>(final_dev, D, kk, wmax, groups, bcnt, bflag, bkey, bid, bcap);
+            search1_collect_kernel<<<blocks3, S1_COLLECT_THREADS, 0, s>>>(final_dev, D, kk, wmax, P.groups, bcnt, bflag, bkey, bid, P.bcap);
             HIPTS_LAUNCH_CHECK();
         }
     }
     {
         QueryProfScope ps(bm25, s, QP_S1_TOPK, (double)kk * 24.0);
-        TopkHandOn hand;
-        hand.clear = reinterpret_cast<uint32_t*>(st);                  // the maxima slots, up to dbg
-        hand.clear_words = (int)(offsetof(Search1State, dbg) / 4);
-        hand.dbg = hand.clear + hand.clear_words;
-        hand.counts = bcnt;
-        hand.flags = bflag;
-        hand.keys = bkey;
-        hand.ids = bid;
-        hand.blocks = blocks3;
-        hand.cap = bcap;
-        TopkPublish pub;
-        pub.flag = use_flag ? flag : nullptr;
-        pub.seq = seq;
-        topk_kernel<<<1, 1024, 0, s>>>(plain_rows(final_dev), D, kk, oi, ov, hand, pub);
+        uint32_t* clear = reinterpret_cast<uint32_t*>(st);             // the maxima slots, up to dbg
+        const int clear_words = (int)(offsetof(Search1State, dbg) / 4);
+        const TopkHandOn hand{clear, clear_words, clear + clear_words, bcnt, bflag, bkey, bid, blocks3, P.bcap};
+        const TopkPublish pub{use_flag ? flag : nullptr, seq};
+        topk_kernel<<<1, 1024, 0, s>>>(TopkScores{final_dev}, D, kk, oi, ov, hand, pub);
         HIPTS_LAUNCH_CHECK();
     }
     bm25->s1_dirty = false;
-    if (via_copy) HIPTS_HIP(hipMemcpyAsync(hv, ov, out_bytes, hipMemcpyDeviceToHost, s));
+    if (via_copy) HIPTS_HIP(hipMemcpyAsync(hv, ov, P.out_bytes, hipMemcpyDeviceToHost, s));
     bool seen = false;
     if (use_flag) {
         // spin on the sequence number the last kernel releases after its result stores (bounded: then the ordinary synchronise)
@@ -1492,10 +1397,7 @@ int search_one(hipts_bm25* bm25, hipts_index* index, const int32_t* q_terms, con
         }
     }
     if (!seen) HIPTS_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < k; ++i) {
-        ids_out[i] = i < kk ? hi[i] : -1;
-        vals_out[i] = i < kk ? hv[i] : -INFINITY;
-    }
+    pad_topk_rows(hi, hv, 1, kk, k, ids_out, vals_out);
     return HIPTS_OK;
 }
 
@@ -1506,35 +1408,17 @@ extern "C" {
 int hipts_query_profile_enable(hipts_bm25_t* h, int enable) {
     HIPTS_REQUIRE(h, "null handle");
     h->prof = enable != 0;
-    if (enable) {
-        for (int c = 0; c < QP_COUNT; ++c) {
-            h->prof_ms[c] = 0.0;
-            h->prof_bytes[c] = 0.0;
-            h->prof_n[c] = 0;
-        }
-    }
+    if (enable) h->ep.reset();
     return HIPTS_OK;
 }
 
 int hipts_query_profile_read(hipts_bm25_t* h, int category, double* total_ms, int64_t* launches, double* total_bytes) {
     HIPTS_REQUIRE(h && category >= 0 && category < QP_COUNT, "hipts_query_profile_read: bad arguments");
     HIPTS_TRY(use_device(h->device));
-    for (auto& r : h->prof_recs) {
-        if (r.a && r.b) {
-            HIPTS_HIP(hipEventSynchronize(r.b));
-            float ms = 0.f;
-            HIPTS_HIP(hipEventElapsedTime(&ms, r.a, r.b));
-            h->prof_ms[r.cat] += ms;
-            h->prof_n[r.cat] += 1;
-            h->prof_bytes[r.cat] += r.bytes;
-        }
-        if (r.a) h->prof_pool.push_back(r.a);
-        if (r.b) h->prof_pool.push_back(r.b);
-    }
-    h->prof_recs.clear();
-    if (total_ms) *total_ms = h->prof_ms[category];
-    if (launches) *launches = h->prof_n[category];
-    if (total_bytes) *total_bytes = h->prof_bytes[category];
+    HIPTS_TRY(h->ep.resolve());
+    if (total_ms) *total_ms = h->ep.ms[category];
+    if (launches) *launches = h->ep.n[category];
+    if (total_bytes) *total_bytes = h->ep.bytes[category];
     return HIPTS_OK;
 }
 
@@ -1557,6 +1441,24 @@ int hiptsdbg_search1_last(hipts_bm25_t* h, uint32_t* candidates, uint32_t* took_
     HIPTS_HIP(hipMemcpy(dbg, reinterpret_cast<const char*>(h->s1_state.p) + offsetof(Search1State, dbg), sizeof(dbg), hipMemcpyDeviceToHost));
     *candidates = dbg[0];
     *took_candidate_path = dbg[1];
+    return HIPTS_OK;
+}
+
+int hiptsdbg_search1_plan(int64_t D, int k, unsigned knob_bits, hiptsdbg_search1_plan_t* out) {
+    HIPTS_REQUIRE(out && D >= 1 && D < (1ll << 32) && k >= 1 && k <= TOPK_MAX_K, "hiptsdbg_search1_plan: bad argument");
+    QueryKnobs kn;
+    kn.s1_finish = (knob_bits & HIPTSDBG_QUERY_FINISH) != 0;
+    *out = search1_plan(D, k, kn);
+    return HIPTS_OK;
+}
+
+int hiptsdbg_sim_plan(int have_tiled, int64_t D, int K, int nq, int want_parts, unsigned knob_bits, hiptsdbg_sim_plan_t* out) {
+    HIPTS_REQUIRE(out && D >= 1 && K >= 1 && nq >= 1, "hiptsdbg_sim_plan: bad argument");
+    QueryKnobs kn;
+    kn.sim_wide = (knob_bits & HIPTSDBG_QUERY_WIDE) != 0;
+    kn.sim_tiled = (knob_bits & HIPTSDBG_QUERY_TILED) != 0;
+    kn.sim_parts = (knob_bits & HIPTSDBG_QUERY_PARTS) != 0;
+    *out = sim_plan(have_tiled != 0, D, K, nq, want_parts != 0, kn);
     return HIPTS_OK;
 }
 
@@ -1720,16 +1622,14 @@ int hipts_bm25_score(hipts_bm25_t* h, const int32_t* q_terms, const double* q_we
     HIPTS_REQUIRE(h && q_ptr && scores_out && nq >= 1, "hipts_bm25_score: bad arguments");
     HIPTS_TRY(use_device(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const int32_t* qt;
-    const double* qw;
-    const int32_t* qp;
-    HIPTS_TRY(stage_queries(h, q_terms, q_weights, q_ptr, nq, &qt, &qw, &qp, s));
+    PackedQueries q;
+    HIPTS_TRY(stage_queries(h, q_terms, q_weights, q_ptr, nq, &q, s));
     double* out_dev = scores_out;
     if (out_memspace != HIPTS_DEVICE) {
         HIPTS_TRY(h->ws_scores.reserve((size_t)nq * h->D * 8));
         out_dev = h->ws_scores.as<double>();
     }
-    HIPTS_TRY(launch_bm25(h, qt, qw, qp, nq, out_dev, s));
+    HIPTS_TRY(launch_bm25(h, q.qt, q.qw, q.qp, nq, out_dev, s));
     return copy_out(scores_out, out_dev, (size_t)nq * h->D * 8, out_memspace, s);
 }
 
@@ -1847,8 +1747,8 @@ int hipts_index_query(hipts_index_t* h, const float* queries, int queries_memspa
         HIPTS_TRY(h->ws_out.reserve((size_t)nq * h->len * 4));
         out_dev = h->ws_out.as<float>();
     }
-    static const bool allow_one = !(getenv("HIPTS_SEARCH1") && strcmp(getenv("HIPTS_SEARCH1"), "0") == 0);
-    if (nq == 1 && allow_one && queries_memspace != HIPTS_DEVICE && h->dim <= S1_MAX_DIM && h->dim % 4 == 0 && h->tiled.p && h->len >= S1_MIN_DOCS) {
+    const QueryKnobs& knobs = query_knobs();
+    if (search1_eligible(nq, h->dim, h->tiled.p != nullptr, h->len, knobs) && queries_memspace != HIPTS_DEVICE) {
         Sim1Query Q;                      // a host query goes straight into the kernel arguments: no staging copy
         memset(&Q, 0, sizeof(Q));
         Q.dim = h->dim;
@@ -1863,7 +1763,8 @@ int hipts_index_query(hipts_index_t* h, const float* queries, int queries_memspa
         HIPTS_HIP(hipMemcpyAsync(h->ws_q.p, queries, (size_t)nq * h->dim * 4, hipMemcpyHostToDevice, s));
         q_dev = h->ws_q.as<float>();
     }
-    HIPTS_TRY(launch_sim(h->rows.as<float>(), h->tiled.as<float>(), h->len, h->dim, q_dev, nq, out_dev, h->len, s));
+    HIPTS_TRY(launch_sim(sim_plan(h->tiled.p != nullptr, h->len, h->dim, nq, false, knobs), h->rows.as<float>(), h->tiled.as<float>(), h->len, h->dim, q_dev, nq,
+                         out_dev, h->len, s));
     return copy_out(scores_out, out_dev, (size_t)nq * h->len * 4, out_memspace, s);
 }
 
@@ -1872,23 +1773,12 @@ int hipts_combine(const double* a, const float* b, int nq, int64_t n, double wa,
                   double* out, int device, void* stream) {
     HIPTS_REQUIRE(a && b && out && nq >= 1 && n >= 1, "hipts_combine: bad arguments");
     HIPTS_TRY(use_device(device));
-    hipStream_t s = (hipStream_t)stream;
     DevBuf& maxbuf = scratch_buf(device, 0);
     HIPTS_TRY(maxbuf.reserve((size_t)nq * 16));
-    double* ma = maxbuf.as<double>();
-    float* mb = reinterpret_cast<float*>(ma + nq);
-    if (norm_a) {
-        rowmax_kernel<double><<<nq, 1024, 0, s>>>(a, n, ma);
-        HIPTS_LAUNCH_CHECK();
-    }
-    if (norm_b) {
-        rowmax_kernel<float><<<nq, 1024, 0, s>>>(b, n, mb);
-        HIPTS_LAUNCH_CHECK();
-    }
-    dim3 grid(ceil_div(n, 256), nq);
-    combine_kernel<<<grid, 256, 0, s>>>(a, b, n, wa, (float)wb, norm_a ? ma : nullptr, norm_b ? mb : nullptr, nullptr, out);
-    HIPTS_LAUNCH_CHECK();
-    return HIPTS_OK;
+    double* ma = norm_a ? maxbuf.as<double>() : nullptr;
+    float* mb = norm_b ? reinterpret_cast<float*>(maxbuf.as<double>() + nq) : nullptr;
+    HIPTS_TRY(hipts_rowmax(norm_a ? a : nullptr, norm_b ? b : nullptr, nq, n, ma, mb, device, stream));
+    return hipts_combine_with_max(a, b, nq, n, wa, wb, ma, mb, out, device, stream);
 }
 
 int hipts_rowmax(const double* a, const float* b, int nq, int64_t n, double* max_a_out, float* max_b_out, int device,
@@ -1927,7 +1817,7 @@ int hipts_topk(const double* vals, int nq, int64_t n, int k, int32_t* ids_out, d
     const int kk = (int)std::min<int64_t>(k, n);
     if (out_memspace == HIPTS_DEVICE) {
         HIPTS_REQUIRE(kk == k, "hipts_topk: k > n needs host outputs");
-        topk_kernel<<<nq, 1024, 0, s>>>(plain_rows(vals), n, k, ids_out, vals_out);
+        topk_kernel<<<nq, 1024, 0, s>>>(TopkScores{vals}, n, k, ids_out, vals_out);
         HIPTS_LAUNCH_CHECK();
         return HIPTS_OK;
     }
@@ -1935,18 +1825,14 @@ int hipts_topk(const double* vals, int nq, int64_t n, int k, int32_t* ids_out, d
     HIPTS_TRY(obuf.reserve((size_t)nq * kk * 12 + 64));
     double* ov = obuf.as<double>();
     int32_t* oi = reinterpret_cast<int32_t*>(ov + (size_t)nq * kk);
-    topk_kernel<<<nq, 1024, 0, s>>>(plain_rows(vals), n, kk, oi, ov);
+    topk_kernel<<<nq, 1024, 0, s>>>(TopkScores{vals}, n, kk, oi, ov);
     HIPTS_LAUNCH_CHECK();
     std::vector<int32_t> hi((size_t)nq * kk);
     std::vector<double> hv((size_t)nq * kk);
     HIPTS_HIP(hipMemcpyAsync(hi.data(), oi, hi.size() * 4, hipMemcpyDeviceToHost, s));
     HIPTS_HIP(hipMemcpyAsync(hv.data(), ov, hv.size() * 8, hipMemcpyDeviceToHost, s));
     HIPTS_HIP(hipStreamSynchronize(s));
-    for (int q = 0; q < nq; ++q)
-        for (int i = 0; i < k; ++i) {
-            ids_out[(size_t)q * k + i] = i < kk ? hi[(size_t)q * kk + i] : -1;
-            vals_out[(size_t)q * k + i] = i < kk ? hv[(size_t)q * kk + i] : -INFINITY;
-        }
+    pad_topk_rows(hi.data(), hv.data(), nq, kk, k, ids_out, vals_out);
     return HIPTS_OK;
 }
 
@@ -1995,8 +1881,8 @@ static int search_submit_impl(hipts_bm25_t* bm25, hipts_index_t* index, const in
     HIPTS_REQUIRE(q_ptr[0] == 0 && nt >= 0, "q_ptr must start at 0 and be non-decreasing");
     S.nq = nq;
     S.k = k;
-    static const bool allow_one = !(getenv("HIPTS_SEARCH1") && strcmp(getenv("HIPTS_SEARCH1"), "0") == 0);       // A/B switch
-    if (nq == 1 && allow_one && nt <= S1_MAX_TERMS && index->dim <= S1_MAX_DIM && index->dim % 4 == 0 && index->tiled.p && D >= S1_MIN_DOCS) {
+    const QueryKnobs& knobs = query_knobs();
+    if (search1_eligible(nq, index->dim, index->tiled.p != nullptr, D, knobs) && nt <= S1_MAX_TERMS) {
         // the one-query path completes inside the call (its last kernel stores into pinned memory and the host spins on a flag)
         S.ids1.resize((size_t)k);
         S.vals1.resize((size_t)k);
@@ -2009,30 +1895,15 @@ static int search_submit_impl(hipts_bm25_t* bm25, hipts_index_t* index, const in
     if (!S.done) HIPTS_HIP(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
     // queries, weights, offsets and the query vectors travel as ONE packed copy from pinned memory (no bounce buffer, no
     // synchronisation before the kernels); the results come back the same way
-    const size_t off_w = ((size_t)nt * 4 + 15) / 16 * 16;
-    const size_t off_p = off_w + (size_t)nt * 8;
-    const size_t off_v = (off_p + (size_t)(nq + 1) * 4 + 15) / 16 * 16;
-    const size_t in_bytes = off_v + (size_t)nq * index->dim * 4;
-    HIPTS_TRY(S.pin_in.reserve(in_bytes));
-    HIPTS_TRY(bm25->ws_q.reserve(in_bytes));
-    char* hin = S.pin_in.as<char>();
-    if (nt) {
-        memcpy(hin, q_terms, (size_t)nt * 4);
-        memcpy(hin + off_w, q_weights, (size_t)nt * 8);
-    }
-    memcpy(hin + off_p, q_ptr, (size_t)(nq + 1) * 4);
-    memcpy(hin + off_v, q_vectors, (size_t)nq * index->dim * 4);
-    HIPTS_HIP(hipMemcpyAsync(bm25->ws_q.p, hin, in_bytes, hipMemcpyHostToDevice, s));
-    const int32_t* qt = bm25->ws_q.as<int32_t>();
-    const double* qw = reinterpret_cast<const double*>(bm25->ws_q.as<char>() + off_w);
-    const int32_t* qp = reinterpret_cast<const int32_t*>(bm25->ws_q.as<char>() + off_p);
-    const float* qvec = reinterpret_cast<const float*>(bm25->ws_q.as<char>() + off_v);
+    const QueryPack pack = query_pack(nt, nq, index->dim);
+    HIPTS_TRY(S.pin_in.reserve(pack.bytes));
+    HIPTS_TRY(bm25->ws_q.reserve(pack.bytes));
+    const PackedQueries q = pack_queries(pack, S.pin_in.as<char>(), bm25->ws_q.p, q_terms, q_weights, q_ptr, q_vectors, nt, nq, index->dim);
+    HIPTS_HIP(hipMemcpyAsync(bm25->ws_q.p, S.pin_in.p, pack.bytes, hipMemcpyHostToDevice, s));
     HIPTS_TRY(bm25->ws_scores.reserve((size_t)nq * D * 8));
     HIPTS_TRY(bm25->ws_sims.reserve((size_t)nq * D * 4));
-    // Without a caller who wants the combined rows they are never written: the top-k kernel combines on the fly (TopkScores::a;
-    // HIPTS_SEARCH_FUSED_TOPK=0 restores combine_kernel + top-k over the stored rows, for A/B).
-    static const bool fuse_topk = !(getenv("HIPTS_SEARCH_FUSED_TOPK") && atoi(getenv("HIPTS_SEARCH_FUSED_TOPK")) == 0);
-    const bool fused = fuse_topk && final_out_device == nullptr;
+    // Without a caller who wants the combined rows they are never written: the top-k kernel combines on the fly (TopkScores::a)
+    const bool fused = knobs.fused_topk && final_out_device == nullptr;
     double* final_dev = final_out_device;
     if (!final_dev && !fused) {
         HIPTS_TRY(bm25->ws_final.reserve((size_t)nq * D * 8));
@@ -2047,10 +1918,9 @@ static int search_submit_impl(hipts_bm25_t* bm25, hipts_index_t* index, const in
     // BM25 and the index product share no data.  Round 4 measured them on two streams (HIPTS_SEARCH_OVERLAP=1): 396-398 k queries/s either
     // way -- side by side BM25 takes 234-336 us instead of 156-167 and the product 262-363 instead of 233: both fill the wave slots of
     // every CU, so they take turns rather than share.  One stream stays the default.
-    static const bool overlap = getenv("HIPTS_SEARCH_OVERLAP") && atoi(getenv("HIPTS_SEARCH_OVERLAP")) != 0;
-    int parts_grid = 0;          // > 0: the index product left per-workgroup row maxima in ws_parts
+    const SimPlan sim = sim_plan(index->tiled.p != nullptr, D, index->dim, nq, fused, knobs);
     hipStream_t sb = s;
-    if (overlap) {
+    if (knobs.overlap) {
         if (!bm25->side) {
             HIPTS_HIP(hipStreamCreateWithFlags(&bm25->side, hipStreamNonBlocking));
             HIPTS_HIP(hipEventCreateWithFlags(&bm25->ev_in, hipEventDisableTiming));
@@ -2067,21 +1937,21 @@ static int search_submit_impl(hipts_bm25_t* bm25, hipts_index_t* index, const in
         for (int j = 0; j < nt; ++j)
             if (q_terms[j] >= 0 && q_terms[j] < bm25->V) pb += (double)bm25->h_df[q_terms[j]] * 12.0;
         QueryProfScope ps(bm25, sb, QP_BM25, pb + (double)nq * D * 8.0 * 3);
-        HIPTS_TRY(launch_bm25(bm25, qt, qw, qp, nq, bm25->ws_scores.as<double>(), sb, ma));
+        HIPTS_TRY(launch_bm25(bm25, q.qt, q.qw, q.qp, nq, bm25->ws_scores.as<double>(), sb, ma));
     }
-    if (overlap) HIPTS_HIP(hipEventRecord(bm25->ev_bm25, sb));
+    if (knobs.overlap) HIPTS_HIP(hipEventRecord(bm25->ev_bm25, sb));
     {
-        QueryProfScope ps(bm25, s, QP_SIM, (double)sim_index_passes(index->tiled.p != nullptr, index->dim, nq) * D * index->dim * 4.0 + (double)nq * D * 4.0);
-        if (fused && sim_parts_enabled()) HIPTS_TRY(bm25->ws_parts.reserve((size_t)((nq + 255) / 256) * SIMW_MAX_GRID * 256 * sizeof(float)));
-        HIPTS_TRY(launch_sim(index->rows.as<float>(), index->tiled.as<float>(), D, index->dim, qvec, nq, bm25->ws_sims.as<float>(), D, s,
-                             fused && sim_parts_enabled() ? bm25->ws_parts.as<float>() : nullptr, &parts_grid));
+        QueryProfScope ps(bm25, s, QP_SIM, (double)sim.index_passes * D * index->dim * 4.0 + (double)nq * D * 4.0);
+        if (sim.parts_bytes) HIPTS_TRY(bm25->ws_parts.reserve(sim.parts_bytes));
+        HIPTS_TRY(launch_sim(sim, index->rows.as<float>(), index->tiled.as<float>(), D, index->dim, q.qvec, nq, bm25->ws_sims.as<float>(), D, s,
+                             sim.parts_bytes ? bm25->ws_parts.as<float>() : nullptr));
     }
-    if (parts_grid == 0) {       // (otherwise the maxima came out of the product kernel's accumulators: the top-k kernel reduces its workgroups' values)
+    if (sim.parts_grid == 0) {       // (otherwise the maxima came out of the product kernel's accumulators: the top-k kernel reduces its workgroups' values)
         QueryProfScope ps(bm25, s, QP_ROWMAX, (double)nq * D * 4.0);
         rowmax_kernel<float><<<nq, 1024, 0, s>>>(bm25->ws_sims.as<float>(), D, mb);
         HIPTS_LAUNCH_CHECK();
     }
-    if (overlap) HIPTS_HIP(hipStreamWaitEvent(s, bm25->ev_bm25, 0));      // BM25 rows and their maxima are complete
+    if (knobs.overlap) HIPTS_HIP(hipStreamWaitEvent(s, bm25->ev_bm25, 0));      // BM25 rows and their maxima are complete
     if (!fused) {
         QueryProfScope ps(bm25, s, QP_COMBINE, (double)nq * D * 20.0);
         dim3 grid(ceil_div(D, 256), nq);
@@ -2105,15 +1975,12 @@ static int search_submit_impl(hipts_bm25_t* bm25, hipts_index_t* index, const in
             fz.wa = w_bm25;
             fz.wb = (float)w_sim;
             fz.max_a = ma;
-            fz.max_b = mb;
-            if (parts_grid > 0) {
-                fz.max_b = nullptr;
-                fz.max_b_parts = bm25->ws_parts.as<float>();
-                fz.parts = parts_grid;
-            }
+            fz.max_b = sim.parts_grid > 0 ? nullptr : mb;
+            fz.max_b_parts = sim.parts_grid > 0 ? bm25->ws_parts.as<float>() : nullptr;      // the index product left its workgroups' row maxima
+            fz.parts = sim.parts_grid;
             topk_kernel<<<nq, 1024, 0, s>>>(fz, D, kk, oi, ov);
         } else {
-            topk_kernel<<<nq, 1024, 0, s>>>(plain_rows(final_dev), D, kk, oi, ov);
+            topk_kernel<<<nq, 1024, 0, s>>>(TopkScores{final_dev}, D, kk, oi, ov);
         }
         HIPTS_LAUNCH_CHECK();
     }
@@ -2123,7 +1990,7 @@ static int search_submit_impl(hipts_bm25_t* bm25, hipts_index_t* index, const in
     return HIPTS_OK;
 }
 
-static int search_collect_impl(hipts_bm25_t* bm25, int sl, int32_t* ids_out, double* vals_out) {
+int hipts_search_collect(hipts_bm25_t* bm25, int sl, int32_t* ids_out, double* vals_out) {
     HIPTS_REQUIRE(bm25 && ids_out && vals_out && (sl == 0 || sl == 1), "hipts_search_collect: bad arguments");
     hipts_bm25::SearchSlot& S = bm25->slot[sl];
     HIPTS_REQUIRE(S.pending, "hipts_search_collect: slot %d holds no submitted batch", sl);
@@ -2139,16 +2006,7 @@ static int search_collect_impl(hipts_bm25_t* bm25, int sl, int32_t* ids_out, dou
     const int nq = S.nq, kk = S.kk;
     const double* hv = S.pin_out.as<double>();
     const int32_t* hi = reinterpret_cast<const int32_t*>(hv + (size_t)nq * kk);
-    if (kk == k) {
-        memcpy(ids_out, hi, (size_t)nq * k * 4);
-        memcpy(vals_out, hv, (size_t)nq * k * 8);
-    } else {
-        for (int q = 0; q < nq; ++q)
-            for (int i = 0; i < k; ++i) {
-                ids_out[(size_t)q * k + i] = i < kk ? hi[(size_t)q * kk + i] : -1;
-                vals_out[(size_t)q * k + i] = i < kk ? hv[(size_t)q * kk + i] : -INFINITY;
-            }
-    }
+    pad_topk_rows(hi, hv, nq, kk, k, ids_out, vals_out);
     return HIPTS_OK;
 }
 
@@ -2158,16 +2016,12 @@ int hipts_search(hipts_bm25_t* bm25, hipts_index_t* index, const int32_t* q_term
     HIPTS_REQUIRE(bm25 && ids_out && vals_out, "hipts_search: bad arguments");
     HIPTS_REQUIRE(!bm25->slot[0].pending, "hipts_search: a submitted batch waits in slot 0 (hipts_search_collect it first)");
     HIPTS_TRY(search_submit_impl(bm25, index, q_terms, q_weights, q_ptr, q_vectors, nq, w_bm25, w_sim, k, final_out_device, 0, (hipStream_t)stream));
-    return search_collect_impl(bm25, 0, ids_out, vals_out);
+    return hipts_search_collect(bm25, 0, ids_out, vals_out);
 }
 
 int hipts_search_submit(hipts_bm25_t* bm25, hipts_index_t* index, const int32_t* q_terms, const double* q_weights, const int32_t* q_ptr,
                         const float* q_vectors, int nq, double w_bm25, double w_sim, int k, int slot, void* stream) {
     return search_submit_impl(bm25, index, q_terms, q_weights, q_ptr, q_vectors, nq, w_bm25, w_sim, k, nullptr, slot, (hipStream_t)stream);
-}
-
-int hipts_search_collect(hipts_bm25_t* bm25, int slot, int32_t* ids_out, double* vals_out) {
-    return search_collect_impl(bm25, slot, ids_out, vals_out);
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "query_plan.h"
 #include "rank_util.h"
 
 namespace {
@@ -58,7 +59,7 @@ __device__ __forceinline__ void hist_add(uint32_t* hist, uint32_t d, bool active
 constexpr int TOPK_U = 16;
 constexpr int TOPK_SORT_TARGET = 256;
 
-constexpr int S1_BLOCK_CAP = 64;     // candidates one search1_collect_kernel workgroup (1024 documents) may hand on: at least this many (search_one sizes it)
+using hipts::S1_BLOCK_CAP;           // query_plan.h
 constexpr int S1_GATHER_BLOCKS = 1024;  // up to this many workgroups' slots are gathered through an offset table in LDS
 
 #ifdef HIPTS_X_TOPK_STAMPS          // measurement-only build (-DHIPTS_X_TOPK_STAMPS=<workgroup>; tools/topk_stamps.py): wall-clock stamps of that workgroup, 10 ns units
@@ -117,7 +118,7 @@ struct TopkScores {
     float wb = 0.f;
     const double* max_a = nullptr;   // [nq] row maxima (normalise when > 0)
     const float* max_b = nullptr;
-    const float* max_b_parts = nullptr;      // instead of max_b: [query / 256][SIMW_MAX_GRID][256] per-workgroup maxima of sim_mfma_wide_kernel,
+    const float* max_b_parts = nullptr;      // instead of max_b: [query / 256][SIM_PARTS_MAX_GRID][256] (query_plan.h) per-workgroup maxima of sim_mfma_wide_kernel,
     int parts = 0;                           //   `parts` workgroups each
 
     // this workgroup's row; all threads of the workgroup call it (one barrier when the maxima come in parts)
@@ -126,7 +127,7 @@ struct TopkScores {
         if (!a) return TopkRow{v + off, nullptr, nullptr, 0.0, 0.0, 0.f, 0.f};
         float mb;
         if (max_b_parts) {        // the maximum over the product kernel's workgroups (exact: the same value rowmax_kernel finds in the stored row)
-            const float* pp = max_b_parts + (int64_t)(blockIdx.x >> 8) * (256 * 256) + (blockIdx.x & 255);
+            const float* pp = max_b_parts + (int64_t)(blockIdx.x >> 8) * hipts::SIM_PARTS_GROUP_FLOATS + (blockIdx.x & 255);
             mb = block_max<1024>((int)threadIdx.x < parts ? pp[(int64_t)threadIdx.x * 256] : -INFINITY);
         } else {
             mb = max_b[blockIdx.x];

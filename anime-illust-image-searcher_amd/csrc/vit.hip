@@ -19,6 +19,7 @@
 
 #include "vit_internal.h"
 #include "model_host.h"
+#include "prof.h"
 #include "row_ln.h"
 #include "patch_rows.h"
 
@@ -32,8 +33,6 @@ struct Layer {
     // folded LayerNorms (EPI_RESID_XG): W gamma and W beta + b of the GEMMs that consume norm1 / norm2
     DevBuf qkv_u, qkv_c, fc1_u, fc1_c;
 };
-
-
 }  // namespace
 
 enum ProfCat { PC_PATCHIFY = 0, PC_GEMM_PATCH, PC_LAYERNORM, PC_GEMM_QK, PC_GEMM_VT, PC_ATTENTION, PC_GEMM_RESID,
@@ -43,21 +42,12 @@ static const char* const kProfNames[PC_COUNT] = {
     "patchify_kernel", "gemm_kernel<EPI_PATCH>", "layernorm_kernel", "gemm_kernel<EPI_QKV>", "gemm_kernel<EPI_VT>",
     "attn2_kernel", "gemm_kernel<EPI_RESID>", "gemm_kernel<EPI_GELU>", "pool_kernels", "gemm_kernel<EPI_HEAD>", "other"};
 
-struct ProfRec {
-    int cat;
-    hipEvent_t a, b;
-    double flops, bytes;
-};
-
 struct hipts_vit {
     bool prof = false;          // events are recorded during THIS forward call
     int prof_every = 0;         // 0 = off, n = record every n-th forward call (sampling keeps event overhead out of the step time)
     uint32_t prof_mask = 0xffffffffu;      // categories recorded (hipts_vit_profile_select)
     long prof_calls = 0;
-    std::vector<ProfRec> recs;
-    std::vector<hipEvent_t> pool;      // recycled events
-    double acc_ms[PC_COUNT] = {0}, acc_flops[PC_COUNT] = {0}, acc_bytes[PC_COUNT] = {0};
-    int64_t acc_n[PC_COUNT] = {0};
+    EventProfile<PC_COUNT> ep;
     int device = 0;
     hipts_vit_config_t cfg{};
     int grid = 0, tokens = 0, tokens_pad = 0, patch_k = 0;
@@ -429,54 +419,10 @@ int hipts_vit_flops_per_image(const hipts_vit_t* h, double* flops) {
 
 namespace {
 
-struct ProfScope {
-    hipts_vit* h;
-    hipStream_t s;
-    ProfRec r{};
-    bool on;
-    ProfScope(hipts_vit* h_, hipStream_t s_, int cat, double flops, double bytes) : h(h_), s(s_), on(h_->prof && ((h_->prof_mask >> cat) & 1u)) {
-        if (!on) return;
-        auto get = [&]() {
-            hipEvent_t e;
-            if (!h->pool.empty()) {
-                e = h->pool.back();
-                h->pool.pop_back();
-            } else if (hipEventCreate(&e) != hipSuccess) {
-                e = nullptr;
-            }
-            return e;
-        };
-        r.cat = cat;
-        r.flops = flops;
-        r.bytes = bytes;
-        r.a = get();
-        r.b = get();
-        if (r.a) (void)hipEventRecord(r.a, s);
-    }
-    ~ProfScope() {
-        if (!on) return;
-        if (r.b) (void)hipEventRecord(r.b, s);
-        h->recs.push_back(r);
-    }
+// records when this forward call is a sampled one and the category is selected
+struct ProfScope : EventProfile<PC_COUNT>::Scope {
+    ProfScope(hipts_vit* h, hipStream_t s, int cat, double fl, double by) : Scope(h->prof && ((h->prof_mask >> cat) & 1u) ? &h->ep : nullptr, s, cat, fl, by) {}
 };
-
-int prof_resolve(hipts_vit* h) {
-    for (auto& r : h->recs) {
-        if (r.a && r.b) {
-            HIPTS_HIP(hipEventSynchronize(r.b));
-            float ms = 0.f;
-            HIPTS_HIP(hipEventElapsedTime(&ms, r.a, r.b));
-            h->acc_ms[r.cat] += ms;
-            h->acc_n[r.cat] += 1;
-            h->acc_flops[r.cat] += r.flops;
-            h->acc_bytes[r.cat] += r.bytes;
-        }
-        if (r.a) h->pool.push_back(r.a);
-        if (r.b) h->pool.push_back(r.b);
-    }
-    h->recs.clear();
-    return HIPTS_OK;
-}
 
 // The whole kernel sequence for images [i0, i0 + nb) of the current call, on stream s.  Every workspace
 // buffer is indexed by image (rows of M = batch * tokens, or (image, head) blocks), so disjoint image
@@ -839,11 +785,8 @@ int hipts_vit_join(hipts_vit_t* h, void* stream) {
 int hipts_vit_profile_enable(hipts_vit_t* h, int enable) {
     HIPTS_REQUIRE(h, "null handle");
     HIPTS_TRY(use_device(h->device));
-    HIPTS_TRY(prof_resolve(h));
-    for (int i = 0; i < PC_COUNT; ++i) {
-        h->acc_ms[i] = h->acc_flops[i] = h->acc_bytes[i] = 0.0;
-        h->acc_n[i] = 0;
-    }
+    HIPTS_TRY(h->ep.resolve());
+    h->ep.reset();
     h->prof_every = enable > 0 ? enable : 0;
     h->prof_calls = 0;
     h->prof = false;
@@ -860,11 +803,11 @@ int hipts_vit_profile_read(hipts_vit_t* h, int category, double* total_ms, int64
                            double* total_bytes) {
     HIPTS_REQUIRE(h && category >= 0 && category < PC_COUNT, "bad category");
     HIPTS_TRY(use_device(h->device));
-    HIPTS_TRY(prof_resolve(h));
-    if (total_ms) *total_ms = h->acc_ms[category];
-    if (launches) *launches = h->acc_n[category];
-    if (total_flops) *total_flops = h->acc_flops[category];
-    if (total_bytes) *total_bytes = h->acc_bytes[category];
+    HIPTS_TRY(h->ep.resolve());
+    if (total_ms) *total_ms = h->ep.ms[category];
+    if (launches) *launches = h->ep.n[category];
+    if (total_flops) *total_flops = h->ep.flops[category];
+    if (total_bytes) *total_bytes = h->ep.bytes[category];
     return HIPTS_OK;
 }
 

@@ -239,6 +239,38 @@ int hiptsdbg_attention2_stamps(unsigned long long* host, int n);
 /* One-query search path (hipts_search with nq == 1): how many candidates its threshold step collected for the last query and
  * whether the ranking used them (1) or fell through to the exact radix select (0). */
 int hiptsdbg_search1_last(hipts_bm25_t* h, uint32_t* candidates, uint32_t* took_candidate_path);
+/* How the query path would run a call (csrc/query_plan.h: search1_plan() and sim_plan() are the one place these decisions live and the
+ * launchers of csrc/query.hip consume exactly these).  Host only, no GPU call.  knob_bits state the four switches the plans depend on
+ * explicitly, whatever the process's environment says: the default is all four.
+ *
+ * hiptsdbg_search1_plan: hipts_search with one query over D documents, k results.  kk = min(k, D); waves of 64 documents; a group of
+ * the threshold step is gl lanes of a wave (gw == 1) or gw whole waves; `groups` group maxima; bcap candidate slots per collect
+ * workgroup; finish: search1_finish_kernel instead of the combine and collect kernels.  grid_score / blocks2 / blocks3: workgroups of
+ * the score, combine and collect (or finish) kernels.  off_*: byte offsets into the workspace of ws_bytes -- group maxima (u64), candidate
+ * counts and flags (u32 per collect workgroup), keys (u64 [blocks3][bcap]), ids (u32 [blocks3][bcap]), witness records (32 B, two per
+ * score wave; present when finish).  out_bytes of results in pinned memory, the completion flag at off_flag. */
+enum { HIPTSDBG_QUERY_FINISH = 1, HIPTSDBG_QUERY_WIDE = 2, HIPTSDBG_QUERY_TILED = 4, HIPTSDBG_QUERY_PARTS = 8, HIPTSDBG_QUERY_DEFAULT = 15 };
+typedef struct hiptsdbg_search1_plan_t {
+    int64_t waves;
+    int32_t kk, gw, gl, groups, bcap, finish;
+    int32_t grid_score, blocks2, blocks3, reserved;
+    uint64_t off_wmax, off_bcnt, off_bflag, off_bkey, off_bid, off_wit, ws_bytes;
+    uint64_t out_bytes, off_flag;
+} hiptsdbg_search1_plan_t;
+int hiptsdbg_search1_plan(int64_t D, int k, unsigned knob_bits, hiptsdbg_search1_plan_t* out);
+/* hiptsdbg_sim_plan: the index product of nq queries of K floats against D rows (have_tiled: the tile-major copy exists).  wide_passes
+ * launches of sim_mfma_wide_kernel, pass i over queries [256 i, ...): 256 queries in 8 query blocks on wide_grid workgroups, except the
+ * last pass: last_n queries, last_nqb blocks, last_grid workgroups.  Then tail_passes launches of sim_mfma_kernel (tail_tiled: over
+ * the tile-major copy) of up to 32 queries from query tail_q0 on, tail_grid workgroups each.  index_passes: all launches, each one pass
+ * over the index.  parts_bytes (only with want_parts): the buffer the caller reserves for per-workgroup row maxima, one group per 256
+ * queries; parts_grid > 0: every wide pass leaves the maxima of its parts_grid workgroups there; 0: the caller runs rowmax_kernel. */
+typedef struct hiptsdbg_sim_plan_t {
+    int32_t wide_passes, wide_grid, last_n, last_nqb, last_grid;
+    int32_t tail_q0, tail_passes, tail_grid, tail_tiled;
+    int32_t parts_grid, index_passes, reserved;
+    uint64_t parts_bytes;
+} hiptsdbg_sim_plan_t;
+int hiptsdbg_sim_plan(int have_tiled, int64_t D, int K, int nq, int want_parts, unsigned knob_bits, hiptsdbg_sim_plan_t* out);
 /* measurement-only builds (-DHIPTS_X_TOPK_STAMPS=<workgroup>): the 16 wall-clock stamps (10 ns units) of the last batched hipts_topk launch */
 int hiptsdbg_topk_stamps(unsigned long long* host16);
 /* The last hipts_bm25_related call on this handle: the HIP-event time of its count launches (all passes) and how many work items

@@ -286,6 +286,38 @@ def test_search_without_stored_rows_equals_search_with_them(D, V):
         assert vals_b.tobytes() == vals_a.tobytes(), (D, k)
 
 
+@pytest.mark.parametrize("D,nq", [(8192, 288), (8192, 300), (32768, 300)])
+def test_search_of_more_than_256_queries_without_stored_rows_equals_search_with_them(D, nq):
+    """The same comparison for batches the index product takes in several passes (csrc/query_plan.h sim_plan): 288 queries are one pass
+    of 256 through the wide kernel and 32 through the 32-query kernel, 300 queries two wide passes.  Over 8192 documents the two passes'
+    grids differ (256 and 64 workgroups), so the products' row maxima come from rowmax_kernel; over 32768 both run 256 workgroups and
+    the top-k kernel takes the maxima from the per-workgroup parts of two query groups.  Both arms share the passes, so the batch is
+    also held against the same queries sent as two one-pass batches."""
+    import torch
+    from hiptagsearch import synth
+    from hiptagsearch.bm25 import BM25Index
+    from hiptagsearch.index import Similarity
+    from hiptagsearch.search import SearchEngine
+    V, dim, k = 800, 32, 100
+    ptr, terms = synth.tag_corpus(D, V, seed=7)
+    bm = BM25Index(ptr, terms, V)
+    index = Similarity("idx", None, dim, capacity=D)
+    index.add_matrix(synth.index_vectors(D, dim, seed=8))
+    eng = SearchEngine(None, index, {}, bm, [])
+    qs = [dict(q) for q in synth.queries(nq, V, seed=9, head=300)]
+    qv = np.random.default_rng(3).standard_normal((nq, dim)).astype(np.float32)
+    final_dev = torch.empty((nq, D), dtype=torch.float64, device="cuda")
+    ids_a, vals_a = eng.score_topk(qs, qv, k, final_out=final_dev)
+    ids_b, vals_b = eng.score_topk(qs, qv, k)
+    assert ids_a.shape == (nq, k)
+    np.testing.assert_array_equal(ids_b, ids_a)
+    assert vals_b.tobytes() == vals_a.tobytes()
+    # a query's result does not depend on its batch: the first 256 and the rest as batches of their own, one pass each
+    ids_c, vals_c = zip(eng.score_topk(qs[:256], qv[:256], k), eng.score_topk(qs[256:], qv[256:], k))
+    np.testing.assert_array_equal(np.concatenate(ids_c), ids_a)
+    assert np.concatenate(vals_c).tobytes() == vals_a.tobytes()
+
+
 def test_search_one_query_path_is_bit_equal_to_the_batched_path(corpus20k):
     """hipts_search with nq == 1 takes the one-query path (thread-per-document BM25 in the reference's document-major form,
     fmaf-chain index product, sampled threshold + candidate ranking): ids, scores and the combined score row must equal the
