@@ -1,6 +1,7 @@
 // rows_dbg.hip -- hiptsdbg_row_ln, hiptsdbg_pool_ln, hiptsdbg_patch_gather (include/hip_tagsearch_debug.h): one launch of a kernel of
 // row_ln.h / patch_rows.h on caller-supplied operands with every output buffer pre-filled, guarded and copied back whole.  Test aid, host
-// code only: it decides nothing about a launch.
+// code only: it decides nothing about a launch.  hiptsdbg_rowstat and hiptsdbg_fold_ln do the same for the folded LayerNorm's two kernels
+// of vit.hip, through that file's own launchers (vit_internal.h): those run vit.o's copy.
 //
 // row_ln.h and patch_rows.h keep everything in an anonymous namespace, so this object compiles its OWN copy of the templates, from the
 // same source with the same flags as vit.o, eva.o, ccip.o, convnext.o and swinv2.o compile theirs.  These entries therefore test the
@@ -164,6 +165,43 @@ extern "C" int hiptsdbg_pool_ln(const float* x, uint64_t x_bytes, const float* g
     }
     HIPTS_HIP(hipDeviceSynchronize());
     return fetch(out, od, out_bytes, who);
+}
+
+extern "C" int hiptsdbg_rowstat(const float* part, uint64_t part_bytes, int M, int stride, int blocks, int D, float eps, int fill, float* out,
+                               uint64_t out_bytes) {
+    using namespace hipts;
+    const char* who = "hiptsdbg_rowstat";
+    HIPTS_REQUIRE(part && out, "%s: null argument", who);
+    HIPTS_REQUIRE(M >= 1 && M <= (1 << 22) && stride >= M && blocks >= 1 && blocks <= 64 && D >= 1, "%s: unsupported shape", who);
+    HIPTS_REQUIRE(part_bytes >= (uint64_t)blocks * stride * 8, "%s: the partial pairs do not cover [blocks][stride]", who);
+    HIPTS_TRY(use_device(0));
+    DevBuf pd, od;
+    HIPTS_TRY(guarded(od, out_bytes, (uint64_t)M * 8, fill, who, "output"));
+    HIPTS_TRY(put(pd, part, part_bytes));
+    HIPTS_TRY(launch_rowstat(pd.as<float>(), od.as<float>(), M, stride, blocks, D, eps, nullptr));
+    HIPTS_HIP(hipDeviceSynchronize());
+    return fetch(out, od, out_bytes, who);
+}
+
+extern "C" int hiptsdbg_fold_ln(const uint16_t* w16, int f16, const float* gamma, const float* beta, const float* bias, int N, int K, int fill, float* u,
+                                float* c, uint64_t out_bytes) {
+    using namespace hipts;
+    const char* who = "hiptsdbg_fold_ln";
+    HIPTS_REQUIRE(w16 && gamma && u && c, "%s: null argument", who);
+    HIPTS_REQUIRE(N >= 1 && N <= (1 << 16) && K >= 1 && K <= (1 << 16), "%s: unsupported shape", who);
+    HIPTS_TRY(use_device(0));
+    DevBuf wd, gd, bd, bi, ud, cd;
+    HIPTS_TRY(guarded(ud, out_bytes, (uint64_t)N * 4, fill, who, "u"));
+    HIPTS_TRY(guarded(cd, out_bytes, (uint64_t)N * 4, fill, who, "c"));
+    HIPTS_TRY(put(wd, w16, (size_t)N * K * 2));
+    HIPTS_TRY(put(gd, gamma, (size_t)K * 4));
+    if (beta) HIPTS_TRY(put(bd, beta, (size_t)K * 4));
+    if (bias) HIPTS_TRY(put(bi, bias, (size_t)N * 4));
+    HIPTS_TRY(launch_fold_ln(wd.as<bf16_t>(), f16 != 0, gd.as<float>(), beta ? bd.as<float>() : nullptr, bias ? bi.as<float>() : nullptr, ud.as<float>(),
+                             cd.as<float>(), N, K, nullptr));
+    HIPTS_HIP(hipDeviceSynchronize());
+    HIPTS_TRY(fetch(u, ud, out_bytes, who));
+    return fetch(c, cd, out_bytes, who);
 }
 
 extern "C" int hiptsdbg_patch_gather(int pixel, int window, int f16, const void* images, uint64_t image_bytes, const float* lut, int batch, int S,

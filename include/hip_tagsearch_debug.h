@@ -179,6 +179,16 @@ int hiptsdbg_row_ln(const hiptsdbg_row_ln_case_t* in, hiptsdbg_rows_out_t* out);
  * otherwise PooledHiLo, out 16-bit patterns [batch][hi(C) | lo(C)].  out_bytes >= 4 batch C either way. */
 int hiptsdbg_pool_ln(const float* x, uint64_t x_bytes, const float* g, const float* b, int batch, int T, int C, int count, int blk, float eps,
                      int hilo, int f16, int fill, void* out, uint64_t out_bytes);
+/* The two kernels of the folded LayerNorm that no GEMM launch contains (csrc/vit.hip; tests/test_gpu_ln_fold.py), ONE launch each through
+ * launch_rowstat / launch_fold_ln, same conventions: the entry fills each whole device output buffer with `fill`, launches once and copies it
+ * back whole; a buffer smaller than the launch's extent is refused.
+ * hiptsdbg_rowstat: out[m] = (rstd, rstd * mean) of row m < M from part [blocks][stride] pairs (sum, sum of squares) over D columns in all;
+ * stride >= M, blocks <= 64, part_bytes >= 8 blocks stride, out_bytes >= 8 M.
+ * hiptsdbg_fold_ln: u[n] = sum_k W[n][k] gamma[k], c[n] = sum_k W[n][k] beta[k] + bias[n] from the 16-bit patterns w16 [N][K] (f16: IEEE half);
+ * gamma, beta [K], bias [N]; beta and bias may be null (absent).  u and c have out_bytes each, out_bytes >= 4 N. */
+int hiptsdbg_rowstat(const float* part, uint64_t part_bytes, int M, int stride, int blocks, int D, float eps, int fill, float* out, uint64_t out_bytes);
+int hiptsdbg_fold_ln(const uint16_t* w16, int f16, const float* gamma, const float* beta, const float* bias, int N, int K, int fill, float* u, float* c,
+                     uint64_t out_bytes);
 /* patch_gather_kernel once with a (pixel, window) tuple a forward launches -- (PIX_U8_AFFINE, WIN_PATCH), (PIX_U8_TABLE, WIN_4X4),
  * (PIX_F32_FLIP, WIN_PATCH), (PIX_F32_FLIP, WIN_4X4), (PIX_F32, WIN_7X7) -- or, with PIX_U8_RAW and WIN_PATCH, patchify_u8_kernel.
  * images: uint8 [batch][S][S][3] or float32 [batch][3][S][S]; lut: float32 [3][256] (PIX_U8_TABLE).  WIN_PATCH: P x P patches, S % P == 0,
