@@ -25,6 +25,7 @@
 
 #include "gemm_plan.h"
 #include "vit_internal.h"
+#include "dbg_buf.h"
 #include "model_host.h"
 #include "convnet.h"
 
@@ -168,6 +169,14 @@ __global__ __launch_bounds__(256) void ds_im2col_kernel(const bf16_t* __restrict
     *reinterpret_cast<uint4*>(col + (m * 9 + tap) * C + g * 8) = v;
 }
 
+// its launch shape, shared by the forward and hiptsdbg_ccip_ds_im2col.  M: the rows of col, batch * (H / 2)^2
+int launch_ds_im2col(const bf16_t* xn, bf16_t* col, int batch, int M, int H, int C, hipStream_t s) {
+    const int64_t chunks = (int64_t)M * 9 * (C / 8);
+    ds_im2col_kernel<<<ceil_div(chunks, 256), 256, 0, s>>>(xn, col, batch, H, C);
+    HIPTS_LAUNCH_CHECK();
+    return HIPTS_OK;
+}
+
 
 // y = act(A W^T) helpers over the shared persistent GEMM
 int gemm(GemmEpilogue epi, GemmArgs& g, hipStream_t s) { return launch_gemm(epi, g, s); }
@@ -269,9 +278,7 @@ int ccip_run_images(hipts_ccip* h, const void* in_dev, bool is_u8, int i0, int b
             const Stage& Pv = h->st[si - 1];
             if (!xn_ready) HIPTS_TRY(layernorm_xn(St.ds_norm.as<float>(), (int64_t)batch * Pv.T, Pv.C));
             xn_ready = false;
-            const int64_t chunks = (int64_t)M * 9 * (Pv.C / 8);
-            ds_im2col_kernel<<<ceil_div(chunks, 256), 256, 0, s>>>(xn, col, batch, Pv.H, Pv.C);
-            HIPTS_LAUNCH_CHECK();
+            HIPTS_TRY(launch_ds_im2col(xn, col, batch, M, Pv.H, Pv.C, s));
             g = gemm_args(f16, shared_chip);
             g.A = col; g.W = St.ds_w.as<bf16_t>(); g.M = M; g.N = C; g.K = 9 * Pv.C;
             g.bias = St.ds_b.as<float>(); g.out_f32 = x;
@@ -729,6 +736,24 @@ int hiptsdbg_ccip_stem_u8(const uint8_t* images, const float* lut, int batch, in
     HIPTS_HIP(hipDeviceSynchronize());
     HIPTS_HIP(hipMemcpy(a0, ad.p, a0_bytes, hipMemcpyDeviceToHost));
     return HIPTS_OK;
+}
+
+// Debug / test entry (tests/test_gpu_tokens.py): ds_im2col_kernel once, launched as the forward launches it, col filled with `fill` before
+// and copied back whole.
+int hiptsdbg_ccip_ds_im2col(const uint16_t* xn, uint64_t xn_bytes, int batch, int H, int C, int fill, uint16_t* col, uint64_t col_bytes) {
+    const char* who = "hiptsdbg_ccip_ds_im2col";
+    HIPTS_REQUIRE(xn && col, "%s: null argument", who);
+    HIPTS_REQUIRE(batch >= 1 && batch <= 4096 && H >= 2 && H <= 1024 && H % 2 == 0, "%s: H=%d must be even (batch %d)", who, H, batch);
+    HIPTS_REQUIRE(C >= 8 && C % 8 == 0 && C <= 4096, "%s: C=%d must be a multiple of 8", who, C);
+    HIPTS_REQUIRE(xn_bytes >= (uint64_t)batch * H * H * C * 2, "%s: xn does not cover the launch", who);
+    HIPTS_TRY(use_device(0));
+    const int M = batch * (H / 2) * (H / 2);
+    DevBuf xd, cd;
+    HIPTS_TRY(dbg_guarded(cd, col_bytes, (uint64_t)M * 9 * C * 2, fill, who, "col"));
+    HIPTS_TRY(dbg_put(xd, xn, xn_bytes));
+    HIPTS_TRY(launch_ds_im2col(xd.as<bf16_t>(), cd.as<bf16_t>(), batch, M, H, C, nullptr));
+    HIPTS_HIP(hipDeviceSynchronize());
+    return dbg_fetch(col, cd, col_bytes, who);
 }
 
 }  // extern "C"

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "vit_internal.h"
+#include "dbg_buf.h"
 #include "model_host.h"
 #include "convnet.h"
 
@@ -77,6 +78,12 @@ __global__ __launch_bounds__(256) void cnx_cast_kernel(const float* __restrict__
     if (i >= n4) return;
     const float4 v = reinterpret_cast<const float4*>(x)[i];
     reinterpret_cast<bf16x4*>(xh)[i] = pack4<F16>(v.x, v.y, v.z, v.w);
+}
+
+// its launch shape, shared by the forward and hiptsdbg_convnext_cast
+int launch_cnx_cast(bool f16, const float* x, bf16_t* xh, int64_t n4, hipStream_t s) {
+    HIPTS_LAUNCH_F16(f16, cnx_cast_kernel, ceil_div(n4, 256), 256, 0, s, x, xh, n4);
+    return HIPTS_OK;
 }
 
 // The kernel sequence for images [i0, i0 + batch) on stream s.  stop_stage >= 0 (debug entry): return after that stage's last block,
@@ -127,7 +134,7 @@ int cnx_run_images(hipts_convnext* h, const void* in_dev, bool is_u8, int i0, in
             g.bias = St.ds_b.as<float>(); g.out_f32 = x;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
             const int64_t n4 = (int64_t)M * C / 4;
-            HIPTS_LAUNCH_F16(f16, cnx_cast_kernel, ceil_div(n4, 256), 256, 0, s, x, xh, n4);
+            HIPTS_TRY(launch_cnx_cast(f16, x, xh, n4, s));
         }
         for (CnxBlock& B : St.blocks) {
             // depthwise 7x7 (no bias) of the 16-bit copy of x
@@ -378,6 +385,22 @@ int hiptsdbg_convnext_stream(hipts_convnext_t* h, const float* x_host, int batch
     // (one run over all the images: their rows are contiguous, [batch * H * H][C])
     HIPTS_HIP(hipMemcpy(out_host, h->x.p, (size_t)batch * h->st[stage].T * h->st[stage].C * 4, hipMemcpyDeviceToHost));
     return HIPTS_OK;
+}
+
+// Debug / test entry (tests/test_gpu_tokens.py): cnx_cast_kernel once on n4 float4, launched as the forward launches it, xh filled with
+// `fill` before and copied back whole.
+int hiptsdbg_convnext_cast(const float* x, uint64_t x_bytes, int64_t n4, int f16, int fill, uint16_t* xh, uint64_t xh_bytes) {
+    const char* who = "hiptsdbg_convnext_cast";
+    HIPTS_REQUIRE(x && xh, "%s: null argument", who);
+    HIPTS_REQUIRE(n4 >= 1 && n4 <= (1 << 26), "%s: n4=%lld", who, (long long)n4);
+    HIPTS_REQUIRE(x_bytes >= (uint64_t)n4 * 16, "%s: x does not cover the launch", who);
+    HIPTS_TRY(use_device(0));
+    DevBuf xd, hd;
+    HIPTS_TRY(dbg_guarded(hd, xh_bytes, (uint64_t)n4 * 8, fill, who, "16-bit"));
+    HIPTS_TRY(dbg_put(xd, x, x_bytes));
+    HIPTS_TRY(launch_cnx_cast(f16 != 0, xd.as<float>(), hd.as<bf16_t>(), n4, nullptr));
+    HIPTS_HIP(hipDeviceSynchronize());
+    return dbg_fetch(xh, hd, xh_bytes, who);
 }
 
 }  // extern "C"

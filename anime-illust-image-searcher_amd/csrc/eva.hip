@@ -14,13 +14,19 @@
 // inside a 1088-token padded layout.  An image owns TS = 1032 rows of the token matrices (1025 rounded up to 8):
 // the 7 spare rows are zero-initialised, stay finite and are never read as keys (masked) or pooled.
 // First version of this model: RoPE and SwiGLU-product + LayerNorm are separate HBM-bound kernels.
+// Tested one launch at a time: eva_assemble_kernel (row-major and the blocked copy) and eva_colsum_kernel through hiptsdbg_eva_assemble /
+// hiptsdbg_eva_colsum at the end of this file (tests/test_gpu_tokens.py: bit for bit; the column sums also chained into pool_ln_kernel
+// against float64), the GEMM epilogues, LayerNorms, patch gather and attention through their own entries (tests/test_gpu_gemm_epi.py,
+// test_gpu_rows.py, test_gpu_ln_fold.py, test_gpu_attention_exact.py), the whole forward against oracle/eva.py (tests/test_gpu_eva.py).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <string>
 #include <vector>
 
+#include "../../include/hip_tagsearch_debug.h"
 #include "vit_internal.h"
+#include "dbg_buf.h"
 #include "model_host.h"
 #include "row_ln.h"
 #include "patch_rows.h"
@@ -106,6 +112,20 @@ __global__ __launch_bounds__(256) void eva_colsum_kernel(const float* __restrict
     reinterpret_cast<float4*>(part + ((int64_t)b * POOL_SPLITS + split) * D)[tid] = acc;
 }
 
+// The two kernels' launch shapes, shared by the forward and the debug entries (hiptsdbg_eva_assemble, hiptsdbg_eva_colsum)
+int launch_eva_assemble(const float* tmp, const float* cls, const float* pos, float* x, int batch, int np, int TS, int D, float* xblk, hipStream_t s) {
+    const int64_t tot4 = (int64_t)batch * TS * (D / 4);
+    eva_assemble_kernel<<<ceil_div(tot4, 256), 256, 0, s>>>(tmp, cls, pos, x, batch, np, TS, D, xblk);
+    HIPTS_LAUNCH_CHECK();
+    return HIPTS_OK;
+}
+
+int launch_eva_colsum(const float* x, float* part, int batch, int np, int TS, int D, hipStream_t s) {
+    eva_colsum_kernel<<<dim3(POOL_SPLITS, batch), 256, 0, s>>>(x, part, np, TS, D);
+    HIPTS_LAUNCH_CHECK();
+    return HIPTS_OK;
+}
+
 // rows x cols float block -> 16-bit operand bits at row offset `row0` of a [*, ld] matrix that was allocated zeroed
 int put_rows16(DevBuf& buf, const float* data, int rows, int cols, int row0, int ld, bool f16) {
     std::vector<uint16_t> h((size_t)rows * ld, 0);
@@ -165,9 +185,7 @@ int eva_run_images(hipts_eva* h, const void* in_dev, bool is_u8, int i0, int bat
         g.A = a0_p; g.W = h->patch_w.as<bf16_t>(); g.M = batch * np; g.N = D; g.K = 2 * h->PK;
         g.bias = h->patch_b.as<float>(); g.out_f32 = tmp_p; g.pos = h->pos.as<float>() + D; g.tokens = np; g.qscale = 1.0f;
         HIPTS_TRY(launch_gemm(EPI_PATCH, g, s));
-        const int64_t tot4 = (int64_t)batch * TS * (D / 4);
-        eva_assemble_kernel<<<ceil_div(tot4, 256), 256, 0, s>>>(tmp_p, h->cls.as<float>(), h->pos.as<float>(), x0, batch, np, TS, D, xb ? x : nullptr);
-        HIPTS_LAUNCH_CHECK();
+        HIPTS_TRY(launch_eva_assemble(tmp_p, h->cls.as<float>(), h->pos.as<float>(), x0, batch, np, TS, D, xb ? x : nullptr, s));
     }
     // pre-LayerNorms folded into the neighbouring GEMM epilogues, as in the ViT forward: the residual GEMM writes gamma * x (16-bit)
     // and the per-tile row sums of x; the consumer finishes the statistics per tile and applies rstd / mean / beta
@@ -233,7 +251,7 @@ int eva_run_images(hipts_eva* h, const void* in_dev, bool is_u8, int i0, int bat
         }
     }
     float* part_p = h->pool_part.as<float>() + (size_t)i0 * POOL_SPLITS * D;
-    eva_colsum_kernel<<<dim3(POOL_SPLITS, batch), 256, 0, s>>>(xb ? x_rm : x, part_p, np, TS, D);
+    HIPTS_TRY(launch_eva_colsum(xb ? x_rm : x, part_p, batch, np, TS, D, s));
     // pooled2 = hi | lo of fc_norm(mean over the patch tokens): the POOL_SPLITS partial rows summed, divided by the np tokens they cover
     HIPTS_LAUNCH_F16(f16, pool_ln_kernel, batch, 1024, 0, s, part_p, h->fcn_g.as<float>(), h->fcn_b.as<float>(), PooledHiLo{pooled2_p}, POOL_SPLITS, D,
                      c.ln_eps, 0, np);
@@ -493,6 +511,45 @@ int hipts_eva_flops_per_image(const hipts_eva_t* h, double* flops) {
     f += 2.0 * D * c.num_classes;
     *flops = f;
     return HIPTS_OK;
+}
+
+// Debug / test entries (include/hip_tagsearch_debug.h; tests/test_gpu_tokens.py): eva_assemble_kernel and eva_colsum_kernel once each,
+// launched as the forward launches them, every output filled with `fill` before and copied back whole.
+int hiptsdbg_eva_assemble(const float* tmp, uint64_t tmp_bytes, const float* cls, const float* pos, int batch, int np, int TS, int D, int blocked, int fill,
+                          float* x, uint64_t x_bytes, float* xblk, uint64_t xblk_bytes) {
+    const char* who = "hiptsdbg_eva_assemble";
+    HIPTS_REQUIRE(tmp && cls && pos && x && (xblk || xblk_bytes == 0), "%s: null argument", who);
+    HIPTS_REQUIRE(batch >= 1 && batch <= 4096 && np >= 1 && np <= (1 << 16) && TS >= np + 1 && TS <= (1 << 16), "%s: unsupported shape", who);
+    HIPTS_REQUIRE(D >= 4 && D % 4 == 0 && D <= 4096, "%s: D=%d must be a multiple of 4", who, D);
+    HIPTS_REQUIRE(!blocked || D % 16 == 0, "%s: the blocked copy needs D %% 16 == 0", who);
+    HIPTS_REQUIRE(tmp_bytes >= (uint64_t)batch * np * D * 4, "%s: tmp does not cover the launch", who);
+    HIPTS_TRY(use_device(0));
+    const uint64_t M = (uint64_t)batch * TS;
+    DevBuf td, cd, pd, xd, bd;
+    HIPTS_TRY(dbg_guarded(xd, x_bytes, M * D * 4, fill, who, "x"));
+    HIPTS_TRY(dbg_guarded(bd, xblk_bytes, blocked ? (M + 15) / 16 * 16 * D * 4 : 0, fill, who, "blocked"));      // the last 16-row block may be ragged
+    HIPTS_TRY(dbg_put(td, tmp, tmp_bytes));
+    HIPTS_TRY(dbg_put(cd, cls, (size_t)D * 4));
+    HIPTS_TRY(dbg_put(pd, pos, (size_t)D * 4));
+    HIPTS_TRY(launch_eva_assemble(td.as<float>(), cd.as<float>(), pd.as<float>(), xd.as<float>(), batch, np, TS, D, blocked ? bd.as<float>() : nullptr, nullptr));
+    HIPTS_HIP(hipDeviceSynchronize());
+    HIPTS_TRY(dbg_fetch(x, xd, x_bytes, who));
+    return dbg_fetch(xblk, bd, xblk_bytes, who);
+}
+
+int hiptsdbg_eva_colsum(const float* x, uint64_t x_bytes, int batch, int np, int TS, int D, int fill, float* part, uint64_t part_bytes) {
+    const char* who = "hiptsdbg_eva_colsum";
+    HIPTS_REQUIRE(x && part, "%s: null argument", who);
+    HIPTS_REQUIRE(batch >= 1 && batch <= 4096 && np >= 1 && np <= (1 << 16) && TS >= np + 1 && TS <= (1 << 16), "%s: unsupported shape", who);
+    HIPTS_REQUIRE(D >= 4 && D % 4 == 0 && D <= 1024, "%s: D=%d must be a multiple of 4, at most 1024", who, D);
+    HIPTS_REQUIRE(x_bytes >= (uint64_t)batch * TS * D * 4, "%s: x does not cover the launch", who);
+    HIPTS_TRY(use_device(0));
+    DevBuf xd, pd;
+    HIPTS_TRY(dbg_guarded(pd, part_bytes, (uint64_t)batch * POOL_SPLITS * D * 4, fill, who, "partial"));
+    HIPTS_TRY(dbg_put(xd, x, x_bytes));
+    HIPTS_TRY(launch_eva_colsum(xd.as<float>(), pd.as<float>(), batch, np, TS, D, nullptr));
+    HIPTS_HIP(hipDeviceSynchronize());
+    return dbg_fetch(part, pd, part_bytes, who);
 }
 
 }  // extern "C"

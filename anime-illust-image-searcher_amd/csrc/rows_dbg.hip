@@ -7,34 +7,13 @@
 // same source with the same flags as vit.o, eva.o, ccip.o, convnext.o and swinv2.o compile theirs.  These entries therefore test the
 // source; the forwards' own tests (parity, batch invariance, u8 == f32 inputs) remain the check on each object's copy.
 #include "../../include/hip_tagsearch_debug.h"
+#include "dbg_buf.h"
 #include "model_host.h"
 #include "patch_rows.h"
 #include "row_ln.h"
 
 namespace hipts {
 namespace {
-
-// a device buffer of `bytes` filled with `fill`; refused when smaller than `need`
-int guarded(DevBuf& buf, uint64_t bytes, uint64_t need, int fill, const char* who, const char* what) {
-    HIPTS_REQUIRE(bytes >= need, "%s: the %s buffer has %llu bytes, the launch's extent is %llu", who, what, (unsigned long long)bytes,
-                  (unsigned long long)need);
-    if (bytes == 0) return HIPTS_OK;
-    HIPTS_TRY(buf.alloc(bytes));
-    HIPTS_HIP(hipMemset(buf.p, fill & 0xff, bytes));
-    return HIPTS_OK;
-}
-
-int fetch(void* host, const DevBuf& buf, uint64_t bytes, const char* who) {
-    if (bytes == 0) return HIPTS_OK;
-    HIPTS_REQUIRE(host, "%s: an output buffer has a size but no host pointer", who);
-    HIPTS_HIP(hipMemcpy(host, buf.p, bytes, hipMemcpyDeviceToHost));
-    return HIPTS_OK;
-}
-
-int put(DevBuf& buf, const void* host, size_t bytes) {
-    HIPTS_TRY(buf.alloc(bytes));
-    return upload(buf.p, host, bytes);
-}
 
 // the (source, affine, sink) tuples the forwards launch, in the order of the header's list
 enum RowLnTuple { RL_OPT_16, RL_BLOCKED_16, RL_INPLACE, RL_F32_AND_16, RL_PATCH2X2, RL_16BIAS_16, RL_ADD_HILO, RL_F32, RL_COUNT };
@@ -90,13 +69,13 @@ extern "C" int hiptsdbg_row_ln(const hiptsdbg_row_ln_case_t* in, hiptsdbg_rows_o
     }
     HIPTS_REQUIRE(in->x_init_bytes <= out->f32_bytes && (in->x_init_bytes == 0 || in->x_init), "%s: x_init does not fit the float32 buffer", who);
     DevBuf f32, o16, src, bias, gv, bv;
-    HIPTS_TRY(guarded(f32, out->f32_bytes, need_f32, in->fill, who, "float32"));
-    HIPTS_TRY(guarded(o16, out->o16_bytes, need_16, in->fill, who, "16-bit"));
+    HIPTS_TRY(dbg_guarded(f32, out->f32_bytes, need_f32, in->fill, who, "float32"));
+    HIPTS_TRY(dbg_guarded(o16, out->o16_bytes, need_16, in->fill, who, "16-bit"));
     if (in->x_init_bytes) HIPTS_TRY(upload(f32.p, in->x_init, in->x_init_bytes));
-    if (!in_place) HIPTS_TRY(put(src, in->in, in->in_bytes));
-    if (in->bias) HIPTS_TRY(put(bias, in->bias, (size_t)D * 4));
-    HIPTS_TRY(put(gv, in->g, (size_t)D * 4));
-    if (in->b) HIPTS_TRY(put(bv, in->b, (size_t)D * 4));
+    if (!in_place) HIPTS_TRY(dbg_put(src, in->in, in->in_bytes));
+    if (in->bias) HIPTS_TRY(dbg_put(bias, in->bias, (size_t)D * 4));
+    HIPTS_TRY(dbg_put(gv, in->g, (size_t)D * 4));
+    if (in->b) HIPTS_TRY(dbg_put(bv, in->b, (size_t)D * 4));
 
     float* x = f32.as<float>();
     bf16_t* h = o16.as<bf16_t>();
@@ -135,8 +114,8 @@ extern "C" int hiptsdbg_row_ln(const hiptsdbg_row_ln_case_t* in, hiptsdbg_rows_o
         break;
     }
     HIPTS_HIP(hipDeviceSynchronize());
-    HIPTS_TRY(fetch(out->f32, f32, out->f32_bytes, who));
-    HIPTS_TRY(fetch(out->o16, o16, out->o16_bytes, who));
+    HIPTS_TRY(dbg_fetch(out->f32, f32, out->f32_bytes, who));
+    HIPTS_TRY(dbg_fetch(out->o16, o16, out->o16_bytes, who));
     return HIPTS_OK;
 }
 
@@ -151,10 +130,10 @@ extern "C" int hiptsdbg_pool_ln(const float* x, uint64_t x_bytes, const float* g
     HIPTS_REQUIRE(x_bytes >= (uint64_t)batch * T * C * 4, "%s: x does not cover the launch", who);
     HIPTS_TRY(use_device(0));
     DevBuf xd, gd, bd, od;
-    HIPTS_TRY(guarded(od, out_bytes, (uint64_t)batch * C * 4, fill, who, "output"));
-    HIPTS_TRY(put(xd, x, x_bytes));
-    HIPTS_TRY(put(gd, g, (size_t)C * 4));
-    HIPTS_TRY(put(bd, b, (size_t)C * 4));
+    HIPTS_TRY(dbg_guarded(od, out_bytes, (uint64_t)batch * C * 4, fill, who, "output"));
+    HIPTS_TRY(dbg_put(xd, x, x_bytes));
+    HIPTS_TRY(dbg_put(gd, g, (size_t)C * 4));
+    HIPTS_TRY(dbg_put(bd, b, (size_t)C * 4));
     if (hilo) {
         HIPTS_LAUNCH_F16(f16 != 0, pool_ln_kernel, batch, 1024, 0, nullptr, xd.as<float>(), gd.as<float>(), bd.as<float>(), PooledHiLo{od.as<bf16_t>()}, T, C,
                          eps, blk ? 1 : 0, count);
@@ -164,7 +143,7 @@ extern "C" int hiptsdbg_pool_ln(const float* x, uint64_t x_bytes, const float* g
         HIPTS_LAUNCH_CHECK();
     }
     HIPTS_HIP(hipDeviceSynchronize());
-    return fetch(out, od, out_bytes, who);
+    return dbg_fetch(out, od, out_bytes, who);
 }
 
 extern "C" int hiptsdbg_rowstat(const float* part, uint64_t part_bytes, int M, int stride, int blocks, int D, float eps, int fill, float* out,
@@ -176,11 +155,11 @@ extern "C" int hiptsdbg_rowstat(const float* part, uint64_t part_bytes, int M, i
     HIPTS_REQUIRE(part_bytes >= (uint64_t)blocks * stride * 8, "%s: the partial pairs do not cover [blocks][stride]", who);
     HIPTS_TRY(use_device(0));
     DevBuf pd, od;
-    HIPTS_TRY(guarded(od, out_bytes, (uint64_t)M * 8, fill, who, "output"));
-    HIPTS_TRY(put(pd, part, part_bytes));
+    HIPTS_TRY(dbg_guarded(od, out_bytes, (uint64_t)M * 8, fill, who, "output"));
+    HIPTS_TRY(dbg_put(pd, part, part_bytes));
     HIPTS_TRY(launch_rowstat(pd.as<float>(), od.as<float>(), M, stride, blocks, D, eps, nullptr));
     HIPTS_HIP(hipDeviceSynchronize());
-    return fetch(out, od, out_bytes, who);
+    return dbg_fetch(out, od, out_bytes, who);
 }
 
 extern "C" int hiptsdbg_fold_ln(const uint16_t* w16, int f16, const float* gamma, const float* beta, const float* bias, int N, int K, int fill, float* u,
@@ -191,17 +170,17 @@ extern "C" int hiptsdbg_fold_ln(const uint16_t* w16, int f16, const float* gamma
     HIPTS_REQUIRE(N >= 1 && N <= (1 << 16) && K >= 1 && K <= (1 << 16), "%s: unsupported shape", who);
     HIPTS_TRY(use_device(0));
     DevBuf wd, gd, bd, bi, ud, cd;
-    HIPTS_TRY(guarded(ud, out_bytes, (uint64_t)N * 4, fill, who, "u"));
-    HIPTS_TRY(guarded(cd, out_bytes, (uint64_t)N * 4, fill, who, "c"));
-    HIPTS_TRY(put(wd, w16, (size_t)N * K * 2));
-    HIPTS_TRY(put(gd, gamma, (size_t)K * 4));
-    if (beta) HIPTS_TRY(put(bd, beta, (size_t)K * 4));
-    if (bias) HIPTS_TRY(put(bi, bias, (size_t)N * 4));
+    HIPTS_TRY(dbg_guarded(ud, out_bytes, (uint64_t)N * 4, fill, who, "u"));
+    HIPTS_TRY(dbg_guarded(cd, out_bytes, (uint64_t)N * 4, fill, who, "c"));
+    HIPTS_TRY(dbg_put(wd, w16, (size_t)N * K * 2));
+    HIPTS_TRY(dbg_put(gd, gamma, (size_t)K * 4));
+    if (beta) HIPTS_TRY(dbg_put(bd, beta, (size_t)K * 4));
+    if (bias) HIPTS_TRY(dbg_put(bi, bias, (size_t)N * 4));
     HIPTS_TRY(launch_fold_ln(wd.as<bf16_t>(), f16 != 0, gd.as<float>(), beta ? bd.as<float>() : nullptr, bias ? bi.as<float>() : nullptr, ud.as<float>(),
                              cd.as<float>(), N, K, nullptr));
     HIPTS_HIP(hipDeviceSynchronize());
-    HIPTS_TRY(fetch(u, ud, out_bytes, who));
-    return fetch(c, cd, out_bytes, who);
+    HIPTS_TRY(dbg_fetch(u, ud, out_bytes, who));
+    return dbg_fetch(c, cd, out_bytes, who);
 }
 
 extern "C" int hiptsdbg_patch_gather(int pixel, int window, int f16, const void* images, uint64_t image_bytes, const float* lut, int batch, int S,
@@ -229,9 +208,9 @@ extern "C" int hiptsdbg_patch_gather(int pixel, int window, int f16, const void*
     HIPTS_TRY(use_device(0));
     const int64_t tokens = (int64_t)batch * G * G, total = tokens * ks;
     DevBuf img, lutd, ad;
-    HIPTS_TRY(guarded(ad, a0_bytes, (uint64_t)tokens * (raw ? 3 * P * P : 2 * half) * 2, fill, who, "a0"));
-    HIPTS_TRY(put(img, images, image_bytes));
-    if (lut) HIPTS_TRY(put(lutd, lut, 3 * 256 * 4));
+    HIPTS_TRY(dbg_guarded(ad, a0_bytes, (uint64_t)tokens * (raw ? 3 * P * P : 2 * half) * 2, fill, who, "a0"));
+    HIPTS_TRY(dbg_put(img, images, image_bytes));
+    if (lut) HIPTS_TRY(dbg_put(lutd, lut, 3 * 256 * 4));
     const int blocks = (int)ceil_div(total, 256);
     bf16_t* a = ad.as<bf16_t>();
     const bool h = f16 != 0;
@@ -249,5 +228,5 @@ extern "C" int hiptsdbg_patch_gather(int pixel, int window, int f16, const void*
         HIPTS_LAUNCH_F16(h, patch_gather_kernel, blocks, 256, 0, nullptr, PixelF32Planes<false>{img.as<float>()}, Window7x7{}, a, total, S, G);
     }
     HIPTS_HIP(hipDeviceSynchronize());
-    return fetch(a0, ad, a0_bytes, who);
+    return dbg_fetch(a0, ad, a0_bytes, who);
 }

@@ -26,6 +26,11 @@
 //                 of merging, q | k | v and fc1 are what brings a flat picture's logits within 1e-3 of float64: its tokens share every
 //                 rounding error, which the mean over tokens then cannot average out
 //   head          row_ln_kernel with the ToF32 sink (per-token LayerNorm, float32) -> sw_mean_kernel (hi | lo, the PooledHiLo sink) -> EPI_HEAD
+// Tested one launch at a time: sw_merge_kernel, sw_split_x_kernel and sw_mean_kernel through hiptsdbg_swinv2_merge / _split_x / _mean
+// below (tests/test_gpu_tokens.py: bit for bit against the reshape / permute, exact-answer means, float64), the row_ln_kernel sinks and
+// the patch gather through csrc/rows_dbg.hip (tests/test_gpu_rows.py), the window attention through hiptsdbg_swinv2_window_attention and
+// the whole forward against swinv2_ref (tests/test_gpu_swinv2.py).  Each launch_sw_* helper is the one launch shape the forward and its
+// entry share.
 // The position-bias tables 16 sigmoid(cpb_mlp(table)) depend on the weights only: computed on the host (double, stored float32) at the
 // first forward after the last cpb_mlp tensor was set, [heads][(2 w - 1)^2] per block.
 #include <algorithm>
@@ -35,6 +40,7 @@
 #include <vector>
 
 #include "vit_internal.h"
+#include "dbg_buf.h"
 #include "model_host.h"
 #include "convnet.h"
 
@@ -118,6 +124,25 @@ __global__ __launch_bounds__(256) void sw_mean_kernel(const float* __restrict__ 
     }
 }
 
+// The three kernels' launch shapes, shared by the forward and the debug entries (hiptsdbg_swinv2_merge, _split_x, _mean).
+// rows_out: the merged rows, batch * (H / 2)^2, of 4 C values each
+int launch_sw_merge(bool f16, const float* x, bf16_t* col, int64_t rows_out, int H, int C, hipStream_t s) {
+    const int64_t total4 = rows_out * C;               // rows_out rows of 4 C, in float4
+    HIPTS_LAUNCH_F16(f16, sw_merge_kernel, ceil_div(total4, 256), 256, 0, s, x, col, total4, H, C);
+    return HIPTS_OK;
+}
+
+int launch_sw_split_x(bool f16, const float* x, bf16_t* xh2, int64_t rows, int D, hipStream_t s) {
+    const int64_t n4 = rows * D / 4;
+    HIPTS_LAUNCH_F16(f16, sw_split_x_kernel, ceil_div(n4, 256), 256, 0, s, x, xh2, n4, D);
+    return HIPTS_OK;
+}
+
+int launch_sw_mean(bool f16, const float* y, bf16_t* feat2, int batch, int T, int C, hipStream_t s) {
+    HIPTS_LAUNCH_F16(f16, sw_mean_kernel, batch, 256, 0, s, y, PooledHiLo{feat2}, T, C);
+    return HIPTS_OK;
+}
+
 // 16 sigmoid(cpb_mlp(table)) for one block: [heads][(2 w - 1)^2], table entry (dy, dx) = sign(t) log2(1 + |t|) / log2(8) with
 // t = 8 offset / (pw - 1) per axis (pw = the window, or cpb_pretrained_window when set).
 std::vector<float> sw_cpb_table(const SwBlock& B, int w, int pw, int heads) {
@@ -190,8 +215,7 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
         HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
         const LnGammaBeta norm{h->stem_nw.as<float>(), h->stem_nb.as<float>()};
         HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(M, 4), 256, 0, s, FromF32{x}, norm, ToF32And16{x, xh}, M, S0.C, c.ln_eps);
-        const int64_t n4 = M * S0.C / 4;
-        HIPTS_LAUNCH_F16(f16, sw_split_x_kernel, ceil_div(n4, 256), 256, 0, s, x, xh2, n4, S0.C);
+        HIPTS_TRY(launch_sw_split_x(f16, x, xh2, M, S0.C, s));
     }
 
     for (int si = 0; si < 4; ++si) {
@@ -201,16 +225,14 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
         if (si > 0) {
             // patch merging: 2x2 gather -> reduction GEMM -> LayerNorm (weight, bias) in place, with the 16-bit copy
             const SwStage& Pv = h->st[si - 1];
-            const int64_t total4 = (int64_t)M * Pv.C;          // M rows of 4 Cprev, in float4
-            HIPTS_LAUNCH_F16(f16, sw_merge_kernel, ceil_div(total4, 256), 256, 0, s, x, col, total4, Pv.H, Pv.C);
+            HIPTS_TRY(launch_sw_merge(f16, x, col, M, Pv.H, Pv.C, s));
             GemmArgs g = gemm_args(f16, shared_chip);
             g.A = col; g.W = St.ds_w.as<bf16_t>(); g.M = M; g.N = C; g.K = 8 * Pv.C;
             g.bias = St.ds_b.as<float>(); g.out_f32 = x;
             HIPTS_TRY(launch_gemm(EPI_BIAS, g, s));
             const LnGammaBeta norm{St.ds_nw.as<float>(), St.ds_nb.as<float>()};
             HIPTS_LAUNCH_F16(f16, row_ln_kernel, ceil_div(M, 4), 256, 0, s, FromF32{x}, norm, ToF32And16{x, xh}, (int64_t)M, C, c.ln_eps);
-            const int64_t n4 = (int64_t)M * C / 4;
-            HIPTS_LAUNCH_F16(f16, sw_split_x_kernel, ceil_div(n4, 256), 256, 0, s, x, xh2, n4, C);
+            HIPTS_TRY(launch_sw_split_x(f16, x, xh2, M, C, s));
         }
         const AddToStreamHiLo to_stream{x, xh2, xh2 + C};       // x += LN(branch); xh2 = [hi | lo] of the new x
         for (SwBlock& B : St.blocks) {
@@ -242,7 +264,7 @@ int sw_run_images(hipts_swinv2* h, const void* in_dev, bool is_u8, int i0, int b
     const LnGammaBeta head_norm{h->head_nw.as<float>(), h->head_nb.as<float>()};
     row_ln_kernel<false><<<ceil_div(ML, 4), 256, 0, s>>>(FromF32{x}, head_norm, ToF32{br}, ML, L.C, c.ln_eps);
     HIPTS_LAUNCH_CHECK();
-    HIPTS_LAUNCH_F16(f16, sw_mean_kernel, batch, 256, 0, s, br, PooledHiLo{feat2}, L.T, L.C);
+    HIPTS_TRY(launch_sw_mean(f16, br, feat2, batch, L.T, L.C, s));
     GemmArgs g = gemm_args(f16, shared_chip);
     g.A = feat2; g.W = h->head_w.as<bf16_t>(); g.M = batch; g.N = c.num_classes; g.K = 2 * L.C;
     g.bias = h->head_b.as<float>(); g.out_f32 = lg ? lg + (size_t)i0 * c.num_classes : nullptr;
@@ -520,6 +542,52 @@ int hiptsdbg_swinv2_window_attention(const float* q, const float* k, const float
         else { const uint32_t bits = (uint32_t)o16[i] << 16; memcpy(&out[i], &bits, 4); }
     }
     return HIPTS_OK;
+}
+
+// Debug / test entries (tests/test_gpu_tokens.py): sw_merge_kernel, sw_split_x_kernel and sw_mean_kernel once each, launched as the
+// forward launches them, the output filled with `fill` before and copied back whole.
+int hiptsdbg_swinv2_merge(const float* x, uint64_t x_bytes, int batch, int H, int C, int f16, int fill, uint16_t* col, uint64_t col_bytes) {
+    const char* who = "hiptsdbg_swinv2_merge";
+    HIPTS_REQUIRE(x && col, "%s: null argument", who);
+    HIPTS_REQUIRE(batch >= 1 && batch <= 4096 && H >= 2 && H <= 1024 && H % 2 == 0, "%s: H=%d must be even (batch %d)", who, H, batch);
+    HIPTS_REQUIRE(C >= 4 && C % 4 == 0 && C <= 4096, "%s: C=%d must be a multiple of 4", who, C);
+    HIPTS_REQUIRE(x_bytes >= (uint64_t)batch * H * H * C * 4, "%s: x does not cover the launch", who);
+    HIPTS_TRY(use_device(0));
+    const int64_t rows_out = (int64_t)batch * (H / 2) * (H / 2);
+    DevBuf xd, cd;
+    HIPTS_TRY(dbg_guarded(cd, col_bytes, (uint64_t)rows_out * 8 * C * 2, fill, who, "col"));
+    HIPTS_TRY(dbg_put(xd, x, x_bytes));
+    HIPTS_TRY(launch_sw_merge(f16 != 0, xd.as<float>(), cd.as<bf16_t>(), rows_out, H, C, nullptr));
+    HIPTS_HIP(hipDeviceSynchronize());
+    return dbg_fetch(col, cd, col_bytes, who);
+}
+
+int hiptsdbg_swinv2_split_x(const float* x, uint64_t x_bytes, int64_t rows, int D, int f16, int fill, uint16_t* xh2, uint64_t xh2_bytes) {
+    const char* who = "hiptsdbg_swinv2_split_x";
+    HIPTS_REQUIRE(x && xh2, "%s: null argument", who);
+    HIPTS_REQUIRE(rows >= 1 && rows <= (1 << 22) && D >= 4 && D % 4 == 0 && D <= 4096, "%s: rows=%lld, D=%d (a multiple of 4)", who, (long long)rows, D);
+    HIPTS_REQUIRE(x_bytes >= (uint64_t)rows * D * 4, "%s: x does not cover the launch", who);
+    HIPTS_TRY(use_device(0));
+    DevBuf xd, hd;
+    HIPTS_TRY(dbg_guarded(hd, xh2_bytes, (uint64_t)rows * 2 * D * 2, fill, who, "hi | lo"));
+    HIPTS_TRY(dbg_put(xd, x, x_bytes));
+    HIPTS_TRY(launch_sw_split_x(f16 != 0, xd.as<float>(), hd.as<bf16_t>(), rows, D, nullptr));
+    HIPTS_HIP(hipDeviceSynchronize());
+    return dbg_fetch(xh2, hd, xh2_bytes, who);
+}
+
+int hiptsdbg_swinv2_mean(const float* y, uint64_t y_bytes, int batch, int T, int C, int f16, int fill, uint16_t* out, uint64_t out_bytes) {
+    const char* who = "hiptsdbg_swinv2_mean";
+    HIPTS_REQUIRE(y && out, "%s: null argument", who);
+    HIPTS_REQUIRE(batch >= 1 && batch <= 4096 && T >= 1 && T <= (1 << 16) && C >= 1 && C <= 4096, "%s: unsupported shape", who);
+    HIPTS_REQUIRE(y_bytes >= (uint64_t)batch * T * C * 4, "%s: y does not cover the launch", who);
+    HIPTS_TRY(use_device(0));
+    DevBuf yd, od;
+    HIPTS_TRY(dbg_guarded(od, out_bytes, (uint64_t)batch * 2 * C * 2, fill, who, "hi | lo"));
+    HIPTS_TRY(dbg_put(yd, y, y_bytes));
+    HIPTS_TRY(launch_sw_mean(f16 != 0, yd.as<float>(), od.as<bf16_t>(), batch, T, C, nullptr));
+    HIPTS_HIP(hipDeviceSynchronize());
+    return dbg_fetch(out, od, out_bytes, who);
 }
 
 }  // extern "C"

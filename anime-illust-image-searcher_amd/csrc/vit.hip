@@ -8,6 +8,11 @@
 //   final LN + token mean (partial sums) -> finalize (hi/lo bf16 split) -> head GEMM (+sigmoid).
 // The residual stream, LN statistics, softmax and every accumulation are float32; only MFMA
 // operands are bf16.
+// Tested one launch at a time: the final norm + mean pool (pool_partial_kernel, pool_finalize_kernel) through hiptsdbg_vit_pool, which
+// launches through launch_vit_pool as the forward does and takes `splits` as an argument (tests/test_gpu_tokens.py: exact partial sums
+// and features in both orders, empty splits, float64); patchify, LayerNorm, folded LayerNorm, GEMM epilogues and attention through
+// their own entries (tests/test_gpu_rows.py, test_gpu_ln_fold.py, test_gpu_gemm_epi.py, test_gpu_attention_exact.py); the whole forward
+// against oracle/vit.py (tests/test_gpu_vit.py).
 #include <algorithm>
 #include "../../include/hip_tagsearch_debug.h"
 #include <cmath>
@@ -18,6 +23,7 @@
 #include <vector>
 
 #include "vit_internal.h"
+#include "dbg_buf.h"
 #include "model_host.h"
 #include "prof.h"
 #include "row_ln.h"
@@ -210,6 +216,16 @@ __global__ __launch_bounds__(256) void pool_finalize_kernel(const float* __restr
         const float f = (feat[d] - mean) * rstd * g[d] + bta[d];
         split_hilo<F16>(f, out[(int64_t)b * 2 * D + d], out[(int64_t)b * 2 * D + D + d]);
     }
+}
+
+// The pool's two launches: partial sums on a grid of (splits, images), then one workgroup per image sums them and writes hi | lo.
+// The forward and hiptsdbg_vit_pool both launch through here.
+int launch_vit_pool(const float* x, float* part, const float* g, const float* b, bf16_t* out, int nb, int tokens, int D, float eps, bool pool_then_norm,
+                    int splits, bool f16, hipStream_t s) {
+    pool_partial_kernel<<<dim3(splits, nb), 256, 0, s>>>(x, part, tokens, D, eps, pool_then_norm ? 0 : 1, splits);
+    HIPTS_LAUNCH_CHECK();
+    HIPTS_LAUNCH_F16(f16, pool_finalize_kernel, nb, 256, 0, s, part, g, b, out, tokens, D, eps, pool_then_norm ? 1 : 0, splits);
+    return HIPTS_OK;
 }
 
 }  // namespace
@@ -578,10 +594,8 @@ int vit_run_images(hipts_vit* h, const void* in_dev, bool is_u8, int i0, int nb,
     // final norm + mean pool (+ hi/lo split)
     {
         ProfScope ps(h, s, PC_POOL, 0.0, dM * dD * 4);
-        pool_partial_kernel<<<dim3(h->pool_splits, nb), 256, 0, s>>>(xb ? x_rm : x, pool_part, T, D, c.ln_eps, c.pool_then_norm ? 0 : 1, h->pool_splits);
-        HIPTS_LAUNCH_CHECK();
-        HIPTS_LAUNCH_F16(f16, pool_finalize_kernel, nb, 256, 0, s, pool_part, h->norm_g.as<float>(), h->norm_b.as<float>(), pooled2, T, D, c.ln_eps,
-                         c.pool_then_norm ? 1 : 0, h->pool_splits);
+        HIPTS_TRY(launch_vit_pool(xb ? x_rm : x, pool_part, h->norm_g.as<float>(), h->norm_b.as<float>(), pooled2, nb, T, D, c.ln_eps, c.pool_then_norm != 0,
+                                  h->pool_splits, f16, s));
     }
     // head (+ sigmoid, tagging.py:176)
     g = gemm_args(f16, shared_chip);
@@ -1275,6 +1289,30 @@ extern "C" int hiptsdbg_vit_patchify_u8_p16(const uint8_t* images, int batch, in
     HIPTS_HIP(hipDeviceSynchronize());
     HIPTS_HIP(hipMemcpy(a0, ad.p, a0_bytes, hipMemcpyDeviceToHost));
     return HIPTS_OK;
+}
+
+// pool_partial_kernel and pool_finalize_kernel once each through launch_vit_pool, on x float32 [batch][tokens][D] and g, b [D]: the partial
+// sums [batch][splits][D] float32 and the feature [batch][hi(D) | lo(D)] come back whole (tests/test_gpu_tokens.py).
+extern "C" int hiptsdbg_vit_pool(const float* x, uint64_t x_bytes, const float* g, const float* b, int batch, int tokens, int D, float eps, int pool_then_norm,
+                                 int splits, int f16, int fill, float* part_out, uint64_t part_bytes, uint16_t* out16, uint64_t out16_bytes) {
+    const char* who = "hiptsdbg_vit_pool";
+    HIPTS_REQUIRE(x && g && b && part_out && out16, "%s: null argument", who);
+    HIPTS_REQUIRE(batch >= 1 && batch <= 4096 && tokens >= 1 && tokens <= (1 << 16), "%s: unsupported shape", who);
+    HIPTS_REQUIRE(D >= 4 && D % 4 == 0 && D <= 1024, "%s: D=%d must be a multiple of 4, at most 1024", who, D);
+    HIPTS_REQUIRE(splits >= 1 && splits <= 32, "%s: splits=%d outside 1..32", who, splits);
+    HIPTS_REQUIRE(x_bytes >= (uint64_t)batch * tokens * D * 4, "%s: x does not cover the launch", who);
+    HIPTS_TRY(use_device(0));
+    DevBuf xd, gd, bd, pd, od;
+    HIPTS_TRY(dbg_guarded(pd, part_bytes, (uint64_t)batch * splits * D * 4, fill, who, "partial"));
+    HIPTS_TRY(dbg_guarded(od, out16_bytes, (uint64_t)batch * 2 * D * 2, fill, who, "hi | lo"));
+    HIPTS_TRY(dbg_put(xd, x, x_bytes));
+    HIPTS_TRY(dbg_put(gd, g, (size_t)D * 4));
+    HIPTS_TRY(dbg_put(bd, b, (size_t)D * 4));
+    HIPTS_TRY(launch_vit_pool(xd.as<float>(), pd.as<float>(), gd.as<float>(), bd.as<float>(), od.as<bf16_t>(), batch, tokens, D, eps, pool_then_norm != 0, splits,
+                              f16 != 0, nullptr));
+    HIPTS_HIP(hipDeviceSynchronize());
+    HIPTS_TRY(dbg_fetch(part_out, pd, part_bytes, who));
+    return dbg_fetch(out16, od, out16_bytes, who);
 }
 
 // Development aid: copy one workspace buffer of the last forward to the host (tools/determinism.py).

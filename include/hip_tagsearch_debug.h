@@ -203,6 +203,46 @@ int hiptsdbg_patch_gather(int pixel, int window, int f16, const void* images, ui
  * of 768). */
 int hiptsdbg_ccip_stem_u8(const uint8_t* images, const float* lut, int batch, int S, int f16, int fill, uint16_t* a0, uint64_t a0_bytes);
 int hiptsdbg_vit_patchify_u8_p16(const uint8_t* images, int batch, int grid, int f16, int fill, uint16_t* a0, uint64_t a0_bytes);
+/* The small file-local kernels at the head and tail of the five forwards, ONE launch each beside the kernel, with the grid and block the
+ * forward uses (each file's launch_* helper; tests/test_gpu_tokens.py against tests/tokens_ref.py).  Same conventions as above: the caller
+ * gives every buffer's byte size, an input or output smaller than the launch's extent is refused (HIPTS_ERR_INVALID, nothing launched),
+ * every output is filled whole with the byte `fill`, and copied back whole.  f16: IEEE half operands, otherwise bf16.
+ *
+ * hiptsdbg_vit_pool: pool_partial_kernel on a grid of (splits, batch), then pool_finalize_kernel (csrc/vit.hip).  x float32
+ * [batch][tokens][D]; g, b float32 [D].  pool_then_norm == 0: the feature is g * mean_t((x_t - mean) * rstd) + b; otherwise
+ * LN(mean_t x_t).  part_out: float32 [batch][splits][D], split s the sum over tokens [s * per, min(tokens, (s + 1) * per)),
+ * per = ceil(tokens / splits), zeros for a split that owns none; part_bytes >= 4 batch splits D.  out16: 16-bit patterns
+ * [batch][hi(D) | lo(D)]; out16_bytes >= 4 batch D.  Refused: D % 4 != 0, D > 1024, splits outside 1..32. */
+int hiptsdbg_vit_pool(const float* x, uint64_t x_bytes, const float* g, const float* b, int batch, int tokens, int D, float eps, int pool_then_norm,
+                      int splits, int f16, int fill, float* part_out, uint64_t part_bytes, uint16_t* out16, uint64_t out16_bytes);
+/* eva_assemble_kernel (csrc/eva.hip).  tmp float32 [batch][np][D] (the patch rows); cls, pos float32 [D] (pos: row 0 of the position table).
+ * x: float32 [batch][TS][D], row 0 of an image cls + pos, rows 1 .. np its patch rows, rows np + 1 .. TS - 1 zero; x_bytes >= 4 batch TS D.
+ * blocked != 0: xblk holds the same rows a second time as 16 x 16 blocks [m / 16][n / 16][m % 16][n % 16] over m = b TS + r; rows of a
+ * ragged last block that no image owns are not written; xblk_bytes >= 4 roundup(batch TS, 16) D.  blocked == 0: xblk (may be null)
+ * comes back holding `fill`.  Refused: TS < np + 1, D % 4 != 0, blocked with D % 16 != 0. */
+int hiptsdbg_eva_assemble(const float* tmp, uint64_t tmp_bytes, const float* cls, const float* pos, int batch, int np, int TS, int D, int blocked, int fill,
+                          float* x, uint64_t x_bytes, float* xblk, uint64_t xblk_bytes);
+/* eva_colsum_kernel (csrc/eva.hip).  x float32 [batch][TS][D]; part: float32 [batch][16][D], split s the sum of patch rows
+ * [s * per, min(np, (s + 1) * per)), per = ceil(np / 16), patch row r at row 1 + r of its image (row 0 and rows past np are not read); zeros
+ * for a split that owns none; part_bytes >= 64 batch D.  Refused: TS < np + 1, D % 4 != 0, D > 1024. */
+int hiptsdbg_eva_colsum(const float* x, uint64_t x_bytes, int batch, int np, int TS, int D, int fill, float* part, uint64_t part_bytes);
+/* The three small kernels of csrc/swinv2.hip.
+ * hiptsdbg_swinv2_merge: sw_merge_kernel.  x float32 [batch][H][H][C]; col: 16-bit patterns [batch (H / 2)^2][hi(4 C) | lo(4 C)], the 4 C
+ * columns of row (b, oy, ox) being x[b][2 oy + dy][2 ox + dx][:] for (dy, dx) = (0,0) (1,0) (0,1) (1,1) in that order; col_bytes >= 4 batch
+ * H H C.  Refused: odd H, C % 4 != 0.
+ * hiptsdbg_swinv2_split_x: sw_split_x_kernel.  x float32 [rows][D]; xh2: 16-bit patterns [rows][hi(D) | lo(D)]; xh2_bytes >= 4 rows D.
+ * Refused: D % 4 != 0.
+ * hiptsdbg_swinv2_mean: sw_mean_kernel with the PooledHiLo sink (the only one a forward launches).  y float32 [batch][T][C]; out: 16-bit
+ * patterns [batch][hi(C) | lo(C)] of (sum of the T rows in order) / T; out_bytes >= 4 batch C. */
+int hiptsdbg_swinv2_merge(const float* x, uint64_t x_bytes, int batch, int H, int C, int f16, int fill, uint16_t* col, uint64_t col_bytes);
+int hiptsdbg_swinv2_split_x(const float* x, uint64_t x_bytes, int64_t rows, int D, int f16, int fill, uint16_t* xh2, uint64_t xh2_bytes);
+int hiptsdbg_swinv2_mean(const float* y, uint64_t y_bytes, int batch, int T, int C, int f16, int fill, uint16_t* out, uint64_t out_bytes);
+/* ds_im2col_kernel (csrc/ccip.hip): the 3 x 3 stride-2 pad-1 patch matrix.  xn: 16-bit patterns [batch][H][H][C] (moved, never
+ * converted: no operand type); col: 16-bit patterns [batch (H / 2)^2][9][C], tap (ky, kx) of row (b, oy, ox) being
+ * xn[b][2 oy - 1 + ky][2 ox - 1 + kx][:], zeros outside the image; col_bytes >= 18 batch (H / 2)^2 C.  Refused: odd H, C % 8 != 0. */
+int hiptsdbg_ccip_ds_im2col(const uint16_t* xn, uint64_t xn_bytes, int batch, int H, int C, int fill, uint16_t* col, uint64_t col_bytes);
+/* cnx_cast_kernel (csrc/convnext.hip).  x float32 [4 n4]; xh: 16-bit patterns [4 n4], each value rounded to nearest even; xh_bytes >= 8 n4. */
+int hiptsdbg_convnext_cast(const float* x, uint64_t x_bytes, int64_t n4, int f16, int fill, uint16_t* xh, uint64_t xh_bytes);
 /* out_host float32 [M][N] = A W^T for bf16 bit patterns a_bf16 [M][K], w_bf16 [N][K] (plain epilogue). */
 int hiptsdbg_gemm_run(int M, int N, int K, const uint16_t* a_bf16, const uint16_t* w_bf16, float* out_host);
 /* The e4m3 operand path: a_f32 / w_f32 are quantised by the library (per-tensor power-of-two weight scale returned in

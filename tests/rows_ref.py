@@ -197,6 +197,15 @@ def e32_of(restated32, want64):
     return 4.0 * float(np.max(np.abs(np.asarray(restated32, np.float64) - want64)))
 
 
+def hilo_bounds(want, e32, f16):
+    """(bound on |hi - want|, bound on |hi + lo - want|) per element for a hi | lo pair split from a float32 v with |v - want| <= e32:
+    hi is v rounded to the operand type; lo = 16bit(v - hi) with |v - hi| <= spacing(v) / 2 <= |v| 2^-(m + 1) (m mantissa bits), rounded
+    with relative error 2^-(m + 1), or half a subnormal step of IEEE half (2^-25)"""
+    m = 10 if f16 else 7
+    want = np.abs(np.asarray(want, np.float64))
+    return spacing(want, "f16" if f16 else "bf16") + e32, want * 2.0 ** -(2 * m + 2) + 2.0 ** -25 + e32 * (1 + 2.0 ** -m)
+
+
 # ---- index maps --------------------------------------------------------------------------------------------------------------------------
 def blocked_offsets(M, D):
     """element offset of (m, n) in the blocked stream [m / 16][n / 16][m % 16][n % 16] (row_ln.h x_blk_row + x_blk_vec)"""

@@ -373,11 +373,9 @@ def test_d_pool_ln_gaussian_against_float64(hilo, f16, name, kind, mult):
     hl = got[:3 * 2 * C].reshape(3, 2 * C)
     hi, lo = R.from_op(hl[:, :C], f16).astype(np.float64), R.from_op(hl[:, C:], f16).astype(np.float64)
     print("D %s count=%dT %s: E32 = %.3g, hi error %.3g, hi + lo error %.3g" % (kind, mult, name, e32, np.max(np.abs(hi - want)), np.max(np.abs(hi + lo - want))))
-    assert np.all(np.abs(hi - want) <= R.spacing(want, "f16" if f16 else "bf16") + e32)
-    # lo = 16bit(v - hi): |v - hi| <= spacing(v) / 2 <= |v| 2^-(m + 1) (m mantissa bits), rounded with relative error 2^-(m + 1), or half a
-    # subnormal step of IEEE half (2^-25)
-    m = 10 if f16 else 7
-    assert np.all(np.abs(hi + lo - want) <= np.abs(want) * 2.0 ** -(2 * m + 2) + 2.0 ** -25 + e32 * (1 + 2.0 ** -m))
+    bound_hi, bound_sum = R.hilo_bounds(want, e32, f16)
+    assert np.all(np.abs(hi - want) <= bound_hi)
+    assert np.all(np.abs(hi + lo - want) <= bound_sum)
 
 
 # ---- E: patch gather -------------------------------------------------------------------------------------------------------------------------
