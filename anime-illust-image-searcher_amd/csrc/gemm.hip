@@ -46,6 +46,7 @@ namespace {
 #define HIPTS_MFMA_ORDER 1      // order of a phase's 16 MFMAs (below): 1 = snake, every MFMA shares an operand with its predecessor: forward +0.5 % (5461 / 5460 against 5426 / 5435 images/s, the chip is power-bound), same bits
 #endif
 #include "gemm_epi.h"
+#include "gemm_loop.h"
 
 
 template <int EPI>
@@ -141,6 +142,12 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
     }
 }
 
+// The kernel reads: prologue; then per work item -- slots, wait / barrier / stagger, K-tiles, balance, the next item's first K-tile,
+// split-K, fold table, epilogue, advance.  gemm_loop.h holds what is shared with the other loops and the host (tile walk, work item, fold
+// table, the staged-epilogue test) and, of a K-tile, the multiply of a phase.  The staging slots, the K-tile's frame, fragment reads
+// and three staging schedules, the split-K tail, the cycle stamps and the epilogue choice stand HERE as text: each was tried as a forceinline
+// function of that header and each changed registers, spills or the s_waitcnt / s_nop / ds_read counts of some instantiation, because
+// a function is simplified on its own before it is inlined (LABNOTES, "GEMM main loops", lists which and what moved).
 // OP8: e4m3 operands.  A K-tile is the same 256 rows x 128 B (now 128 elements), staged by the same code with the
 // matrices seen as 16-bit ones of K / 2 columns; one 16x16x128 MFMA (32 cycles) replaces the two 16x16x32 (16 each)
 // of a (row block, column block), so the four phases split the column blocks instead of the K halves --
@@ -163,55 +170,30 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave_m = wave >> 2, wave_n = wave & 3;
 
-    // Persistent: workgroup w walks tiles w, w + grid, w + 2 grid, ...  The grid is a multiple of 8 (or the
-    // whole problem), so every tile of a workgroup keeps its XCD and the bijective remap below still
-    // hands neighbouring tiles to the workgroups that share an L2.
     const int nwg = tiles_m * tiles_n;
-    auto tile_origin = [&](int id, int& m0, int& n0) {
-        const int bid = xcd_work_id(id, nwg);
-        if (a.raster_gn > 0) {
-            // Column groups outermost: all row panels x raster_gn column tiles, row-major inside the group, then the next group.
-            // An XCD's contiguous chunk of the order then lies inside one group (or two): its slice of W (raster_gn panels) is all the
-            // W it ever reads and stays in its L2, a round is 32 / raster_gn row panels x raster_gn column tiles, and a row panel of A
-            // is fetched once per column group.
-            const int per = tiles_m * a.raster_gn, grp = bid / per, rem = bid - grp * per;
-            const int left = tiles_n - grp * a.raster_gn, gn = left < a.raster_gn ? left : a.raster_gn;
-            m0 = (rem / gn) * TBM;
-            n0 = (grp * a.raster_gn + rem % gn) * BN;
-            return;
-        }
-        if (a.raster_gm > 0) {
-            // Wide outputs (fc1: 12 column tiles): row-major order hands the 32 workgroups of an XCD 2.7 row panels x ALL column
-            // tiles per round -- the whole W (4.7 MB) plus 1 MB of A against a 4 MB L2, so W is pulled through the fabric again every
-            // round.  Groups of raster_gm row panels, walked column-major inside the group: a round is raster_gm row panels x
-            // 32 / raster_gm column tiles, and the next rounds keep the same row panels.
-            const int per = a.raster_gm * tiles_n, grp = bid / per, rem = bid - grp * per;
-            const int left = tiles_m - grp * a.raster_gm, gm = left < a.raster_gm ? left : a.raster_gm;
-            m0 = (grp * a.raster_gm + rem % gm) * TBM;
-            n0 = (rem / gm) * BN;
-            return;
-        }
-        m0 = (bid / tiles_n) * TBM;
-        n0 = (bid % tiles_n) * BN;
-    };
     const int K = OP8 ? a.K / 2 : a.K, nt_all = K / BK;      // row stride in 16-bit units
     const int w_rows = tiles_n * BN;
-    // Work items: tiles [0, sk_first) whole, then (tile, slice) pairs; without SK an item is a tile.
+    // Work items: tiles [0, sk_first) whole, then (tile, slice) pairs; without SK an item is a tile.  (A lambda, not a function of
+    // gemm_loop.h: as one the split-K instantiations lost the frozen sk_first / sk_slices the optimiser keeps here, and 49 instructions moved.)
     const int S = SK ? a.sk_slices : 1;
     const int n_items = SK ? a.sk_first + (nwg - a.sk_first) * S : nwg;
-    auto decode = [&](int item, int& tid_, int& slice_, int& kt0_, int& ntl_) {
+    auto decode = [&](int item, WorkItem& w) {
         if (!SK || item < a.sk_first) {
-            tid_ = item; slice_ = -1; kt0_ = 0; ntl_ = nt_all;
+            w.tile = item; w.slice = -1; w.kt0 = 0; w.nt = nt_all;
         } else {
             const int j = item - a.sk_first;
-            tid_ = a.sk_first + j / S;
-            slice_ = j - (j / S) * S;
-            kt0_ = slice_ * nt_all / S;
-            ntl_ = (slice_ + 1) * nt_all / S - kt0_;
+            w.tile = a.sk_first + j / S;
+            w.slice = j - (j / S) * S;
+            w.kt0 = w.slice * nt_all / S;
+            w.nt = (w.slice + 1) * nt_all / S - w.kt0;
         }
     };
     const int scale_w = (127 - a.w_exp) * 0x01010101, scale_1 = 127 * 0x01010101;
 
+    // Cycle stamps of workgroup 8's first eight items, stamps[wave][item][slot]: 0 item start | 1 K-tile 0 landed | 2 past the stagger |
+    // 3 main loop done | 4 next item's first K-tile issued | 5 epilogue done (cycle counter); 6, 7 main loop start and end (100 MHz clock).
+    // hiptsdbg_gemm_time, hiptsdbg_gemm_clock and bench.py read them.  (A macro: as a function its test became an `and` of what is a
+    // poison-safe select here, and s_waitcnt / s_nop counts moved in every instantiation.)
     int stamp_tile = 0;
 #define PPSTAMP(idx)                                                                                     \
     do {                                                                                                 \
@@ -222,15 +204,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
             __builtin_amdgcn_sched_barrier(0);                                                           \
         }                                                                                                \
     } while (0)
-    int tile = blockIdx.x, m0, n0;      // `tile`: the work item
-    int tix, slice, kt0, nt;             // its tile, K slice (-1: whole K), first K-tile and K-tile count
-    decode(tile, tix, slice, kt0, nt);
-    tile_origin(tix, m0, n0);
+    int item = blockIdx.x, m0, n0;
+    WorkItem wi;
+    decode(item, wi);
+    tile_origin<TBM>(a, wi.tile, tiles_m, tiles_n, m0, n0);
     int par = 0;        // K-tile t of the current output tile lives in LDS stage (par + t) & 1
 
     // prologue of the first tile: K-tile 0 complete
-    if (wave * 4 < 4 * MR) stage_tile(a.A, a.M, K, m0, kt0, smem, wave, lane);     // 4 MR sub-tiles of 8 rows (wave 7 idle for MR = 7)
-    stage_tile(a.W, w_rows, K, n0, kt0, smem + TILE_BYTES, wave, lane);
+    if (wave * 4 < 4 * MR) stage_tile(a.A, a.M, K, m0, wi.kt0, smem, wave, lane);     // 4 MR sub-tiles of 8 rows (wave 7 idle for MR = 7)
+    stage_tile(a.W, w_rows, K, n0, wi.kt0, smem + TILE_BYTES, wave, lane);
     if constexpr (INT) {
         // the per-column vectors of the residual epilogue, once per workgroup (behind the first K-tile's requests; the barrier that opens
         // the first main loop publishes them)
@@ -245,11 +227,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
     for (;;) {
         // not cleared: the first product into a block in a work item takes C = 0 (ktile's FIRST); a pass of 32 MR v_mov per tile else
         f32x4 acc[MR][4];
-
         // This wave's eight staging slots of a K-tile (two per phase), as (global source pointer for
         // K-tile 1, LDS offset inside a stage).  Phase lists of 16 sub-tiles (8 rows x 128 B each), wave w
         // takes entries 2w, 2w+1:  0: W rows 0..127 | 1: W rows 128..255 | 2: A-low | 3: A-high, where
         // A-low = the rows the two wave groups multiply in phases 0/1 (8-row blocks 0..7, 16..23).
+        // (Text, not a struct of gemm_loop.h: as two local arrays beside the tile-start loop below, dst[] is vectorised into one
+        // <4 x i32> and two <2 x i32>; as a struct's members it is eight scalars or four pairs, and PATCH 256 rows went from 219 to
+        // 213 VGPRs, QK 256 rows from 241 to 231.)
         const bf16_t* src[8];
         int dst[8];
         {
@@ -259,7 +243,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
                 int grow = (isW ? n0 : m0) + rb8 * 8 + row_in;
                 const int lim = isW ? w_rows : a.M;
                 grow = grow < lim ? grow : lim - 1;
-                src[idx] = (isW ? a.W : a.A) + (size_t)grow * K + (size_t)(kt0 + 1) * BK + chunk * 8;
+                src[idx] = (isW ? a.W : a.A) + (size_t)grow * K + (size_t)(wi.kt0 + 1) * BK + chunk * 8;
                 dst[idx] = (isW ? TILE_BYTES : 0) + rb8 * 1024;
             };
             // A-low = the first 64 rows of each wave group (8-row blocks g*2*MR + 0..7): 16 sub-tiles, 2 per wave.
@@ -305,7 +289,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
         if (wave_m == 1) __builtin_amdgcn_s_barrier();      // stagger group 1 by one interval
         PPSTAMP(2);
         if (a.stamps && blockIdx.x == 8 && stamp_tile < 8 && lane == 0) a.stamps[wave * 64 + stamp_tile * 8 + 6] = wall_clock64();
-        if (HIPTS_STAGE_AHEAD && !HIPTS_STAGE_ORDER_OLD && nt > 1) {
+        if (HIPTS_STAGE_AHEAD && !HIPTS_STAGE_ORDER_OLD && wi.nt > 1) {
             // "phase 3 of K-tile -1": A-low and W-low of K-tile 1 into the other stage (the previous epilogue's scratch, free now)
             char* st1 = smem + ((par + 1) & 1) * STAGE_BYTES;
             for (int k : {4, 5, 0, 1}) {
@@ -320,11 +304,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
         // One K-tile.  FIRST (compile time; the item's first K-tile, peeled below -- a split-K slice's is K-tile kt0) : the phases that touch
         // an accumulator block first -- 0 and 2 (kk == 0); with e4m3 operands every phase has a j half of its own -- multiply onto a literal
         // zero.  0 + sum from an inline 0 and from a cleared register are the same bits.
+        // The multiply of a phase (pp_multiply) is a function of gemm_loop.h.  (The K-tile itself is a lambda here, its fragment reads
+        // and staging schedules text: as a function template with those as functions the fragment-read addresses are formed another way,
+        // and GELU 256 rows went from 353 to 274 s_waitcnt, QK 256 rows half from 297 to 275.  The reads alone as a function moved integer
+        // address instructions in 8 of 9 kernels probed; the three schedules alone as functions over src / dst / n_hi swapped two branch
+        // polarities in every 224-row kernel and moved RESID_XGI 224 rows from 222 to 223 s_waitcnt.)
         auto ktile = [&](int t, auto first_tag) __attribute__((always_inline)) {
             constexpr bool FIRST = decltype(first_tag)::value;
             const char* cur = smem + ((par + t) & 1) * STAGE_BYTES;
             char* nxt = smem + ((par + t + 1) & 1) * STAGE_BYTES;
-            const bool more = t + 1 < nt;
+            const bool more = t + 1 < wi.nt;
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 const int mh = p >> 1, kk = p & 1;
@@ -381,7 +370,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
                             if (n_hi == 2) issue(7);
                             wait_vmcnt(6 + n_hi);
                         } else if (p == 3) {
-                            if (t + 2 < nt) {
+                            if (t + 2 < wi.nt) {
                                 for (int k : {4, 5, 0, 1}) {
                                     glds16(src[k], const_cast<char*>(cur) + dst[k]);
                                     src[k] += BK;
@@ -431,38 +420,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_setprio(1);
-                if constexpr (OP8) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int jj = 0; jj < 2; ++jj) {
-                            const int j = 2 * kk + jj;
-                            const f32x4 c = FIRST ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[mh * 4 + i][j];
-                            if constexpr (EPI == EPI_VT)
-                                acc[mh * 4 + i][j] = mfma_16x16x128_e4m3(af8[i], wf8[j], c, scale_1, scale_w);
-                            else
-                                acc[mh * 4 + i][j] = mfma_16x16x128_e4m3(wf8[j], af8[i], c, scale_w, scale_1);
-                        }
-                } else {
-#pragma unroll
-                for (int ij = 0; ij < 16; ++ij) {
-                    // HIPTS_MFMA_ORDER (measurement): 0 = rows outer (the A fragment stays for four MFMAs), 1 = snake (every MFMA shares one
-                    // operand with its predecessor), 2 = columns outer (the W fragment stays)
-#if HIPTS_MFMA_ORDER == 2
-                    const int j = ij >> 2, i = ij & 3;
-#elif HIPTS_MFMA_ORDER == 1
-                    const int i = ij >> 2, j = (i & 1) ? 3 - (ij & 3) : (ij & 3);
-#else
-                    const int i = ij >> 2, j = ij & 3;
-#endif
-                    if (mh * 4 + i >= MR) continue;
-                    const f32x4 c = (FIRST && kk == 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[mh * 4 + i][j];
-                    if constexpr (EPI == EPI_VT)
-                        acc[mh * 4 + i][j] = mfma_16x16x32<F16>(af[i], wf[kk][j], c);
-                    else
-                        acc[mh * 4 + i][j] = mfma_16x16x32<F16>(wf[kk][j], af[i], c);
-                }
-                }
+                pp_multiply<EPI, MR, F16, OP8, FIRST>(p, acc, wf, af, wf8, af8, scale_w, scale_1);
                 __builtin_amdgcn_s_setprio(0);
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_barrier();
@@ -470,7 +428,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
             }
         };
         ktile(0, std::true_type{});
-        for (int t = 1; t < nt; ++t) ktile(t, std::false_type{});
+        for (int t = 1; t < wi.nt; ++t) ktile(t, std::false_type{});
         if (wave_m == 0) __builtin_amdgcn_s_barrier();      // balance the stagger
         PPSTAMP(3);
         if (a.stamps && blockIdx.x == 8 && stamp_tile < 8 && lane == 0) a.stamps[wave * 64 + stamp_tile * 8 + 7] = wall_clock64();
@@ -494,33 +452,36 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
         }
         constexpr bool FOLDABLE = EPI == EPI_VT || EPI == EPI_GELU || EPI == EPI_STAR || EPI == EPI_QK || EPI == EPI_QK_ROPE || EPI == EPI_SWIGLU ||
                                   EPI == EPI_RESID_ROWSTAT || EPI == EPI_RESID_XGI;
-        const bool fold_st = FOLDABLE && a.stat_in != nullptr;
+        const bool fold_st = FOLDABLE && a.stat_in != nullptr;      // uniform over the workgroup
         const bool fold_many = fold_st && a.stat_in_blocks > 4;      // EVA02's fc2: 22 partial pairs per row (one per 256-column tile of the SwiGLU launch)
         float2 st_pv[4];
         if (fold_st && !fold_many && tid < TBM) row_stat_request(a, m0 + tid, st_pv);
-        const int next = tile + gridDim.x;
+        const int next = item + gridDim.x;
         const bool has_next = next < n_items;
-        int m0n = 0, n0n = 0, tixn = 0, slicen = -1, kt0n = 0, ntn = nt_all;
-        const int par_next = (par + nt) & 1;
+        WorkItem wi_next{0, -1, 0, nt_all};
+        int m0n = 0, n0n = 0;
+        const int par_next = (par + wi.nt) & 1;
         if (has_next) {
-            decode(next, tixn, slicen, kt0n, ntn);
-            tile_origin(tixn, m0n, n0n);
+            decode(next, wi_next);
+            tile_origin<TBM>(a, wi_next.tile, tiles_m, tiles_n, m0n, n0n);
             char* st = smem + par_next * STAGE_BYTES;
-            if (wave * 4 < 4 * MR) stage_tile(a.A, a.M, K, m0n, kt0n, st, wave, lane);
-            stage_tile(a.W, w_rows, K, n0n, kt0n, st + TILE_BYTES, wave, lane);
+            if (wave * 4 < 4 * MR) stage_tile(a.A, a.M, K, m0n, wi_next.kt0, st, wave, lane);
+            stage_tile(a.W, w_rows, K, n0n, wi_next.kt0, st + TILE_BYTES, wave, lane);
         }
         PPSTAMP(4);
         bool run_epilogue = true;       // uniform over the workgroup
+        // (The split-K tail is text: as a function the accumulators stay <4 x float> where the slab store's bit_cast makes them
+        // <4 x i32> here, and the split-K RESID_XG kernel went from 252 to 253 s_waitcnt, 99 to 105 s_nop.)
         if constexpr (SK) {
-            if (slice >= 0) {
+            if (wi.slice >= 0) {
                 constexpr size_t SLAB = (size_t)TBM * BN * 4;
-                const int tl = tix - a.sk_first;
+                const int tl = wi.tile - a.sk_first;
                 unsigned* tickets = reinterpret_cast<unsigned*>(a.sk_ws);
                 char* slabs = reinterpret_cast<char*>(a.sk_ws) + 4096 + (size_t)tl * S * SLAB;
                 // (1) this slice's accumulators into its slab, write-through (sc1: no release fence needed, the bytes are at the memory
                 // side when vmcnt says so): [wave][i][j][lane] f32x4, 1 KB per store instruction
                 {
-                    const auto rs = __builtin_amdgcn_make_buffer_rsrc(slabs + (size_t)slice * SLAB, 0, (int)SLAB, 0x00020000);
+                    const auto rs = __builtin_amdgcn_make_buffer_rsrc(slabs + (size_t)wi.slice * SLAB, 0, (int)SLAB, 0x00020000);
                     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
                     for (int i = 0; i < MR; ++i)
@@ -566,58 +527,46 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(240))) void gem
             }
         }
         if (run_epilogue) {
-        if (fold_st) {      // uniform over the workgroup
-            if (fold_many) {
-                if (tid < TBM) st_table[tid] = row_stat(a, m0 + tid);       // sums the partials in index order (deterministic), 8 loads in flight
-            } else if (tid < TBM) st_table[tid] = row_stat_finish(a, st_pv);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        }
-        bool staged = false;
-        if constexpr (EPI == EPI_VT || EPI == EPI_GELU || EPI == EPI_STAR || EPI == EPI_QK || EPI == EPI_QK_ROPE || EPI == EPI_SWIGLU) {
-            const bool ok = EPI == EPI_VT                            ? (a.tokens % 8 == 0 && a.tokens_pad % 8 == 0)
-                            : (EPI == EPI_QK || EPI == EPI_QK_ROPE) ? (a.dim % 64 == 0)
-                                                                     : ((a.ld_out ? a.ld_out : a.N) % 8 == 0);
-            if (ok) {
-                float2* red = (EPI == EPI_SWIGLU && a.stat_part) ? sw_red : nullptr;
-                gemm_epilogue_staged<EPI, MR, F16>(a, acc, m0, n0, wave_m, wave_n, elane,
-                                                   smem + ((par + nt + 1) & 1) * STAGE_BYTES + wave * 8192, bias_pre, fold_st ? st_table : nullptr, red);
-                staged = true;
-                if constexpr (EPI == EPI_SWIGLU) {
-                    if (red) {      // uniform: the four waves that hold a row meet; sw_red is written again only after the next tile's main loop
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                        __builtin_amdgcn_s_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                        if (tid < TBM) {
-                            const float2 p0 = red[tid * 4], p1 = red[tid * 4 + 1], p2 = red[tid * 4 + 2], p3 = red[tid * 4 + 3];
-                            const int m = m0 + tid;
-                            if (m < a.M)
-                                *reinterpret_cast<float2*>(a.stat_part + 2 * ((size_t)(n0 >> 8) * a.stat_stride + m)) =
-                                    make_float2((p0.x + p1.x) + (p2.x + p3.x), (p0.y + p1.y) + (p2.y + p3.y));
+            if (fold_st) fold_publish(a, m0, tid, TBM, fold_many, st_pv, st_table);
+            // (The choice between the two epilogues is text: called from a function, the staged epilogue of the 224- and 192-row GELU
+            // kernels and the RESID_LN epilogue moved s_waitcnt counts, and SWIGLU's row sums below read `red` as ds_read_b128 pairs.)
+            bool staged = false;
+            if constexpr (staged_epilogue_built(EPI)) {
+                if (staged_epilogue_ok(EPI, a)) {
+                    float2* red = (EPI == EPI_SWIGLU && a.stat_part) ? sw_red : nullptr;
+                    gemm_epilogue_staged<EPI, MR, F16>(a, acc, m0, n0, wave_m, wave_n, elane, smem + ((par + wi.nt + 1) & 1) * STAGE_BYTES + wave * 8192, bias_pre,
+                                                       fold_st ? st_table : nullptr, red);
+                    staged = true;
+                    if constexpr (EPI == EPI_SWIGLU) {
+                        if (red) {      // uniform: the four waves that hold a row meet; sw_red is written again only after the next tile's main loop
+                            lds_table_visible();
+                            if (tid < TBM) {
+                                const float2 p0 = red[tid * 4], p1 = red[tid * 4 + 1], p2 = red[tid * 4 + 2], p3 = red[tid * 4 + 3];
+                                const int m = m0 + tid;
+                                if (m < a.M)
+                                    *reinterpret_cast<float2*>(a.stat_part + 2 * ((size_t)(n0 >> 8) * a.stat_stride + m)) =
+                                        make_float2((p0.x + p1.x) + (p2.x + p3.x), (p0.y + p1.y) + (p2.y + p3.y));
+                            }
                         }
                     }
                 }
             }
+            if (!staged)
+                gemm_epilogue<EPI, MR, F16, INT>(a, acc, m0, n0, wave_m, wave_n, elane, bias_pre, smem + ((par + wi.nt + 1) & 1) * STAGE_BYTES,
+                                                 fold_st ? st_table : nullptr, INT ? colvec : nullptr);
         }
-        if (!staged)
-            gemm_epilogue<EPI, MR, F16, INT>(a, acc, m0, n0, wave_m, wave_n, elane, bias_pre, smem + ((par + nt + 1) & 1) * STAGE_BYTES,
-                                             fold_st ? st_table : nullptr, INT ? colvec : nullptr);
-        }       // run_epilogue
         if (a.epi_prio) __builtin_amdgcn_s_setprio(0);
         if constexpr (INT) asm volatile("" ::"v"(xpf));
         PPSTAMP(5);
         ++stamp_tile;
         if (!has_next) break;
-        tile = next;
-        tix = tixn;
-        slice = slicen;
-        kt0 = kt0n;
-        nt = ntn;
+        item = next;
+        wi = wi_next;
         m0 = m0n;
         n0 = n0n;
         par = par_next;
     }
+#undef PPSTAMP
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1032,20 +981,12 @@ __global__ __launch_bounds__(256, 2) void gemm_dw_kernel(const GemmArgs a, int t
         a.stamps[wave * 64 + 3] = wall_clock64() - wall_t0;
     }
     __builtin_amdgcn_s_barrier();       // every wave is past its last fragment read; all loads have landed
-    if constexpr (EPI == EPI_VT || EPI == EPI_GELU || EPI == EPI_STAR || EPI == EPI_QK || EPI == EPI_QK_ROPE || EPI == EPI_SWIGLU) {
-        const bool ok = EPI == EPI_VT                            ? (a.tokens % 8 == 0 && a.tokens_pad % 8 == 0)
-                        : (EPI == EPI_QK || EPI == EPI_QK_ROPE) ? (a.dim % 64 == 0)
-                                                                 : ((a.ld_out ? a.ld_out : a.N) % 8 == 0);
-        if (ok) {
+    if constexpr (staged_epilogue_built(EPI)) {
+        if (staged_epilogue_ok(EPI, a)) {
             const float2* st_tab = nullptr;
             if (a.stat_in) {        // folded LayerNorm: finish this tile's 256 row statistics (one row per thread) into LDS past the staging images
-                float2 pv[4];
-                row_stat_request(a, m0 + tid, pv);
                 float2* tab = reinterpret_cast<float2*>(smem + 4 * 8192 * 2);
-                tab[tid] = row_stat_finish(a, pv);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                fold_rows<false>(a, m0 + tid, tab, tid);
                 st_tab = tab;
             }
             gemm_epilogue_staged<EPI, 8, F16>(a, acc, m0, n0, wave_m, wave_n, lane, smem + wave * 8192, nullptr, st_tab);
@@ -1245,7 +1186,7 @@ int launch_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
     HIPTS_REQUIRE(a.M >= 1 && a.N >= 1, "gemm: empty problem");
     if (epi != EPI_HEAD) HIPTS_REQUIRE(a.N % 16 == 0, "gemm: N=%d must be a multiple of 16", a.N);
     if (epi == EPI_VT) HIPTS_REQUIRE(a.M % 4 == 0 && a.tokens % 4 == 0, "gemm: V^T epilogue needs tokens %% 4 == 0");
-    if (epi == EPI_VT && a.tokens % 8 == 0 && a.tokens_pad % 8 == 0)      // the staged V^T store writes eight tokens of a column at a time
+    if (epi == EPI_VT && staged_epilogue_ok(epi, a))      // the staged V^T store writes eight tokens of a column at a time
         HIPTS_REQUIRE(a.M % 8 == 0, "gemm: V^T epilogue with tokens %% 8 == 0 needs M %% 8 == 0 (M = %d)", a.M);
     if (epi == EPI_QK || epi == EPI_VT) HIPTS_REQUIRE(a.hd_log2 == 5 || a.hd_log2 == 6, "gemm: head_dim must be 32 or 64");
     if (epi == EPI_QK || epi == EPI_QK_ROPE)
@@ -1262,12 +1203,9 @@ int launch_gemm(GemmEpilogue epi, const GemmArgs& a, hipStream_t s) {
         HIPTS_REQUIRE(a.col_u && (epi == EPI_QK || epi == EPI_QK_ROPE || epi == EPI_VT || epi == EPI_GELU || epi == EPI_SWIGLU || epi == EPI_STAR),
                       "gemm: a folded LayerNorm (rowstat) is built for the QK, QK_ROPE, VT, GELU, STAR and SWIGLU epilogues");
     if ((a.rowstat || a.stat_in) && epi != EPI_RESID_ROWSTAT && epi != EPI_RESID_XGI) {
-        // the fold lives in the LDS-staged epilogues only
-        const int ldo = a.ld_out ? a.ld_out : (epi == EPI_SWIGLU ? a.N / 2 : a.N);
-        const bool staged = (epi == EPI_QK || epi == EPI_QK_ROPE) ? a.dim % 64 == 0
-                            : epi == EPI_VT                       ? (a.tokens % 8 == 0 && a.tokens_pad % 8 == 0)
-                                                                  : ldo % 8 == 0;
-        HIPTS_REQUIRE(staged && (gemm_variant() == 1 || gemm_variant() == 4), "gemm: a folded LayerNorm needs the staged epilogue (pp / dw loops, aligned outputs)");
+        // the fold lives in the LDS-staged epilogues only: the kernels' own test (SWIGLU without ld_out writes rows of N / 2; N % 16 == 0,
+        // required above, makes N and N / 2 multiples of 8 alike)
+        HIPTS_REQUIRE(staged_epilogue_ok(epi, a) && (gemm_variant() == 1 || gemm_variant() == 4), "gemm: a folded LayerNorm needs the staged epilogue (pp / dw loops, aligned outputs)");
     }
     if (epi == EPI_RESID_ROWSTAT) HIPTS_REQUIRE((a.rowstat || a.stat_in) && a.col_u && a.out_f32, "gemm: RESID_ROWSTAT needs rowstat / stat_in, col_u and the fp32 stream");
     if (epi == EPI_SWIGLU) HIPTS_REQUIRE(!a.stat_part || a.stat_stride >= a.M, "gemm: SWIGLU stat_stride must cover M rows");
@@ -1361,4 +1299,24 @@ extern "C" int hiptsdbg_gemm_plan(int epi, int M, int N, int K, int f16, int sha
     if (features & 128) g.stamps = reinterpret_cast<unsigned long long*>(dummy);
     *out = gemm_plan((GemmEpilogue)epi, g, cus, gemm_knobs(), q4_mask);
     return gemm_plan_status(*out, (GemmEpilogue)epi);
+}
+
+// Development/test aid (not part of the public ABI), host only: the persistent loops' tile walk (gemm_loop.h tile_origin, the function
+// the kernels call) -- the origin of every id in [0, tiles_m * tiles_n) for tiles of tile_rows x 256 under a raster pair.
+extern "C" int hiptsdbg_gemm_tile_walk(int tiles_m, int tiles_n, int tile_rows, int raster_gm, int raster_gn, int32_t* m0, int32_t* n0) {
+    using namespace hipts;
+    HIPTS_REQUIRE(m0 && n0 && tiles_m >= 1 && tiles_n >= 1 && (tile_rows == 256 || tile_rows == 224 || tile_rows == 192) && raster_gm >= 0 && raster_gn >= 0,
+                  "hiptsdbg_gemm_tile_walk: bad argument");
+    GemmArgs g{};
+    g.raster_gm = raster_gm;
+    g.raster_gn = raster_gn;
+    for (int id = 0; id < tiles_m * tiles_n; ++id) {
+        int m, n;
+        if (tile_rows == 256) tile_origin<256>(g, id, tiles_m, tiles_n, m, n);
+        else if (tile_rows == 224) tile_origin<224>(g, id, tiles_m, tiles_n, m, n);
+        else tile_origin<192>(g, id, tiles_m, tiles_n, m, n);
+        m0[id] = m;
+        n0[id] = n;
+    }
+    return HIPTS_OK;
 }

@@ -29,6 +29,7 @@ namespace hipts {
 namespace {
 
 #include "gemm_epi.h"
+#include "gemm_loop.h"
 
 template <bool F16>
 __device__ __forceinline__ void q4_mfma(f32x4& acc, const bf16x8& w, const bf16x8& x) {
@@ -193,25 +194,6 @@ __global__ __launch_bounds__(256, 1) void gemm_q4_kernel(const GemmArgs a, int t
     const int wm = wave >> 1, wn = wave & 1;
 
     const int nwg = tiles_m * tiles_n;
-    auto tile_origin = [&](int id, int& m0, int& n0) {      // as gemm_pp_kernel: XCD-aware bijective remap, then the launcher's raster
-        const int bid = xcd_work_id(id, nwg);
-        if (a.raster_gn > 0) {
-            const int per = tiles_m * a.raster_gn, grp = bid / per, rem = bid - grp * per;
-            const int left = tiles_n - grp * a.raster_gn, gn = left < a.raster_gn ? left : a.raster_gn;
-            m0 = (rem / gn) * BM;
-            n0 = (grp * a.raster_gn + rem % gn) * BN;
-            return;
-        }
-        if (a.raster_gm > 0) {
-            const int per = a.raster_gm * tiles_n, grp = bid / per, rem = bid - grp * per;
-            const int left = tiles_m - grp * a.raster_gm, gm = left < a.raster_gm ? left : a.raster_gm;
-            m0 = (grp * a.raster_gm + rem % gm) * BM;
-            n0 = (rem / gm) * BN;
-            return;
-        }
-        m0 = (bid / tiles_n) * BM;
-        n0 = (bid % tiles_n) * BN;
-    };
     const int K = a.K, nt = K / BK;
     const size_t row_bytes = (size_t)K * 2;
 
@@ -246,7 +228,7 @@ __global__ __launch_bounds__(256, 1) void gemm_q4_kernel(const GemmArgs a, int t
     }
 
     int tile = blockIdx.x, m0, n0;
-    tile_origin(tile, m0, n0);
+    tile_origin<BM>(a, tile, tiles_m, tiles_n, m0, n0);
     const char* a0 = reinterpret_cast<const char*>(a.A) + (size_t)m0 * row_bytes;
     const char* w0 = reinterpret_cast<const char*>(a.W) + (size_t)n0 * row_bytes;
 
@@ -272,7 +254,7 @@ __global__ __launch_bounds__(256, 1) void gemm_q4_kernel(const GemmArgs a, int t
         const int next = tile + gridDim.x;
         const bool has_next = next < nwg;
         int m0n = m0, n0n = n0;
-        if (has_next) tile_origin(next, m0n, n0n);
+        if (has_next) tile_origin<BM>(a, next, tiles_m, tiles_n, m0n, n0n);
         const char* an = reinterpret_cast<const char*>(a.A) + (size_t)m0n * row_bytes;      // !has_next: a harmless reload of this tile's K-tile 0
         const char* wn_ = reinterpret_cast<const char*>(a.W) + (size_t)n0n * row_bytes;
 
@@ -324,15 +306,7 @@ __global__ __launch_bounds__(256, 1) void gemm_q4_kernel(const GemmArgs a, int t
         constexpr bool FOLDABLE = EPI == EPI_GELU || EPI == EPI_QK;
         const bool fold_st = FOLDABLE && a.stat_in != nullptr;
         if (fold_st) {      // uniform over the workgroup: thread t finishes row m0 + t
-            if (a.stat_in_blocks > 4) st_table[tid] = row_stat(a, m0 + tid);
-            else {
-                float2 st_pv[4];
-                row_stat_request(a, m0 + tid, st_pv);
-                st_table[tid] = row_stat_finish(a, st_pv);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            fold_rows<true>(a, m0 + tid, st_table, tid);
         }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -357,9 +331,7 @@ __global__ __launch_bounds__(256, 1) void gemm_q4_kernel(const GemmArgs a, int t
         }
         if constexpr (EPI == EPI_RESID_XG) {
             if (a.out_bf16 && a.stat_part) {      // uniform: the four wave-parts of a row have left their sums in `red`; thread t adds row t
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                lds_table_visible();
                 const float2* red = reinterpret_cast<const float2*>(scratch + 8 * 4096);
                 const float2 p0 = red[tid * 4], p1 = red[tid * 4 + 1], p2 = red[tid * 4 + 2], p3 = red[tid * 4 + 3];
                 const int m = m0 + tid;

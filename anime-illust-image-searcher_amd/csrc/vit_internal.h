@@ -57,7 +57,7 @@ __device__ __forceinline__ f32x16 mfma_32x32x16(bf16x8 a, bf16x8 b, f32x16 c) {
 // are dealt round-robin over the 8 XCDs (ids equal mod 8 share an L2), so XCD x is handed the x-th contiguous eighth of 0 .. n - 1 and
 // consecutive work items -- neighbouring GEMM tiles, the query blocks of one (image, head) -- run on ONE XCD and reuse what its L2
 // holds (attention: 1.23 GB fetched per launch against 0.23 GB algorithmic before this).
-__device__ __forceinline__ int xcd_work_id(int id, int n) {
+__host__ __device__ __forceinline__ int xcd_work_id(int id, int n) {
     const int q = n >> 3, r = n & 7, xcd = id & 7, loc = id >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
 }

@@ -83,6 +83,10 @@ typedef struct hiptsdbg_gemm_plan_t {
  * refuses returns its error (and out->error). */
 int hiptsdbg_gemm_plan(int epi, int M, int N, int K, int f16, int shared_chip, unsigned features, int ld_out, int dim, int cus,
                        unsigned q4_mask, hiptsdbg_gemm_plan_t* out);
+/* The tile walk of the persistent GEMM loops (csrc/gemm_loop.h tile_origin, the function the kernels call).  Host only, no GPU call.
+ * m0[id], n0[id]: first row and first column of the tile that work id `id` of [0, tiles_m * tiles_n) is handed, for tiles of tile_rows
+ * (256 / 224 / 192) x 256 under the raster pair (raster_gm, raster_gn) of a plan. */
+int hiptsdbg_gemm_tile_walk(int tiles_m, int tiles_n, int tile_rows, int raster_gm, int raster_gn, int32_t* m0, int32_t* n0);
 /* What the loaded code object says of the ping-pong GEMM kernel the launcher picks for (epilogue, mr = tile rows / 32, operand type,
  * e4m3 operands, split-K, interior), from hipFuncGetAttributes: VGPRs per lane, bytes of scratch (private segment) per lane -- 0 means
  * nothing is spilled --, bytes of static LDS.  A combination no kernel is built for is refused. */
